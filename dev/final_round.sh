@@ -11,9 +11,9 @@ if [ "$WHAT" = spmv ]; then
     timeout -k 10 170 dev/collect_spmv_profile.sh C2 ${TAG}_C2 > $OUT/spmv_C2.log 2>&1
 else
     # (the C3 bench runs FIRST: its value_cold is that of the first process on a freshly restored box, without any prefault -- round 4)
-    timeout -k 10 500 python bench.py > $OUT/bench.log 2> $OUT/bench.err
+    timeout -k 10 500 python bench.py --full > $OUT/bench.log 2> $OUT/bench.err
     grep "^{" $OUT/bench.log > $OUT/bench.json
-    timeout -k 10 300 python bench.py --preset C2 --N 32 --l 16 > $OUT/bench_C2.log 2> $OUT/bench_C2.err
+    timeout -k 10 300 python bench.py --full --preset C2 --N 32 --l 16 > $OUT/bench_C2.log 2> $OUT/bench_C2.err
     grep "^{" $OUT/bench_C2.log > $OUT/bench_C2.json
     timeout -k 10 300 dev/prof_bench.sh $OUT/prof_bench > $OUT/prof_bench.log 2>&1
 fi

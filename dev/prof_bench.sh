@@ -4,7 +4,7 @@ set -e
 OUT=${1:-gpurun_out/prof_bench}; shift || true
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats -d $OUT -o bench --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-newton "$@" > $OUT/log.txt 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT -o bench --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-newton "$@" > $OUT/log.txt 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True)[0]

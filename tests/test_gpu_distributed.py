@@ -153,7 +153,7 @@ def test_bench_gpus_2_launches_two_ranks_and_matches_one_rank():
     """`python bench.py --gpus 2` (no launcher): two ranks over gloo on this box's one GPU -- the N > 1 path of the scaling bench,
     entered the way a driver that only knows `--gpus N` enters it.  Same eigenvalues as the one-rank run."""
     one = _bench(["--gpus", "1"])
-    two = _bench(["--gpus", "2"], WAE_BENCH_BACKEND="gloo")
+    two = _bench(["--gpus", "2", "--full"], WAE_BENCH_BACKEND="gloo")
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2 and two["rccl_ranks"] == 2
     assert two["roofline"]["frac"] > 0 and two["solver"]["n_unconverged"] == 0
     assert one["eigenpairs"] == two["eigenpairs"] > 0
@@ -170,3 +170,21 @@ def test_bench_mgpu_mode_drives_two_handles_from_one_process():
     assert one["eigenpairs"] == two["eigenpairs"] > 0
     a, b = np.array(one["eigenvalues_hz"]), np.array(two["eigenvalues_hz"])
     assert np.max(np.abs(a - b)) <= 1e-6 * np.max(np.abs(a))
+
+
+def test_plain_bench_run_dumps_what_its_last_step_returned(tmp_path):
+    """A plain `bench.py` run measures only the headline (roofline, second cold call and the other extras are --full's);
+    `--dump-outputs DIR` writes the eigenpairs and moments of the last timed step: the eigenvalues of the JSON line, in float64."""
+    import re
+    one = _bench(["--gpus", "1", "--dump-outputs", str(tmp_path)])
+    assert not {"roofline", "newton", "value_cold_second_handle", "cpu_baseline"} & set(one)
+    out = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(out) == {"eigenvalues", "eig_residuals", "singular_values", "eigenvectors_sample", "moments_sample"}
+    assert all(a.dtype == np.float64 for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    good = out["eig_residuals"] <= 1e-6
+    assert good.sum() == one["eigenpairs"] > 0
+    assert np.allclose(out["eigenvalues"][good] / 2 / np.pi, np.array(one["eigenvalues_hz"]), rtol=1e-14, atol=0)
+    assert np.array_equal(out["singular_values"], np.array(one["singular_values"]))
+    rows = min(int(re.search(r"d=(\d+)", one["config"]["workload"]).group(1)), 16384)
+    assert out["eigenvectors_sample"].shape == (rows, len(out["eigenvalues"]), 2)
+    assert out["moments_sample"].shape == (rows, 8, 4, 2)
