@@ -7,6 +7,7 @@ shift-invert Arnoldi on the GPU); only scalar updates and the tiny Hessenberg ei
 """
 from __future__ import annotations
 
+import time
 from math import factorial
 
 import numpy as np
@@ -45,6 +46,27 @@ def decode_error_flag(flag):
 
 class EigsError(RuntimeError):
     """stands where Arpack.ARPACKException stands in the reference (Householder.jl:140)"""
+
+
+def _ritz(H, nev, tol, d):
+    """The host half of one run of a shift-invert Arnoldi process (`eigs`, `eigs_many`, `eigs_many_slots`): the Hessenberg matrix H
+    ((m+1) x m) of the device trimmed to the steps taken and cut at an invariant subspace, its eigenpairs sorted by decreasing |theta|,
+    the residual estimate |H[m,m-1]| |Y[m-1,:k]| of the k = min(nev, m) wanted Ritz pairs and the stop test.  Returns
+    (theta, Y, m, k, done)."""
+    m = H.shape[1]
+    while m > 1 and not H[:, m - 1].any():   # steps not taken (early exit on the device): zero columns
+        m -= 1
+    taken = m
+    for j in range(m):                       # invariant subspace: H[j+1,j] == 0
+        if H[j + 1, j] == 0:
+            m = j + 1
+            break
+    theta, Y = np.linalg.eig(H[:m, :m])
+    order = np.argsort(-np.abs(theta))
+    theta, Y = theta[order], Y[:, order]
+    k = min(nev, m)
+    res = np.abs(H[m, m - 1]) * np.abs(Y[m - 1, :k])
+    return theta, Y, m, k, bool(np.all(res <= tol * np.abs(theta[:k])) or m < taken or m >= d)
 
 
 def eigs(A, M, nev=1, v0=None, ncv=None, tol=1e-12, maxiter=300, sigma=0.0, return_gap=False):
@@ -96,25 +118,13 @@ def eigs(A, M, nev=1, v0=None, ncv=None, tol=1e-12, maxiter=300, sigma=0.0, retu
             failed_runs += 1
             if failed_runs >= 2:
                 raise EigsError(f"inner solves stalled at relative residual {fam.last_info['relres_max']:.1e}")
-        m = step
-        while m > 1 and not H[:, m - 1].any():   # steps not taken (early exit on the device): zero columns
-            m -= 1
-        taken = m
-        for j in range(m):                   # invariant subspace: H[j+1,j] == 0
-            if H[j + 1, j] == 0:
-                m = j + 1
-                break
-        theta, Yr = np.linalg.eig(H[:m, :m])
-        order = np.argsort(-np.abs(theta))
-        theta, Yr = theta[order], Yr[:, order]
-        k = min(nev, m)
-        res = np.abs(H[m, m - 1]) * np.abs(Yr[m - 1, :k])
+        theta, Yr, m, k, done = _ritz(H, nev, tol, d)
         X = V[:, :m] @ Yr[:, :k]
         X = X / np.linalg.norm(X, axis=0)
         last = (sig_out + 1.0 / theta[:k], X)
         if m > k:
             gap = abs(1.0 / theta[k])          # crude estimate of the next eigenvalue's modulus
-        if np.all(res <= tol * np.abs(theta[:k])) or m < taken or m >= d:
+        if done:
             return last + (gap,) if return_gap else last
         v = X @ np.ones(k)                    # restart with the wanted Ritz vectors
     if last is None:
@@ -139,110 +149,147 @@ def householder_update(f):
         + 10 * f[0] ** 2 * f[1] * (-9 * f[2] ** 2 + f[0] * f[4]) + f[0] ** 3 * (20 * f[2] * f[3] - f[0] * f[5]))
 
 
-def _aux_step(L, z, order, nev, v0, v0_adj, update, state):
-    """one pass of the loop body shared by householder and mslp (Householder.jl:96-120).
-    ``state`` carries |lam| and the gap estimate of the previous pass to choose the regularising shift."""
-    L.params[L.eigval] = z
-    L.params[L.auxval] = 0
-    A = L(z)
-    M = L.term_operator(len(L.terms) - 1, -1.0)          # M = -L.terms[end].coeff
-    sigma = 0.0
-    gap_prev, lam_prev = state.get("gap", np.inf), state.get("lam", np.inf)
-    if np.isfinite(gap_prev) and lam_prev < 1e-4 * gap_prev:
-        sigma = 1e-5 * gap_prev
-    lam, v, gap = eigs(A, M, nev=nev, v0=v0, sigma=sigma, return_gap=True)
-    lam_adj, v_adj = eigs(A.H, M.H, nev=nev, v0=v0_adj, sigma=sigma)
-    state["gap"] = gap if np.isfinite(gap) else gap_prev
-    state["lam"] = float(np.min(np.abs(lam)))
-    idx = np.argsort(np.abs(lam)); lam, v = lam[idx], v[:, idx]
-    idx = np.argsort(np.abs(lam_adj)); lam_adj, v_adj = lam_adj[idx], v_adj[:, idx]
-    cand = []
-    L.active = [L.auxval, L.eigval]
-    try:
-        # fewer than nev pairs come back when the Krylov space is numerically invariant (z on an eigenvalue: one
-        # shift-invert step already spans it); the candidates are then the pairs that exist
-        for i in range(min(nev, len(lam), len(lam_adj))):
-            L.params[L.auxval] = lam[i]
-            sol = Solution(L.params, v[:, i], v_adj[:, i], L.auxval)
-            perturb_(sol, L, L.eigval, order, mode="householder")
-            cand.append(update(sol.eigval_pert[f"{L.eigval}/Taylor"]))
-    finally:
-        L.active = [L.eigval]
-    return lam, v, v_adj, cand
+def _taylor_update(c):
+    """`householder_update` on the Taylor coefficients c of the auxiliary eigenvalue (the derivatives are i! c[i])"""
+    return householder_update([factorial(i) * ci for i, ci in enumerate(c)])
 
 
-def _normalise(L, v0, v0_adj):
-    """Householder.jl:189-190"""
-    M = L.term_operator(len(L.terms) - 1, -1.0)
-    v0 = v0 / np.sqrt(np.vdot(v0, M @ v0))
+def _mass(L):
+    """the coefficients of M = -L.terms[end].coeff (Householder.jl:92)"""
+    c = np.zeros(len(L.terms), dtype=np.complex128)
+    c[-1] = -1.0
+    return c
+
+
+def _shift(state):
+    """the shift of the next two Arnoldi processes (see `eigs`): 1e-5 of the gap estimate once |lam| fell below 1e-4 of it.  `state`
+    carries |lam| and the gap estimate of the previous Newton step."""
+    gap, lam = state.get("gap", np.inf), state.get("lam", np.inf)
+    return 1e-5 * gap if np.isfinite(gap) and lam < 1e-4 * gap else 0.0
+
+
+def _flag(n, maxiter, lam, lam_tol, z, z0, tol):
+    """Householder.jl:150-171: the flag of an iteration that ended without an exception"""
+    if n >= maxiter:
+        return -1
+    elif abs(lam) <= lam_tol:
+        return 1
+    elif abs(z - z0) <= tol:
+        return 0
+    elif np.isnan(z):
+        return -5
+    return -3
+
+
+def _derivative(L):
+    """the coefficients of L'(z) at the current parameters (Householder.jl:190)"""
     saved = L.active, L.mode
     L.active, L.mode = [L.eigval], "all"
     try:
-        v0_adj = v0_adj / np.conj(np.vdot(v0_adj, L(L.params[L.eigval], 1) @ v0))
+        return L.coefficients(L.params[L.eigval], 1)
     finally:
         L.active, L.mode = saved
-    return v0, v0_adj
 
 
-def _aux_step_slots(L, fam, z, order, update, state):
-    """`_aux_step` for nev = 1 with the eigenvector pair resident in HBM: v0 / v0_adj are column 0 of the slots _SV / _SW of the family,
-    the Ritz vectors of the two Arnoldi processes go to column 0 of _SXR / _SXL and the perturbation step reads them there.  Returns
-    (lam, candidate update)."""
-    L.params[L.eigval] = z
-    L.params[L.auxval] = 0
-    T = len(L.terms)
-    cA = np.array([L.coefficients(z)])
-    cM = np.zeros(T, dtype=np.complex128)
-    cM[T - 1] = -1.0                                      # M = -L.terms[end].coeff
-    sigma = 0.0
-    gap_prev, lam_prev = state.get("gap", np.inf), state.get("lam", np.inf)
-    if np.isfinite(gap_prev) and lam_prev < 1e-4 * gap_prev:
-        sigma = 1e-5 * gap_prev
-    right = eigs_many_slots(fam, cA, cM, _SV, [0], OP_N, [sigma], _SXR, stol=L.solver_tol, smax=L.solver_maxit)[0]
-    left = eigs_many_slots(fam, cA, cM, _SW, [0], OP_C, [sigma], _SXL, stol=L.solver_tol, smax=L.solver_maxit)[0]
-    for r in (right, left):
-        if isinstance(r, Exception):
-            raise r
-    lam, gap = right
-    state["gap"] = gap if np.isfinite(gap) else gap_prev
-    state["lam"] = float(abs(lam))
-    L.params[L.auxval] = lam
-    try:
-        cand = update(eigval_series_slots(L, L.auxval, L.eigval, order, _SXR, 0, _SXL, 0))
-    finally:
-        L.active = [L.eigval]
-    return lam, cand
+def _lib_flag(e):
+    """Householder.jl:139-146: the flag of an iteration a library error ended (-6: singular)"""
+    return -6 if e.code == -2 else -2
 
 
-def _slots_begin(L, fam, v0, v0_adj):
-    """the eigenvector pair of a single-start iteration into column 0 of the slots (v0_adj None: conj(v0), Householder.jl:84-86)"""
-    d = L.size()
-    fam.slot_write(_SV, np.ones((d, 1), dtype=np.complex128) if v0 is None else np.asarray(v0, dtype=np.complex128).reshape(d, 1))
-    if v0_adj is None:
-        fam.slot_write(_SW, None, ncols_total=1)
-        fam.slot_axpby(_SW, [0], _SV, [0], alpha=1.0, beta=0.0, conj_src=True)
-    else:
-        fam.slot_write(_SW, np.asarray(v0_adj, dtype=np.complex128).reshape(d, 1))
-    fam.slot_write(_SXR, None, ncols_total=1)
-    fam.slot_write(_SXL, None, ncols_total=1)
+# `householder`'s flags as `mslp` reports them (iterative_solvers.jl:4-14); `padesolve` maps them back
+_ITSOL = {1: itsol_converged, 0: itsol_slow_convergence, -1: itsol_maxiter, -5: itsol_isnan, -3: itsol_impossible,
+          -4: itsol_arpack_exception, -6: itsol_singular_exception, -2: itsol_unknown}
 
 
-def _slots_finish(L, fam):
-    """`_normalise` (Householder.jl:189-190) on the slots, then the pair back to the host: (v0, v0_adj)"""
-    T = len(L.terms)
-    cM = np.zeros(T, dtype=np.complex128)
-    cM[T - 1] = -1.0
-    nv = fam.slot_forms(cM, _SV, [0], _SV, [0])
-    fam.slot_axpby(_SV, [0], _SV, [0], alpha=1.0 / np.sqrt(nv), beta=0.0)
-    saved = L.active, L.mode
-    L.active, L.mode = [L.eigval], "all"
-    try:
-        cD = np.array([L.coefficients(L.params[L.eigval], 1)])
-    finally:
-        L.active, L.mode = saved
-    dw = fam.slot_forms(cD, _SW, [0], _SV, [0])
-    fam.slot_axpby(_SW, [0], _SW, [0], alpha=1.0 / np.conj(dw), beta=0.0)
-    return fam.slot_read(_SV, 0, 1)[:, 0], fam.slot_read(_SW, 0, 1)[:, 0]
+class _HostPair:
+    """The eigenvector pair (v0, v0_adj) of a single-start iteration in host memory, with the loop body of `householder` and `mslp`
+    (Householder.jl:96-120) around it: nev candidate pairs per step from two `eigs` runs, their eigenvalue series through wae_perturb."""
+
+    def __init__(self, L, nev, v0, v0_adj):
+        self.L, self.nev = L, nev
+        self.v = np.ones(L.size(), dtype=np.complex128) if v0 is None else np.asarray(v0, dtype=np.complex128)
+        self.v_adj = np.conj(self.v) if v0_adj is None else np.asarray(v0_adj, dtype=np.complex128)
+
+    def step(self, z, order, update, state):
+        """one pass of the loop body at z: the candidate eigenvalues (ascending modulus) and their updates"""
+        L = self.L
+        L.params[L.eigval] = z
+        L.params[L.auxval] = 0
+        A = L(z)
+        M = L.term_operator(len(L.terms) - 1, -1.0)          # M = -L.terms[end].coeff
+        sigma = _shift(state)
+        lam, v, gap = eigs(A, M, nev=self.nev, v0=self.v, sigma=sigma, return_gap=True)
+        lam_adj, v_adj = eigs(A.H, M.H, nev=self.nev, v0=self.v_adj, sigma=sigma)
+        state["gap"] = gap if np.isfinite(gap) else state.get("gap", np.inf)
+        state["lam"] = float(np.min(np.abs(lam)))
+        idx = np.argsort(np.abs(lam)); lam, self.vr = lam[idx], v[:, idx]
+        idx = np.argsort(np.abs(lam_adj)); lam_adj, self.vl = lam_adj[idx], v_adj[:, idx]
+        cand = []
+        L.active = [L.auxval, L.eigval]
+        try:
+            # fewer than nev pairs come back when the Krylov space is numerically invariant (z on an eigenvalue: one
+            # shift-invert step already spans it); the candidates are then the pairs that exist
+            for i in range(min(self.nev, len(lam), len(lam_adj))):
+                L.params[L.auxval] = lam[i]
+                sol = Solution(L.params, self.vr[:, i], self.vl[:, i], L.auxval)
+                perturb_(sol, L, L.eigval, order, mode="householder")
+                cand.append(update(sol.eigval_pert[f"{L.eigval}/Taylor"]))
+        finally:
+            L.active = [L.eigval]
+        return lam, cand
+
+    def relax(self, i, relax):
+        """v0 = (1 - relax) v0 + relax v with candidate i, both vectors (Householder.jl:173-176)"""
+        self.v = (1 - relax) * self.v + relax * self.vr[:, i]
+        self.v_adj = (1 - relax) * self.v_adj + relax * self.vl[:, i]
+
+    def finish(self):
+        """the pair normalised as Householder.jl:189-190: (v0, v0_adj)"""
+        L = self.L
+        M = L.term_operator(len(L.terms) - 1, -1.0)
+        v0 = self.v / np.sqrt(np.vdot(self.v, M @ self.v))
+        return v0, self.v_adj / np.conj(np.vdot(self.v_adj, Operator(L.device(), _derivative(L), OP_N, L) @ v0))
+
+
+class _SlotPair:
+    """`_HostPair` for nev = 1 with the pair resident in HBM: column 0 of the slots of `householder_many` (a `_SlotStore` of one column).
+    The Ritz vectors of the two Arnoldi processes stay in the slots and the perturbation step reads them there; the pair comes back once,
+    normalised, at the end."""
+
+    def __init__(self, L, v0, v0_adj):
+        self.L = L
+        self.store = _SlotStore(L, L.ensure_solver(), 1, v0, v0_adj, {})
+
+    def step(self, z, order, update, state):
+        """`_HostPair.step` for the one candidate: ([lam], [update])"""
+        L = self.L
+        L.params[L.eigval] = z
+        L.params[L.auxval] = 0
+        cA = np.array([L.coefficients(z)])
+        sig = [_shift(state)]
+        right = self.store.arnoldi(cA, [0], OP_N, sig)[0]
+        left = self.store.arnoldi(cA, [0], OP_C, sig)[0]
+        for r in (right, left):
+            if isinstance(r, Exception):
+                raise r
+        lam, gap = right
+        state["gap"] = gap if np.isfinite(gap) else state.get("gap", np.inf)
+        state["lam"] = float(abs(lam))
+        L.params[L.auxval] = lam
+        try:
+            cand = update(self.store.series(0, order))
+        finally:
+            L.active = [L.eigval]
+        return [lam], [cand]
+
+    def relax(self, i, relax):
+        self.store.relax([0], relax)
+
+    def finish(self):
+        """`_HostPair.finish` on the slots, then the pair back to the host"""
+        self.store.normalise(np.array([_derivative(self.L)]))
+        V, W = self.store.read()
+        return V[:, 0], W[:, 0]
 
 
 def householder(L, z, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, nev=1, v0=None, v0_adj=None, output=False, resident=True):
@@ -250,21 +297,16 @@ def householder(L, z, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, n
     (Householder.jl:70-192; flags 1 converged / 0 slow / -1 maxiter / -4 eigs / -6 singular / -5 NaN)
     nev = 1 (the default) runs the device-resident iteration of `householder_many` for the one start value: the eigenvector pair stays
     in HBM between the Arnoldi processes, the perturbation step and the update (0.49 -> 0.26 s per call at 1M DoF); resident=False or
-    nev > 1: the vectors pass through host memory between the library calls, as below."""
+    nev > 1: the vectors pass through host memory between the library calls (`_HostPair`)."""
     if resident and nev == 1:
-        d = L.size()
-        return householder_many(L, [z], maxiter=maxiter, tol=tol, relax=relax, lam_tol=lam_tol, order=order,
-                                v0s=None if v0 is None else np.asarray(v0, dtype=np.complex128).reshape(d, 1),
-                                v0s_adj=None if v0_adj is None else np.asarray(v0_adj, dtype=np.complex128).reshape(d, 1), output=output,
-                                _single=True)[0]
+        return householder_many(L, [z], maxiter=maxiter, tol=tol, relax=relax, lam_tol=lam_tol, order=order, v0s=v0, v0s_adj=v0_adj,
+                                output=output, _single=True)[0]
     z = complex(z)
     z0 = complex(np.inf)
     lam = np.inf
     n = 0
     active, mode = L.active, L.mode
-    d = L.size()
-    v0 = np.ones(d, dtype=np.complex128) if v0 is None else np.asarray(v0, dtype=np.complex128)
-    v0_adj = np.conj(v0) if v0_adj is None else np.asarray(v0_adj, dtype=np.complex128)
+    pair = _HostPair(L, nev, v0, v0_adj)
     flag = 1
     history = []
     state = {}
@@ -274,36 +316,24 @@ def householder(L, z, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, n
                 print(n, "\t\t", abs(lam), "\t", abs(z - z0), "\t", z)
             history.append(z)
             z0 = z
-            lams, v, v_adj, dzs = _aux_step(L, z, order, nev, v0, v0_adj,
-                                            lambda c: householder_update([factorial(i) * ci for i, ci in enumerate(c)]), state)
+            lams, dzs = pair.step(z, order, _taylor_update, state)
             i = int(np.argsort(np.abs(dzs))[0])
             lam = lams[i]
             L.params[L.auxval] = lam
             z = z + relax * dzs[i]
-            v0 = (1 - relax) * v0 + relax * v[:, i]
-            v0_adj = (1 - relax) * v0_adj + relax * v_adj[:, i]
+            pair.relax(i, relax)
             n += 1
     except EigsError:
         flag = -4
     except WaeError as e:
-        flag = -6 if e.code == -2 else -2
+        flag = _lib_flag(e)
         L.params[L.eigval] = z
     if flag == 1:
         L.params[L.eigval] = z
         history.append(z)
-        if n >= maxiter:
-            flag = -1
-        elif abs(lam) <= lam_tol:
-            flag = 1
-        elif abs(z - z0) <= tol:
-            flag = 0
-        elif np.isnan(z):
-            flag = -5
-        else:
-            flag = -3
+        flag = _flag(n, maxiter, lam, lam_tol, z, z0, tol)
     L.active, L.mode = active, mode
-    v0, v0_adj = _normalise(L, v0, v0_adj)
-    sol = Solution(L.params, v0, v0_adj, L.eigval)
+    sol = Solution(L.params, *pair.finish(), L.eigval)
     sol.history = history
     return sol, n, flag
 
@@ -312,7 +342,7 @@ def mslp(L, z, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, nev=1, v
          scale=1.0, output=False, resident=True):
     """sol, n, flag = mslp(L, z; ...)   (iterative_solvers.jl:93-252)
     nev = 1 (the default): the eigenvector pair stays in HBM between the Arnoldi processes, the perturbation step and the update
-    (`_aux_step_slots`); resident=False or nev > 1: through host memory (`_aux_step`)."""
+    (`_SlotPair`); resident=False or nev > 1: through host memory (`_HostPair`)."""
     z = complex(z) * scale
     tol = tol * scale
     z0 = complex(np.inf)
@@ -320,21 +350,15 @@ def mslp(L, z, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, nev=1, v
     lam0 = np.inf
     n = 0
     active, mode = L.active, L.mode
-    d = L.size()
-    on_dev = bool(resident) and nev == 1
-    if not on_dev:
-        v0 = np.ones(d, dtype=np.complex128) if v0 is None else np.asarray(v0, dtype=np.complex128)
-        v0_adj = np.conj(v0) if v0_adj is None else np.asarray(v0_adj, dtype=np.complex128)
-    flag = itsol_converged
+    flag = 1
     if L.terms[-1].operator != "__aux__":          # iterative_solvers.jl:119-123
+        d = L.size()
         L.push(Term(-sp.identity(d, dtype=np.complex128, format="csr"), (pow1,), (("__aux__",),), "__aux__", "__aux__"))
         L.auxval = "__aux__"
+    # (after the push: the family on the device has the aux term)
+    pair = _SlotPair(L, v0, v0_adj) if resident and nev == 1 else _HostPair(L, nev, v0, v0_adj)
     history = []
     state = {}
-    fam = None
-    if on_dev:
-        fam = L.ensure_solver()                    # (after the push: the family on the device has the aux term)
-        _slots_begin(L, fam, v0, v0_adj)
     try:
         while abs(z - z0) > tol and n < maxiter:
             if output:
@@ -347,11 +371,7 @@ def mslp(L, z, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, nev=1, v
                 pades.append((num, den))
                 roots = poly_roots(num)
                 return roots[np.argsort(np.abs(roots))[0]]
-            if on_dev:
-                lam1, dz1 = _aux_step_slots(L, fam, z, order, upd, state)
-                lams, dzs = [lam1], [dz1]
-            else:
-                lams, v, v_adj, dzs = _aux_step(L, z, order, nev, v0, v0_adj, upd, state)
+            lams, dzs = pair.step(z, order, upd, state)
             if not np.isinf(z0):
                 back = [lam0 - polyval(num, z0 - z) / polyval(den, z0 - z) for num, den in pades]
                 i = int(np.argsort(np.abs(back))[0])
@@ -362,36 +382,21 @@ def mslp(L, z, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, nev=1, v
             z0 = z
             lam0 = lam
             z = z + relax * dzs[i]
-            if on_dev:
-                fam.slot_axpby(_SV, [0], _SXR, [0], alpha=relax, beta=1.0 - relax)
-                fam.slot_axpby(_SW, [0], _SXL, [0], alpha=relax, beta=1.0 - relax)
-            else:
-                v0 = (1 - relax) * v0 + relax * v[:, i]
-                v0_adj = (1 - relax) * v0_adj + relax * v_adj[:, i]
+            pair.relax(i, relax)
             n += 1
     except EigsError:
-        flag = itsol_arpack_exception
+        flag = -4
     except WaeError as e:
-        flag = itsol_singular_exception if e.code == -2 else itsol_unknown
+        flag = _lib_flag(e)
         L.params[L.eigval] = z
-    if flag == itsol_converged:
+    if flag == 1:
         L.params[L.eigval] = z
         history.append(z)
-        if n >= maxiter:
-            flag = itsol_maxiter
-        elif abs(lam) <= lam_tol:
-            flag = itsol_converged
-        elif abs(z - z0) <= tol:
-            flag = itsol_slow_convergence
-        elif np.isnan(z):
-            flag = itsol_isnan
-        else:
-            flag = itsol_impossible
+        flag = _flag(n, maxiter, lam, lam_tol, z, z0, tol)
     L.active, L.mode = active, mode
-    v0, v0_adj = _slots_finish(L, fam) if on_dev else _normalise(L, v0, v0_adj)
-    sol = Solution(L.params, v0, v0_adj, L.eigval)
+    sol = Solution(L.params, *pair.finish(), L.eigval)
     sol.history = history
-    return sol, n, flag
+    return sol, n, _ITSOL[flag]
 
 
 def padesolve(L, z, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, nev=1, v0=None, v0_adj=None, output=False,
@@ -536,7 +541,6 @@ def count_poles_and_zeros(L, G, N=16, output=False):
         s += np.trace(X) * w
     return s / 2 / np.pi / 1j
 
-
 # ------------------------------------------------------------------------------------------------------
 # many start values at once: the Newton-type refinement of all the estimates a Beyn solve returned, in lock-step.
 # A single-column solve is latency-bound on the device (0.65 ms per Krylov iteration whether the batch holds one column
@@ -573,26 +577,12 @@ def eigs_many(fam, cA, cM, v0s, op, sigmas, nev=1, tol=1e-12, maxiter=300, stol=
         failed = fam.last_info["n_unconverged"] > 0 and fam.last_info["relres_max"] > 1e-4
         still = []
         for q, s in enumerate(pending):
-            Hs, Vs = H[q], V[q]
-            m = step
-            while m > 1 and not Hs[:, m - 1].any():
-                m -= 1
-            taken = m
-            for j in range(m):
-                if Hs[j + 1, j] == 0:
-                    m = j + 1
-                    break
-            theta, Yr = np.linalg.eig(Hs[:m, :m])
-            order = np.argsort(-np.abs(theta))
-            theta, Yr = theta[order], Yr[:, order]
-            k = min(nev, m)
-            res = np.abs(Hs[m, m - 1]) * np.abs(Yr[m - 1, :k])
-            X = Vs[:, :m] @ Yr[:, :k]
+            theta, Yr, m, k, done = _ritz(H[q], nev, tol, d)
+            X = V[q][:, :m] @ Yr[:, :k]
             for jj in range(k):                           # (BLAS dot + in-place scaling: np.linalg.norm and a division cost three passes
                 X[:, jj] *= 1.0 / np.sqrt(np.vdot(X[:, jj], X[:, jj]).real)      # with temporaries over 16 MB per vector)
-            gap = abs(1.0 / theta[k]) if m > k else np.inf
-            out[s] = (sig_out[s] + 1.0 / theta[:k], X, gap)
-            if not (np.all(res <= tol * np.abs(theta[:k])) or m < taken or m >= d):
+            out[s] = (sig_out[s] + 1.0 / theta[:k], X, abs(1.0 / theta[k]) if m > k else np.inf)
+            if not done:
                 if failed:
                     out[s] = EigsError("inner solves stalled")
                 else:
@@ -625,151 +615,9 @@ def _conjugate_span_coefficients(V):
 
 
 def _conjugate_span_start(V):
-    """conj(V C), C = _conjugate_span_coefficients(V) (host arrays: householder_many_host)"""
+    """conj(V C), C = _conjugate_span_coefficients(V) (host arrays: `_HostStore`)"""
     C = _conjugate_span_coefficients(V)
     return np.conj(V) if C is None else np.conj(V @ C)
-
-
-def householder_many_host(L, zs, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, v0s=None, v0s_adj=None, output=False, stats=None):
-    """`householder_many` with every vector passing through host memory between the device calls (wae_arnoldi_shiftinvert_batch,
-    wae_perturb, wae_spmv_sum): the form of rounds 2-3, kept as the cross-check of the device-resident one below
-    (tests/test_gpu_parity.py) and for `householder_many(..., resident=False)`."""
-    import time as _time
-    st_ = {"right_arnoldi_seconds": 0.0, "left_arnoldi_seconds": 0.0, "perturbation_seconds": 0.0, "newton_rounds": 0,
-           "inner_column_iterations": 0}
-    zs = [complex(z) for z in zs]
-    ns = len(zs)
-    if ns == 0:                                           # an empty batch of start values: nothing to refine
-        if stats is not None:
-            stats.update(st_)
-        return []
-    d = L.size()
-    fam = L.ensure_solver()
-    active, mode = L.active, L.mode
-    # (column-major: every start value's vectors are contiguous -- the updates below touch 16 MB columns at 1M DoF)
-    V = np.ones((d, ns), dtype=np.complex128, order="F") if v0s is None else np.array(np.asarray(v0s, dtype=np.complex128).reshape(d, ns), order="F")
-    W = np.array(_conjugate_span_start(V) if v0s_adj is None else np.asarray(v0s_adj, dtype=np.complex128).reshape(d, ns), order="F")
-    z = list(zs)
-    z0 = [complex(np.inf)] * ns
-    lam = [np.inf] * ns
-    n = [0] * ns
-    flag = [1] * ns
-    hist = [[] for _ in range(ns)]
-    state = [dict() for _ in range(ns)]
-    T = len(L.terms)
-    cM = np.zeros(T, dtype=np.complex128)
-    cM[T - 1] = -1.0                                      # M = -L.terms[end].coeff  (Householder.jl:92)
-    upd = lambda c: householder_update([factorial(i) * ci for i, ci in enumerate(c)])   # noqa: E731
-    while True:
-        act = [s for s in range(ns) if flag[s] == 1 and abs(z[s] - z0[s]) > tol and n[s] < maxiter]
-        if not act:
-            break
-        cA, sig = [], []
-        for s in act:
-            hist[s].append(z[s])
-            z0[s] = z[s]
-            L.params[L.eigval] = z[s]
-            L.params[L.auxval] = 0
-            cA.append(L.coefficients(z[s]))
-            gp, lp = state[s].get("gap", np.inf), state[s].get("lam", np.inf)
-            sig.append(1e-5 * gp if (np.isfinite(gp) and lp < 1e-4 * gp) else 0.0)
-        cA = np.array(cA)
-        try:
-            st_["newton_rounds"] += 1
-            t_ = _time.perf_counter()
-            allact = len(act) == ns
-            right = eigs_many(fam, cA, cM, V if allact else [V[:, s] for s in act], OP_N, sig, stol=L.solver_tol, smax=L.solver_maxit, stats=st_)
-            st_["right_arnoldi_seconds"] += _time.perf_counter() - t_
-            t_ = _time.perf_counter()
-            left = eigs_many(fam, cA, cM, W if allact else [W[:, s] for s in act], OP_C, sig, stol=L.solver_tol, smax=L.solver_maxit, stats=st_)
-            st_["left_arnoldi_seconds"] += _time.perf_counter() - t_
-        except WaeError as e:
-            for s in act:
-                flag[s] = -6 if e.code == -2 else -2
-            break
-        for q, s in enumerate(act):
-            if isinstance(right[q], Exception) or isinstance(left[q], Exception):
-                flag[s] = -4
-                continue
-            lam_r, v_r, gap = right[q]
-            lam_l, v_l, _ = left[q]
-            state[s]["gap"] = gap if np.isfinite(gap) else state[s].get("gap", np.inf)
-            state[s]["lam"] = float(np.min(np.abs(lam_r)))
-            L.params[L.eigval] = z[s]
-            L.params[L.auxval] = lam_r[0]
-            L.active = [L.auxval, L.eigval]
-            try:
-                t_ = _time.perf_counter()
-                sol = Solution(L.params, v_r[:, 0], v_l[:, 0], L.auxval)
-                perturb_(sol, L, L.eigval, order, mode="householder")
-                dz = upd(sol.eigval_pert[f"{L.eigval}/Taylor"])
-                st_["perturbation_seconds"] += _time.perf_counter() - t_
-            except WaeError as e:
-                flag[s] = -6 if e.code == -2 else -2
-                continue
-            finally:
-                L.active = [L.eigval]
-            lam[s] = lam_r[0]
-            if output:
-                print(s, n[s], "\t", abs(lam[s]), "\t", abs(dz), "\t", z[s])
-            z[s] = z[s] + relax * dz
-            if relax == 1.0:
-                V[:, s] = v_r[:, 0]
-                W[:, s] = v_l[:, 0]
-            else:
-                V[:, s] = (1 - relax) * V[:, s] + relax * v_r[:, 0]
-                W[:, s] = (1 - relax) * W[:, s] + relax * v_l[:, 0]
-            n[s] += 1
-    # Householder.jl:189-190 for all start values at once: v / sqrt(v' M v), v_adj / conj(v_adj' L'(z) v) -- two batched operator
-    # products (the same term coefficients `_normalise` forms one start value at a time)
-    t_ = _time.perf_counter()
-    cMn = np.zeros(T, dtype=np.complex128)
-    cMn[T - 1] = -1.0
-    MV = fam.spmv(cMn, V)
-    for s in range(ns):
-        V[:, s] *= 1.0 / np.sqrt(np.vdot(V[:, s], MV[:, s]))          # (a complex in-place division is ten times slower)
-    del MV
-    cD = np.zeros((ns, T), dtype=np.complex128)
-    saved_p = dict(L.params)
-    L.active, L.mode = [L.eigval], "all"
-    try:
-        for s in range(ns):
-            L.params[L.eigval] = z[s]
-            L.params[L.auxval] = lam[s] if np.isfinite(lam[s]) else 0
-            cD[s] = L.coefficients(z[s], 1)
-    finally:
-        L.active, L.mode = active, mode
-        L.params.update(saved_p)
-    DV = fam.spmv(cD, V)
-    for s in range(ns):
-        W[:, s] *= 1.0 / np.conj(np.vdot(W[:, s], DV[:, s]))
-    del DV
-    st_["normalisation_seconds"] = _time.perf_counter() - t_
-    out = []
-    for s in range(ns):
-        f = flag[s]
-        L.params[L.eigval] = z[s]
-        L.params[L.auxval] = lam[s] if np.isfinite(lam[s]) else 0
-        if f == 1:
-            hist[s].append(z[s])
-            if n[s] >= maxiter:
-                f = -1
-            elif abs(lam[s]) <= lam_tol:
-                f = 1
-            elif abs(z[s] - z0[s]) <= tol:
-                f = 0
-            elif np.isnan(z[s]):
-                f = -5
-            else:
-                f = -3
-        L.active, L.mode = active, mode
-        sol = Solution(L.params, V[:, s], W[:, s], L.eigval)        # (columns of the local column-major arrays: contiguous views, no copies)
-        sol.history = hist[s]
-        out.append((sol, n[s], f))
-    L.active, L.mode = active, mode
-    if stats is not None:
-        stats.update(st_)
-    return out
 
 
 # slots of the family the lock-step Newton iteration keeps its vectors in (the upper half of DeviceFamily.NSLOTS: 0-3 stay the caller's)
@@ -799,24 +647,11 @@ def eigs_many_slots(fam, cA, cM, v0_slot, cols, op, sigmas, out_slot, tol=1e-12,
         ny = 1
         still = []
         for q, s in enumerate(pending):
-            Hs = H[q]
-            m = step
-            while m > 1 and not Hs[:, m - 1].any():
-                m -= 1
-            taken = m
-            for j in range(m):
-                if Hs[j + 1, j] == 0:
-                    m = j + 1
-                    break
-            theta, Yr = np.linalg.eig(Hs[:m, :m])
-            order = np.argsort(-np.abs(theta))
-            theta, Yr = theta[order], Yr[:, order]
-            res = np.abs(Hs[m, m - 1]) * np.abs(Yr[m - 1, 0])
+            theta, Yr, m, _, done = _ritz(H[q], 1, tol, d)
             Y[q, :m] = Yr[:, 0]
             ny = max(ny, m)
-            gap = abs(1.0 / theta[1]) if m > 1 else np.inf
-            out[s] = (sig_out[s] + 1.0 / theta[0], gap)
-            if not (res <= tol * np.abs(theta[0]) or m < taken or m >= d):
+            out[s] = (sig_out[s] + 1.0 / theta[0], abs(1.0 / theta[1]) if m > 1 else np.inf)
+            if not done:
                 if failed:
                     out[s] = EigsError("inner solves stalled")
                 else:
@@ -827,22 +662,133 @@ def eigs_many_slots(fam, cA, cM, v0_slot, cols, op, sigmas, out_slot, tol=1e-12,
     return out
 
 
+# The vectors of `householder_many`, in one of two stores.  Both keep V, W (the right and left start vectors, column s: start value s) and
+# the Ritz vectors of the last Arnoldi round, and give the lock-step loop the same six steps: start (the constructor), `arnoldi` (the
+# right or left processes of the active columns), `series` (the eigenvalue series of one column), `relax` (v0 = (1 - relax) v0 + relax v,
+# Householder.jl:173-176, for the columns that moved), `normalise` (Householder.jl:189-190) and `read`.
+
+class _HostStore:
+    """Every vector in host memory, passed to the library at each call (wae_arnoldi_shiftinvert_batch, wae_perturb, wae_spmv_sum): the
+    form of rounds 2-3, kept as the cross-check of `_SlotStore` (tests/test_gpu_slots.py) and for `householder_many(..., resident=False)`."""
+
+    def __init__(self, L, fam, ns, v0s, v0s_adj, stats):
+        d = L.size()
+        self.L, self.fam, self.cM, self.stats = L, fam, _mass(L), stats
+        # (column-major: every start value's vectors are contiguous -- the updates below touch 16 MB columns at 1M DoF)
+        self.V = (np.ones((d, ns), dtype=np.complex128, order="F") if v0s is None
+                  else np.array(np.asarray(v0s, dtype=np.complex128).reshape(d, ns), order="F"))
+        self.W = np.array(_conjugate_span_start(self.V) if v0s_adj is None else np.asarray(v0s_adj, dtype=np.complex128).reshape(d, ns),
+                          order="F")
+        self.ritz = {}
+
+    def arnoldi(self, cA, act, op, sig):
+        """the processes of the columns `act` (op OP_N: right, from V; OP_C: left, from W): per column (lam, gap) or an EigsError"""
+        X = self.V if op == OP_N else self.W
+        out = eigs_many(self.fam, cA, self.cM, X if len(act) == X.shape[1] else [X[:, s] for s in act], op, sig,
+                        stol=self.L.solver_tol, smax=self.L.solver_maxit, stats=self.stats)
+        self.ritz[op] = {s: r[1][:, 0] for s, r in zip(act, out) if not isinstance(r, Exception)}
+        return [r if isinstance(r, Exception) else (r[0][0], r[2]) for r in out]
+
+    def series(self, s, order):
+        L = self.L
+        L.active = [L.auxval, L.eigval]
+        sol = Solution(L.params, self.ritz[OP_N][s], self.ritz[OP_C][s], L.auxval)
+        perturb_(sol, L, L.eigval, order, mode="householder")
+        return sol.eigval_pert[f"{L.eigval}/Taylor"]
+
+    def relax(self, moved, relax):
+        for s in moved:
+            if relax == 1.0:
+                self.V[:, s] = self.ritz[OP_N][s]
+                self.W[:, s] = self.ritz[OP_C][s]
+            else:
+                self.V[:, s] = (1 - relax) * self.V[:, s] + relax * self.ritz[OP_N][s]
+                self.W[:, s] = (1 - relax) * self.W[:, s] + relax * self.ritz[OP_C][s]
+
+    def normalise(self, cD):
+        """two batched operator products (the term coefficients `_HostPair.finish` forms one start value at a time)"""
+        V, W = self.V, self.W
+        MV = self.fam.spmv(self.cM, V)
+        for s in range(V.shape[1]):
+            V[:, s] *= 1.0 / np.sqrt(np.vdot(V[:, s], MV[:, s]))          # (a complex in-place division is ten times slower)
+        del MV
+        DV = self.fam.spmv(cD, V)
+        for s in range(V.shape[1]):
+            W[:, s] *= 1.0 / np.conj(np.vdot(W[:, s], DV[:, s]))
+
+    def read(self):
+        return self.V, self.W
+
+
+class _SlotStore:
+    """Every vector resident in HBM: V, W in slots _SV, _SW, the Ritz vectors in _SXR, _SXL.  The start vectors go to the device once
+    (wae_slot_write), the Arnoldi processes start from slot columns and leave their Ritz vectors in slot columns
+    (wae_arnoldi_shiftinvert_slots, wae_arnoldi_ritz_to_slot), the perturbation step reads them there (wae_perturb_slots), the relaxed
+    update and the normalisations are slot operations (wae_slot_axpby, wae_slot_forms), and the eigenvectors come back once at the end.
+    The host sees Hessenberg matrices and scalars."""
+
+    def __init__(self, L, fam, ns, v0s, v0s_adj, stats):
+        d = L.size()
+        self.L, self.fam, self.cM, self.stats = L, fam, _mass(L), stats
+        self.cols = allc = list(range(ns))
+        t_ = time.perf_counter()
+        fam.slot_write(_SV, np.ones((d, ns), dtype=np.complex128, order="F") if v0s is None
+                       else np.asarray(v0s, dtype=np.complex128).reshape(d, ns))
+        if v0s_adj is None:
+            # the conjugate-span start W = conj(V C): the small matrix C from the caller's array, the combination on the device (column i of V,
+            # conjugated, into every column of W with its weight)
+            Cs = None if v0s is None else _conjugate_span_coefficients(np.asarray(v0s, dtype=np.complex128).reshape(d, ns))
+            fam.slot_write(_SW, None, ncols_total=ns)
+            if Cs is None:
+                fam.slot_axpby(_SW, allc, _SV, allc, alpha=1.0, beta=0.0, conj_src=True)
+            else:
+                for i in range(ns):
+                    fam.slot_axpby(_SW, allc, _SV, [i] * ns, alpha=np.conj(Cs[i, :]), beta=0.0 if i == 0 else 1.0, conj_src=True)
+        else:
+            fam.slot_write(_SW, np.asarray(v0s_adj, dtype=np.complex128).reshape(d, ns))
+        fam.slot_write(_SXR, None, ncols_total=ns)
+        fam.slot_write(_SXL, None, ncols_total=ns)
+        stats["upload_seconds"] = time.perf_counter() - t_
+
+    def arnoldi(self, cA, act, op, sig):
+        """`_HostStore.arnoldi`; the Ritz vectors go to _SXR (right) or _SXL (left)"""
+        src, dst = (_SV, _SXR) if op == OP_N else (_SW, _SXL)
+        return eigs_many_slots(self.fam, cA, self.cM, src, act, op, sig, dst, stol=self.L.solver_tol, smax=self.L.solver_maxit,
+                               stats=self.stats)
+
+    def series(self, s, order):
+        L = self.L
+        return eigval_series_slots(L, L.auxval, L.eigval, order, _SXR, s, _SXL, s)
+
+    def relax(self, moved, relax):
+        if moved:
+            self.fam.slot_axpby(_SV, moved, _SXR, moved, alpha=relax, beta=1.0 - relax)
+            self.fam.slot_axpby(_SW, moved, _SXL, moved, alpha=relax, beta=1.0 - relax)
+
+    def normalise(self, cD):
+        """two batched forms"""
+        fam, c = self.fam, self.cols
+        nv = fam.slot_forms(self.cM, _SV, c, _SV, c)
+        fam.slot_axpby(_SV, c, _SV, c, alpha=1.0 / np.sqrt(nv), beta=0.0)
+        dw = fam.slot_forms(cD, _SW, c, _SV, c)
+        fam.slot_axpby(_SW, c, _SW, c, alpha=1.0 / np.conj(dw), beta=0.0)
+
+    def read(self):
+        t_ = time.perf_counter()
+        V = self.fam.slot_read(_SV, 0, len(self.cols))
+        W = self.fam.slot_read(_SW, 0, len(self.cols))
+        self.stats["download_seconds"] = time.perf_counter() - t_
+        return V, W
+
+
 def householder_many(L, zs, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, v0s=None, v0s_adj=None, output=False, stats=None, resident=True,
                      _single=False):
     """[(sol, n, flag), ...] = householder_many(L, zs; ...): `householder` (Householder.jl:70-192) for several start values, the device
-    work (two shift-invert Arnoldi processes per Newton step and start value) batched over the start values, and every vector of the
-    iteration resident in HBM: the estimates go to the device once (wae_slot_write), the Arnoldi processes start from slot columns and
-    leave their Ritz vectors in slot columns (wae_arnoldi_shiftinvert_slots, wae_arnoldi_ritz_to_slot), the perturbation step reads them
-    there (wae_perturb_slots), the relaxed update and the two normalisations of Householder.jl:173-176,189-190 are slot operations
-    (wae_slot_axpby, wae_slot_forms), and the eigenvectors come back once at the end.  The host sees Hessenberg matrices and scalars.
-    (Through host memory -- householder_many_host, resident=False -- a step of 8 start values at 1M DoF moved 2 GB over PCIe and the
-    GPU idled 45 % of the time.)
+    work (two shift-invert Arnoldi processes per Newton step and start value) batched over the start values.  resident=True (the
+    default): every vector of the iteration stays in HBM (`_SlotStore`); resident=False: the vectors pass through host memory between
+    the library calls (`_HostStore`: a step of 8 start values at 1M DoF moved 2 GB over PCIe and the GPU idled 45 % of the time).
     stats (optional dict): receives the seconds spent in the right / left Arnoldi processes and in the perturbation step, the
     number of lock-step Newton rounds and the inner (Krylov) column-iterations."""
-    if not resident:
-        return householder_many_host(L, zs, maxiter=maxiter, tol=tol, relax=relax, lam_tol=lam_tol, order=order, v0s=v0s, v0s_adj=v0s_adj,
-                                     output=output, stats=stats)
-    import time as _time
     st_ = {"right_arnoldi_seconds": 0.0, "left_arnoldi_seconds": 0.0, "perturbation_seconds": 0.0, "newton_rounds": 0,
            "inner_column_iterations": 0}
     zs = [complex(z) for z in zs]
@@ -851,30 +797,9 @@ def householder_many(L, zs, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, orde
         if stats is not None:
             stats.update(st_)
         return []
-    d = L.size()
     fam = L.ensure_solver()
     active, mode = L.active, L.mode
-    allc = list(range(ns))
-    t_ = _time.perf_counter()
-    if v0s is None:
-        fam.slot_write(_SV, np.ones((d, ns), dtype=np.complex128, order="F"))
-    else:
-        fam.slot_write(_SV, np.asarray(v0s, dtype=np.complex128).reshape(d, ns))
-    if v0s_adj is None:
-        # the conjugate-span start W = conj(V C): the small matrix C from the caller's array, the combination on the device (column i of V,
-        # conjugated, into every column of W with its weight)
-        Cs = None if v0s is None else _conjugate_span_coefficients(np.asarray(v0s, dtype=np.complex128).reshape(d, ns))
-        fam.slot_write(_SW, None, ncols_total=ns)
-        if Cs is None:
-            fam.slot_axpby(_SW, allc, _SV, allc, alpha=1.0, beta=0.0, conj_src=True)
-        else:
-            for i in range(ns):
-                fam.slot_axpby(_SW, allc, _SV, [i] * ns, alpha=np.conj(Cs[i, :]), beta=0.0 if i == 0 else 1.0, conj_src=True)
-    else:
-        fam.slot_write(_SW, np.asarray(v0s_adj, dtype=np.complex128).reshape(d, ns))
-    fam.slot_write(_SXR, None, ncols_total=ns)
-    fam.slot_write(_SXL, None, ncols_total=ns)
-    st_["upload_seconds"] = _time.perf_counter() - t_
+    store = (_SlotStore if resident else _HostStore)(L, fam, ns, v0s, v0s_adj, st_)
     z = list(zs)
     z0 = [complex(np.inf)] * ns
     lam = [np.inf] * ns
@@ -882,10 +807,6 @@ def householder_many(L, zs, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, orde
     flag = [1] * ns
     hist = [[] for _ in range(ns)]
     state = [dict() for _ in range(ns)]
-    T = len(L.terms)
-    cM = np.zeros(T, dtype=np.complex128)
-    cM[T - 1] = -1.0                                      # M = -L.terms[end].coeff  (Householder.jl:92)
-    upd = lambda c: householder_update([factorial(i) * ci for i, ci in enumerate(c)])   # noqa: E731
     while True:
         act = [s for s in range(ns) if flag[s] == 1 and abs(z[s] - z0[s]) > tol and n[s] < maxiter]
         if not act:
@@ -899,20 +820,19 @@ def householder_many(L, zs, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, orde
             L.params[L.eigval] = z[s]
             L.params[L.auxval] = 0
             cA.append(L.coefficients(z[s]))
-            gp, lp = state[s].get("gap", np.inf), state[s].get("lam", np.inf)
-            sig.append(1e-5 * gp if (np.isfinite(gp) and lp < 1e-4 * gp) else 0.0)
+            sig.append(_shift(state[s]))
         cA = np.array(cA)
         try:
             st_["newton_rounds"] += 1
-            t_ = _time.perf_counter()
-            right = eigs_many_slots(fam, cA, cM, _SV, act, OP_N, sig, _SXR, stol=L.solver_tol, smax=L.solver_maxit, stats=st_)
-            st_["right_arnoldi_seconds"] += _time.perf_counter() - t_
-            t_ = _time.perf_counter()
-            left = eigs_many_slots(fam, cA, cM, _SW, act, OP_C, sig, _SXL, stol=L.solver_tol, smax=L.solver_maxit, stats=st_)
-            st_["left_arnoldi_seconds"] += _time.perf_counter() - t_
+            t_ = time.perf_counter()
+            right = store.arnoldi(cA, act, OP_N, sig)
+            st_["right_arnoldi_seconds"] += time.perf_counter() - t_
+            t_ = time.perf_counter()
+            left = store.arnoldi(cA, act, OP_C, sig)
+            st_["left_arnoldi_seconds"] += time.perf_counter() - t_
         except WaeError as e:
             for s in act:
-                flag[s] = -6 if e.code == -2 else -2
+                flag[s] = _lib_flag(e)
             break
         moved = []
         for q, s in enumerate(act):
@@ -925,12 +845,11 @@ def householder_many(L, zs, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, orde
             L.params[L.eigval] = z[s]
             L.params[L.auxval] = lam_r
             try:
-                t_ = _time.perf_counter()
-                series = eigval_series_slots(L, L.auxval, L.eigval, order, _SXR, s, _SXL, s)
-                dz = upd(series)
-                st_["perturbation_seconds"] += _time.perf_counter() - t_
+                t_ = time.perf_counter()
+                dz = _taylor_update(store.series(s, order))
+                st_["perturbation_seconds"] += time.perf_counter() - t_
             except WaeError as e:
-                flag[s] = -6 if e.code == -2 else -2
+                flag[s] = _lib_flag(e)
                 continue
             finally:
                 L.active = [L.eigval]
@@ -940,14 +859,10 @@ def householder_many(L, zs, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, orde
             z[s] = z[s] + relax * dz
             moved.append(s)
             n[s] += 1
-        if moved:                                         # v0 = (1 - relax) v0 + relax v  (Householder.jl:173-176), both vectors, on the device
-            fam.slot_axpby(_SV, moved, _SXR, moved, alpha=relax, beta=1.0 - relax)
-            fam.slot_axpby(_SW, moved, _SXL, moved, alpha=relax, beta=1.0 - relax)
-    # Householder.jl:189-190 for all start values at once: v / sqrt(v' M v), v_adj / conj(v_adj' L'(z) v) -- two batched forms
-    t_ = _time.perf_counter()
-    nv = fam.slot_forms(cM, _SV, allc, _SV, allc)
-    fam.slot_axpby(_SV, allc, _SV, allc, alpha=1.0 / np.sqrt(nv), beta=0.0)
-    cD = np.zeros((ns, T), dtype=np.complex128)
+        store.relax(moved, relax)
+    # Householder.jl:189-190 for all start values at once: v / sqrt(v' M v), v_adj / conj(v_adj' L'(z) v)
+    t_ = time.perf_counter()
+    cD = np.zeros((ns, len(L.terms)), dtype=np.complex128)
     saved_p = dict(L.params)
     L.active, L.mode = [L.eigval], "all"
     try:
@@ -958,13 +873,9 @@ def householder_many(L, zs, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, orde
     finally:
         L.active, L.mode = active, mode
         L.params.update(saved_p)
-    dw = fam.slot_forms(cD, _SW, allc, _SV, allc)
-    fam.slot_axpby(_SW, allc, _SW, allc, alpha=1.0 / np.conj(dw), beta=0.0)
-    st_["normalisation_seconds"] = _time.perf_counter() - t_
-    t_ = _time.perf_counter()
-    V = fam.slot_read(_SV, 0, ns)
-    W = fam.slot_read(_SW, 0, ns)
-    st_["download_seconds"] = _time.perf_counter() - t_
+    store.normalise(cD)
+    st_["normalisation_seconds"] = time.perf_counter() - t_
+    V, W = store.read()
     out = []
     for s in range(ns):
         f = flag[s]
@@ -972,21 +883,16 @@ def householder_many(L, zs, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, orde
         L.params[L.auxval] = lam[s] if np.isfinite(lam[s]) else 0
         if f == 1:
             hist[s].append(z[s])
-            if n[s] >= maxiter:
-                f = -1
-            elif abs(lam[s]) <= lam_tol:
-                f = 1
-            elif abs(z[s] - z0[s]) <= tol:
-                f = 0
-            elif np.isnan(z[s]):
-                f = -5
-            else:
-                f = -3
-        L.active, L.mode = active, mode
+            f = _flag(n[s], maxiter, lam[s], lam_tol, z[s], z0[s], tol)
         sol = Solution(L.params, V[:, s], W[:, s], L.eigval)        # (columns of the local column-major arrays: contiguous views, no copies)
         sol.history = hist[s]
         out.append((sol, n[s], f))
-    L.active, L.mode = active, mode
     if stats is not None:
         stats.update(st_)
     return out
+
+
+def householder_many_host(L, zs, maxiter=10, tol=0.0, relax=1.0, lam_tol=np.inf, order=1, v0s=None, v0s_adj=None, output=False, stats=None):
+    """`householder_many(..., resident=False)`: every vector passes through host memory between the device calls"""
+    return householder_many(L, zs, maxiter=maxiter, tol=tol, relax=relax, lam_tol=lam_tol, order=order, v0s=v0s, v0s_adj=v0s_adj,
+                            output=output, stats=stats, resident=False)
