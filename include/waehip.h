@@ -302,6 +302,34 @@ int wae_perturb_slots(wae_family *h, const double *coeff_table, int32_t N, int32
                       int32_t norm_mode, const double *coeffsY, double tol, int32_t maxit, double *lambda_out, double *v_out,
                       wae_solve_info *info);
 
+/* -- batched adjoint perturbation -----------------------------------------------------------------------------------
+ * The recurrence of wae_perturb (perturbation.jl:319-367,374-444,487-560; the wrappers LinOpFam.jl:546-618) for nsys eigenpairs in
+ * lock-step: what a user does with the handful of modes a Beyn solve returned (expand each of them in tau, n, ...).  Every system has
+ * its own base eigenvalue and parameter point -- its own coefficient table --, its own right and left vector; per order the library
+ * runs ONE tall-skinny product, ONE multi-input operator product and ONE lock-step solve with nsys coefficient sets for the whole
+ * batch, where nsys calls of wae_perturb run nsys one-column solves one after another.
+ *   nsys          1 .. the solver batch width (opts[6] of wae_solver_setup); anything else: WAE_ERR_INVALID.  nsys = 1 computes what
+ *                 wae_perturb computes.
+ *   coeff_tables  nsys tables, each laid out as wae_perturb's coeff_table, one after the other
+ *   v0, v0adj     d x nsys column-major, host   (wae_perturb_batch)
+ *   v_slot, v_cols, vadj_slot, vadj_cols   the same vectors as nsys slot columns each   (wae_perturb_batch_slots)
+ *   norm_mode     as in wae_perturb (0, 1, 2; +16: eigenvalue series only); coeffsY: one row of T coefficients shared by all systems
+ *   lambda_out    nsys x (N+1) complex, system-major (entry 0 of every row untouched)
+ *   v_out         nsys blocks of d x (N+1), column-major; may be NULL; NOT written with norm_mode + 16
+ *   status_out    (may be NULL) one code per system: WAE_OK, WAE_WARN_MAXITER (an inner solve of that system ended above tol), or
+ *                 WAE_ERR_NAN (its normalisation or an eigenvalue coefficient was not finite: the system is given up, its remaining
+ *                 coefficients and vectors are zero).  The columns of a lock-step solve are independent: a system that fails neither
+ *                 stops the others nor changes their results.
+ *   info          maxima and sums over all systems and orders, as in wae_beyn_moments_mgpu
+ * Returns WAE_OK, or WAE_WARN_MAXITER / WAE_WARN_STAGNATION if any status is not WAE_OK.  All work space -- d*(N+1)*nsys for the
+ * series, d*T*nsys input columns and five vectors of d*nsys -- is allocated by the call and released when it returns. */
+int wae_perturb_batch(wae_family *h, int32_t nsys, const double *coeff_tables, int32_t N, const double *v0, const double *v0adj,
+                      int32_t norm_mode, const double *coeffsY, double tol, int32_t maxit, double *lambda_out, double *v_out,
+                      int32_t *status_out, wae_solve_info *info);
+int wae_perturb_batch_slots(wae_family *h, int32_t nsys, const double *coeff_tables, int32_t N, int32_t v_slot, const int32_t *v_cols,
+                            int32_t vadj_slot, const int32_t *vadj_cols, int32_t norm_mode, const double *coeffsY, double tol,
+                            int32_t maxit, double *lambda_out, double *v_out, int32_t *status_out, wae_solve_info *info);
+
 /* -- P1 assembly on the device (input production) ------------------------------------------------
  * Mass and stiffness matrices of the P1 tetrahedral discretisation, as `discretize` assembles them for the "interior"
  * domain (src/Helmholtz.jl:405-441 with the element kernels src/FEM/FEM.jl:704-710,1745-1766):

@@ -412,6 +412,71 @@ function perturb_norm!(sol::Solution, fam::DeviceFamily, param::Symbol, N::Int; 
     _perturb_wrapper!(sol, fam, param, N, mode, 2; cY=cY)
 end
 
+"`perturb!` (kind = :plain), `perturb_fast!` (:fast) or `perturb_norm!` (:norm) for a vector of solutions, expanded in lock-step by ONE
+device call per group of at most `batch` solutions (wae_perturb_batch; perturbation.jl:319-367,374-444,487-560, LinOpFam.jl:546-618).
+Every solution is expanded at its own `params`; each receives `eigval_pert` / `v_pert` as from the single call.  Returns the library's
+per-solution status codes (0: every inner solve of that pair converged)."
+function perturb_many!(sols::Vector{Solution}, fam::DeviceFamily, param::Symbol, N::Int; kind::Symbol=:fast, mode::Symbol=:compact, batch::Int=64)
+    isempty(sols) && return Int32[]
+    ensure_solver!(fam)
+    L = fam.L; T = length(L.terms); d = length(sols[1].v)
+    norm_mode = mode == :householder ? 16 : Dict(:plain => 0, :fast => 1, :norm => 2)[kind]
+    cY = nothing
+    if norm_mode == 2
+        cY = zeros(ComplexF64, T); cY[end] = -1
+    end
+    key = Symbol("$(string(param))/Taylor")
+    status = zeros(Int32, length(sols))
+    active, params, current_mode = L.active, L.params, L.mode
+    tables = zeros(ComplexF64, T, N + 1, N + 1, length(sols))       # table s: [(m*(N+1)+n)*T + k] in C order = [k, n+1, m+1, s] here
+    try
+        for (s, sol) in enumerate(sols)
+            L.params = sol.params; L.active = [sol.eigval, param]; L.mode = mode
+            for m in 0:N, n in 0:N-m
+                tables[:, n+1, m+1, s] = coefficients(L, m, n)
+            end
+        end
+    finally
+        L.active, L.mode, L.params = active, current_mode, params
+    end
+    for i0 in 1:batch:length(sols)
+        idx = i0:min(i0 + batch - 1, length(sols)); ns = length(idx)
+        V0 = zeros(ComplexF64, d, ns); W0 = zeros(ComplexF64, d, ns)
+        for (j, i) in enumerate(idx)
+            V0[:, j] = sols[i].v; W0[:, j] = sols[i].v_adj
+        end
+        tab = tables[:, :, :, idx]
+        lam = zeros(ComplexF64, N + 1, ns); V = zeros(ComplexF64, d, N + 1, ns); st = zeros(Int32, ns); info = Ref{SolveInfo}()
+        code = check(ccall((:wae_perturb_batch, libwaehip), Cint,
+                    (Ptr{Cvoid}, Int32, Ptr{ComplexF64}, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}, Int32, Ptr{ComplexF64}, Float64, Int32,
+                     Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Int32}, Ref{SolveInfo}),
+                    fam.handle, ns, tab, N, V0, W0, norm_mode, cY === nothing ? C_NULL : cY, fam.tol, fam.maxit, lam, V, st, info))
+        report(code, info[], "perturb_batch ($ns systems, order $N)"; quiet=(mode == :householder))
+        status[idx] = st
+        for (j, i) in enumerate(idx)
+            lj = lam[:, j]; lj[1] = sols[i].params[sols[i].eigval]
+            sols[i].eigval_pert[key], sols[i].v_pert[key] = lj, [V[:, k, j] for k in 1:N+1]
+        end
+    end
+    return status
+end
+
+"wae_perturb_batch_slots: the eigenvalue series lam[0..N] of `ns` eigenpairs held in slot columns (1-based `v_cols`, `w_cols`), one
+coefficient table per pair (`tables`: T x (N+1) x (N+1) x ns as in `perturb_many!`); no vector leaves the device.  Returns (lam, status)."
+function perturb_batch_slots(fam::DeviceFamily, tables::Array{ComplexF64,4}, N::Int, v_slot::Integer, v_cols::Vector{Int}, w_slot::Integer,
+                             w_cols::Vector{Int}; norm_mode::Int=16, cY=nothing)
+    ensure_solver!(fam)
+    ns = size(tables, 4)
+    lam = zeros(ComplexF64, N + 1, ns); st = zeros(Int32, ns); info = Ref{SolveInfo}()
+    code = check(ccall((:wae_perturb_batch_slots, libwaehip), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{ComplexF64}, Int32, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{ComplexF64}, Float64, Int32,
+                 Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Int32}, Ref{SolveInfo}),
+                fam.handle, ns, tables, N, v_slot, _cols0(v_cols), w_slot, _cols0(w_cols), norm_mode | 16, cY === nothing ? C_NULL : cY,
+                fam.tol, fam.maxit, lam, C_NULL, st, info))
+    report(code, info[], "perturb_batch_slots ($ns systems, order $N)"; quiet=true)
+    return lam, st
+end
+
 # one pass of the loop body shared by householder and mslp (Householder.jl:96-120)
 function _aux_step(fam::DeviceFamily, z, order, nev, v0, v0_adj, update, state)
     L = fam.L

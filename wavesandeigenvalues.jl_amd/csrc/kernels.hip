@@ -2925,3 +2925,193 @@ void launch_triad(double *a, const double *b, const double *c, double s_, int64_
     hipLaunchKernelGGL(triad_kernel, dim3(grid_for(n2, grid_cap)), dim3(256), 0, st, (double2 *)a, (const double2 *)b, (const double2 *)c, s_, n2);
     HIP_CHECK(hipGetLastError());
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Batched adjoint perturbation (lib.hip perturb_batch_core): nb eigenpairs expanded in lock-step.  Every vector of the batch is
+// interleaved [row][system] like the solver's multivectors; the input columns of the regrouped recurrence are U[row][t][system].
+// ---------------------------------------------------------------------------------------------------
+// U[row][t0 + t][b] (+)= sum_{i<k} G[i][t0 + t][b] * V_i[row][b],  t < tn <= TMAX;  V_i = V + i*stride, G: [k][T][nb].
+// A stream over the series: thread t owns column t % nb and every R-th row (R = 256 / nb, as in dots_kernel), holds the tn outputs of
+// its (row, column) in registers and reads V_i[row][b] ONCE for all of them; the k x tn x nb weights sit in LDS (the launcher cuts k so
+// that they fit).  Four 16-B loads of the series in flight per lane.
+constexpr int PTG_MAXW = 3072;      // weights per launch (48 KB of LDS)
+template <int TMAX>
+__global__ __launch_bounds__(256) void pt_gemm_batch_kernel(const cplx *__restrict__ V, size_t stride, int k, const cplx *__restrict__ G, int T, int t0,
+                                                            int tn, cplx *__restrict__ U, int64_t d, int nb, int accumulate) {
+    extern __shared__ cplx ptg_w[];                          // [k][tn][nb]
+    const int tid = threadIdx.x;
+    for (int e = tid; e < k * tn * nb; e += 256) {
+        const int b = e % nb, it = e / nb, t = it % tn, i = it / tn;
+        ptg_w[e] = G[((size_t)i * T + t0 + t) * nb + b];
+    }
+    __syncthreads();
+    const int R = 256 / nb;
+    const int b = tid % nb, rl = tid / nb;
+    if (rl >= R) return;
+    for (int64_t row = (int64_t)blockIdx.x * R + rl; row < d; row += (int64_t)gridDim.x * R) {
+        const size_t e = (size_t)row * nb + b;
+        cplx acc[TMAX];
+#pragma unroll
+        for (int t = 0; t < TMAX; ++t) acc[t] = cplx{0.0, 0.0};
+        int i = 0;
+        for (; i + 4 <= k; i += 4) {
+            cplx v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = stream_load(V + (size_t)(i + u) * stride + e);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int t = 0; t < TMAX; ++t)
+                    if (t < tn) cfma(acc[t], ptg_w[((i + u) * tn + t) * nb + b], v[u]);
+        }
+        for (; i < k; ++i) {
+            const cplx v = stream_load(V + (size_t)i * stride + e);
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t)
+                if (t < tn) cfma(acc[t], ptg_w[(i * tn + t) * nb + b], v);
+        }
+        cplx *out = U + ((size_t)row * T + t0) * nb + b;
+#pragma unroll
+        for (int t = 0; t < TMAX; ++t)
+            if (t < tn) {
+                cplx a = acc[t];
+                if (accumulate) { const cplx o = out[(size_t)t * nb]; a.x += o.x; a.y += o.y; }
+                out[(size_t)t * nb] = a;
+            }
+    }
+}
+void launch_pt_gemm_batch(const cplx *V, size_t stride, int k, const cplx *G, cplx *U, int64_t d, int T, int nb, hipStream_t st) {
+    if (nb < 1 || nb > 256 || k < 1 || T < 1) throw WaeError(WAE_ERR_INVALID, "pt_gemm_batch: nb in 1..256, k >= 1, T >= 1");
+    const int R = 256 / nb;
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (d + R - 1) / R));
+    for (int t0 = 0; t0 < T; t0 += 16) {
+        const int tn = std::min(16, T - t0);
+        const int kc = std::max(1, PTG_MAXW / (tn * nb));                  // series vectors per launch: their weights fill LDS
+        for (int i0 = 0; i0 < k; i0 += kc) {
+            const int kk = std::min(kc, k - i0);
+            const size_t shm = (size_t)kk * tn * nb * sizeof(cplx);
+            const cplx *Vc = V + (size_t)i0 * stride, *Gc = G + (size_t)i0 * T * nb;
+            const int acc = i0 > 0;
+            if (tn <= 4) hipLaunchKernelGGL(pt_gemm_batch_kernel<4>, dim3(grid), dim3(256), shm, st, Vc, stride, kk, Gc, T, t0, tn, U, d, nb, acc);
+            else if (tn <= 8) hipLaunchKernelGGL(pt_gemm_batch_kernel<8>, dim3(grid), dim3(256), shm, st, Vc, stride, kk, Gc, T, t0, tn, U, d, nb, acc);
+            else hipLaunchKernelGGL(pt_gemm_batch_kernel<16>, dim3(grid), dim3(256), shm, st, Vc, stride, kk, Gc, T, t0, tn, U, d, nb, acc);
+            HIP_CHECK(hipGetLastError());
+        }
+    }
+}
+
+// Per-plane input column for nb systems: Y[row][b] (+)= sum_q pc[q] plane_q U[:, plane_col[q], b]  (U: [row][nin][nb]).  The batched form
+// of spmv_multi_kernel: a team of C*S lanes owns a row, C lanes across the systems of an 8-column chunk (the gather of one entry and
+// plane is one contiguous C*16-byte access: a 128-B line at 8 systems), S lanes across the row's entries; index and values of an entry
+// are read once for the chunk's systems.  Real / conjugated planes and long rows as in spmv_multi_kernel.
+template <int C, int S>
+__global__ __launch_bounds__(256) void pt_spmv_batch_kernel(OpDev op, const cplx *__restrict__ pc, const int *__restrict__ plane_col,
+                                                            const cplx *__restrict__ U, int nin, cplx *__restrict__ Y, int nb, int accumulate) {
+    constexpr int TEAM = C * S;
+    const int tid = threadIdx.x;
+    const int64_t row = (int64_t)blockIdx.x * (256 / TEAM) + tid / TEAM;
+    const int c = tid % C, s = (tid % TEAM) / C;
+    if (row >= op.n) return;
+    const int b = blockIdx.y * C + c;
+    const int bb = b < nb ? b : nb - 1;                       // lanes past the batch repeat its last column (loads stay in bounds)
+    const size_t ldu = (size_t)nin * nb;
+    cplx acc = {0.0, 0.0};
+    for (int g = 0; g < op.ngroups; ++g) {
+        const GroupDev G = op.g[g];
+        const int p0 = G.rowptr[row], p1 = G.rowptr[row + 1];
+        const int np = G.nplanes;
+        for (int p = p0 + s; p < p1; p += S) {
+            const cplx *u = U + (size_t)G.col[p] * ldu + bb;
+            for (int q = 0; q < np; ++q) {
+                cplx a;
+                if (G.is_real) a = cplx{((const double *)G.vals)[(size_t)p * np + q], 0.0};
+                else { a = ((const cplx *)G.vals)[(size_t)p * np + q]; if (G.conj_vals) a.y = -a.y; }
+                cfma(acc, cmul(pc[G.plane0 + q], a), u[(size_t)plane_col[G.plane0 + q] * nb]);
+            }
+        }
+    }
+    if (op.nlong) {
+        const int li = long_row_index(op, row);
+        if (li >= 0)
+            for (int p = op.long_ptr[li] + s; p < op.long_ptr[li + 1]; p += S) {
+                cplx a = op.long_val[p];
+                if (op.long_conj) a.y = -a.y;
+                const int slot = op.long_slot[p];
+                cfma(acc, cmul(pc[slot], a), U[(size_t)op.long_col[p] * ldu + (size_t)plane_col[slot] * nb + bb]);
+            }
+    }
+    for (int off = C; off < TEAM; off <<= 1) {
+        acc.x += __shfl_xor(acc.x, off);
+        acc.y += __shfl_xor(acc.y, off);
+    }
+    if (s == 0 && b < nb) {
+        cplx *y = Y + (size_t)row * nb + b;
+        if (accumulate) { acc.x += y->x; acc.y += y->y; }
+        *y = acc;
+    }
+}
+void launch_pt_spmv_batch(const OpDev &op, const cplx *pc, const int *plane_col, const cplx *U, int nin, cplx *Y, int nb, int accumulate,
+                          hipStream_t st) {
+    if (op.n <= 0) return;
+    if (nb < 1 || nb > 256) throw WaeError(WAE_ERR_INVALID, "pt_spmv_batch: nb in 1..256");
+    const int C = nb >= 8 ? 8 : (nb >= 4 ? 4 : (nb >= 2 ? 2 : 1));
+#define WAE_PT_SPMV(c, s_) hipLaunchKernelGGL((pt_spmv_batch_kernel<c, s_>), dim3((unsigned)((op.n + 256 / (c * s_) - 1) / (256 / (c * s_))), (unsigned)((nb + c - 1) / c)), \
+                                              dim3(256), 0, st, op, pc, plane_col, U, nin, Y, nb, accumulate)
+    if (C == 8) WAE_PT_SPMV(8, 2);
+    else if (C == 4) WAE_PT_SPMV(4, 2);
+    else if (C == 2) WAE_PT_SPMV(2, 4);
+    else WAE_PT_SPMV(1, 8);
+#undef WAE_PT_SPMV
+    HIP_CHECK(hipGetLastError());
+}
+
+// out[row][b] = a[b] x[row][b] + c[b] y[row][b]  (coef = a[0..nb), c[0..nb) on the device; out may alias x or y).  A column whose two
+// coefficients are both zero is WRITTEN as zero whatever x and y hold: a system that has been given up leaves no NaN behind.
+__global__ __launch_bounds__(256) void pt_axpby_cols_kernel(const cplx *__restrict__ coef, const cplx *x, const cplx *y, cplx *out, int64_t d, int nb) {
+    const int tid = threadIdx.x;
+    const int R = 256 / nb;
+    const int b = tid % nb, rl = tid / nb;
+    if (rl >= R) return;
+    const cplx a = coef[b], c = coef[nb + b];
+    const bool dead = a.x == 0.0 && a.y == 0.0 && c.x == 0.0 && c.y == 0.0;
+    for (int64_t row = (int64_t)blockIdx.x * R + rl; row < d; row += (int64_t)gridDim.x * R) {
+        const size_t e = (size_t)row * nb + b;
+        cplx r = {0.0, 0.0};
+        if (!dead) { r = cmul(a, x[e]); cfma(r, c, y[e]); }
+        out[e] = r;
+    }
+}
+void launch_pt_axpby_cols(const cplx *coef, const cplx *x, const cplx *y, cplx *out, int64_t d, int nb, hipStream_t st) {
+    if (nb < 1 || nb > 256) throw WaeError(WAE_ERR_INVALID, "pt_axpby_cols: nb in 1..256");
+    const int R = 256 / nb;
+    hipLaunchKernelGGL(pt_axpby_cols_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (d + R - 1) / R))), dim3(256), 0, st, coef, x, y,
+                       out, d, nb);
+    HIP_CHECK(hipGetLastError());
+}
+
+// The two projections of an order in one pass: vk[row][b] += (-dots[0][b] - 1/2 sum_{1<=j<nd} dots[j][b]) * v0[row][b]
+// (dots[0] = v0^H [Y] v_k: perturbation.jl:425; dots[j] = v_j^H [Y] v_{k-j}: the normalisation sum of perturbation.jl:427-432; both
+// corrections are multiples of v0, and the second does not involve v_k).  The coefficients never visit the host.
+__global__ __launch_bounds__(256) void pt_project_kernel(cplx *__restrict__ vk, const cplx *__restrict__ v0, const cplx *__restrict__ dots, int nd,
+                                                         int64_t d, int nb) {
+    const int tid = threadIdx.x;
+    const int R = 256 / nb;
+    const int b = tid % nb, rl = tid / nb;
+    if (rl >= R) return;
+    cplx c = dots[b];
+    c.x = -c.x; c.y = -c.y;
+    for (int j = 1; j < nd; ++j) { const cplx t = dots[(size_t)j * nb + b]; c.x -= 0.5 * t.x; c.y -= 0.5 * t.y; }
+    for (int64_t row = (int64_t)blockIdx.x * R + rl; row < d; row += (int64_t)gridDim.x * R) {
+        const size_t e = (size_t)row * nb + b;
+        cplx v = vk[e];
+        cfma(v, c, v0[e]);
+        vk[e] = v;
+    }
+}
+void launch_pt_project(cplx *vk, const cplx *v0, const cplx *dots, int nd, int64_t d, int nb, hipStream_t st) {
+    if (nb < 1 || nb > 256 || nd < 1) throw WaeError(WAE_ERR_INVALID, "pt_project: nb in 1..256, nd >= 1");
+    const int R = 256 / nb;
+    hipLaunchKernelGGL(pt_project_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (d + R - 1) / R))), dim3(256), 0, st, vk, v0, dots, nd,
+                       d, nb);
+    HIP_CHECK(hipGetLastError());
+}

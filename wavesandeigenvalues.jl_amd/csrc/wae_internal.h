@@ -312,6 +312,16 @@ void launch_beyn_accum(const cplx *Xi, int nb, int64_t d, int l, int nsys, const
                        int lA = 0, int c0 = 0, const int *perm = nullptr);
 // X[row][t] = sum_i G[i][t] V_i[row], V_i = V + i*stride (single vectors), X interleaved with leading dimension T
 void launch_gemv_multi(const cplx *V, size_t stride, int k, const cplx *G, cplx *X, int64_t d, int T, hipStream_t s);
+// batched perturbation recurrence (nb systems interleaved; kernels.hip "Batched adjoint perturbation")
+// U[row][t][b] = sum_{i<k} G[i][t][b] V_i[row][b], V_i = V + i*stride (interleaved blocks), G: [k][T][nb]; every V_i is read once
+void launch_pt_gemm_batch(const cplx *V, size_t stride, int k, const cplx *G, cplx *U, int64_t d, int T, int nb, hipStream_t s);
+// Y[row][b] (+)= sum_q pc[q] plane_q U[:, plane_col[q], b]  (U: [row][nin][nb]; pc shared by the systems)
+void launch_pt_spmv_batch(const OpDev &op, const cplx *pc, const int *plane_col, const cplx *U, int nin, cplx *Y, int nb, int accumulate,
+                          hipStream_t s);
+// out = a[b] x + c[b] y per column (coef: a[0..nb) then c[0..nb), device); both zero: the column is written as zero
+void launch_pt_axpby_cols(const cplx *coef, const cplx *x, const cplx *y, cplx *out, int64_t d, int nb, hipStream_t s);
+// vk += (-dots[0][b] - 1/2 sum_{1<=j<nd} dots[j][b]) v0, per column
+void launch_pt_project(cplx *vk, const cplx *v0, const cplx *dots, int nd, int64_t d, int nb, hipStream_t s);
 // device-resident state of the lock-step GMRES recurrence (one thread per column, kernels.hip gmres_*_kernel)
 struct GmresDev {
     int nb, m, histcap;

@@ -401,6 +401,41 @@ class DeviceFamily:
         self._report(code, info, f"perturb_slots (order {N})", quiet=quiet)
         return lam, V
 
+    def perturb_batch(self, coeff_tables, N, V0=None, V0adj=None, slots=None, norm_mode=1, coeffsY=None, tol=1e-12, maxit=400, quiet=False,
+                      vectors=True):
+        """wae_perturb_batch / wae_perturb_batch_slots: nsys eigenpairs expanded to order N in lock-step.  coeff_tables: nsys tables as
+        ``perturb``'s; V0, V0adj: (d, nsys) host arrays, or slots = (v_slot, v_cols, vadj_slot, vadj_cols).  Returns lam (nsys, N+1),
+        V (nsys, d, N+1) -- None with vectors=False or norm_mode + 16 -- and the per-system status codes (``last_status`` as well)."""
+        ct = np.ascontiguousarray(coeff_tables, dtype=np.complex128).reshape(-1, (N + 1) * (N + 1) * self.T)
+        nsys = ct.shape[0]
+        lam = np.zeros((nsys, N + 1), dtype=np.complex128)
+        want_v = vectors and not (norm_mode & 16)
+        V = np.zeros((nsys, N + 1, self.d), dtype=np.complex128) if want_v else None      # each block column-major d x (N+1)
+        status = np.zeros(max(nsys, 1), dtype=np.int32)
+        sp_ = status.ctypes.data_as(C.POINTER(C.c_int32))
+        cy = None if coeffsY is None else np.ascontiguousarray(coeffsY, dtype=np.complex128)
+        cyp = None if cy is None else zptr(cy)
+        vp = None if V is None else zptr(V)
+        info = SolveInfo()
+        if slots is None:
+            v0 = np.asfortranarray(np.asarray(V0, dtype=np.complex128).reshape(self.d, -1))
+            va = np.asfortranarray(np.asarray(V0adj, dtype=np.complex128).reshape(self.d, -1))
+            if v0.shape[1] != nsys or va.shape[1] != nsys:
+                raise ValueError("perturb_batch: one right and one left vector per coefficient table")
+            code = check(_lib.lib().wae_perturb_batch(self.handle, nsys, zptr(ct), N, zptr(v0), zptr(va), norm_mode, cyp, tol, maxit, zptr(lam), vp,
+                                                      sp_, C.byref(info)))
+        else:
+            v_slot, v_cols, w_slot, w_cols = slots
+            vc, vcp = self._icols(v_cols)
+            wc, wcp = self._icols(w_cols)
+            if len(vc) != nsys or len(wc) != nsys:
+                raise ValueError("perturb_batch: one right and one left slot column per coefficient table")
+            code = check(_lib.lib().wae_perturb_batch_slots(self.handle, nsys, zptr(ct), N, int(v_slot), vcp, int(w_slot), wcp, norm_mode, cyp, tol,
+                                                            maxit, zptr(lam), vp, sp_, C.byref(info)))
+        self.last_status = status[:nsys].copy()
+        self._report(code, info, f"perturb_batch ({nsys} systems, order {N})", quiet=quiet)
+        return lam, (None if V is None else V.transpose(0, 2, 1)), self.last_status
+
     def debug_spmv(self, coeffs, X, mode=0, B=None, Y0=None, op=OP_N, jac_w=0.8, cmask=None, level=0, which=0, no_tiles=False):
         """wae_debug_spmv (test hook): one launch of the fused operator product in any of the solver's forms.  Returns Y, or
         (Y, B2) for mode 6.  ``level``/``which`` select a coarse-level operator or a restriction of the multigrid hierarchy."""

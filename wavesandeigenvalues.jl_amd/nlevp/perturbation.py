@@ -77,17 +77,23 @@ def multi_indices_at_order(k):
     return Mu
 
 
+def coefficient_table(L, N):
+    """The (N+1) x (N+1) x T table f_t^{(m,n)} = L.coefficients(m, n), m + n <= N (zero elsewhere), at L's current ``params``,
+    ``active`` and ``mode``: the host's whole share of the recurrence (wae_perturb's ``coeff_table``)."""
+    table = np.zeros((N + 1, N + 1, len(L.terms)), dtype=np.complex128)
+    for m in range(N + 1):
+        for n in range(N + 1 - m):
+            table[m, n] = L.coefficients(m, n)
+    return table
+
+
 def _recurrence(L, N, v0, v0Adj, normalize, Y=None, skip_last_solve=False):
     """perturbation.jl:319-367 (normalize=False), :374-444 (normalize=True), :487-560 (Y given): ONE device call
     (``wae_perturb``).  The host only evaluates the (N+1)^2 x T scalar coefficient table f_t^{(m,n)} = L.coefficients(m,n);
     partitions, the tall-skinny products V_k g_t, the fused multi-input SpMV, the N solves on the fixed hierarchy and
     all normalisations run inside the library on HBM-resident vectors."""
     fam = L.ensure_solver()
-    T = len(L.terms)
-    table = np.zeros((N + 1, N + 1, T), dtype=np.complex128)
-    for m in range(N + 1):
-        for n in range(N + 1 - m):
-            table[m, n] = L.coefficients(m, n)
+    table = coefficient_table(L, N)
     mode = (2 if Y is not None else (1 if normalize else 0)) + (16 if skip_last_solve else 0)
     lam, V = fam.perturb(table, N, v0, v0Adj, norm_mode=mode, coeffsY=None if Y is None else Y.coeffs,
                          tol=L.solver_tol, maxit=L.solver_maxit, quiet=skip_last_solve)   # (inside a Newton step: the caller judges)
@@ -200,15 +206,11 @@ def eigval_series_slots(L, eigval, param, N, v_slot, v_col, w_slot, w_col):
     eigenvalue parameter of the pair (the auxiliary eigenvalue of Householder.jl:115-116), `param` the perturbed one.  Returns the
     Taylor coefficients lam[0..N] (lam[0] = L.params[eigval]); no vector leaves the device."""
     fam = L.ensure_solver()
-    T = len(L.terms)
     active, cur_mode = L.active, L.mode
     L.active = [eigval, param]
     L.mode = "householder"
     try:
-        table = np.zeros((N + 1, N + 1, T), dtype=np.complex128)
-        for m in range(N + 1):
-            for n in range(N + 1 - m):
-                table[m, n] = L.coefficients(m, n)
+        table = coefficient_table(L, N)
     finally:
         L.active, L.mode = active, cur_mode
     lam, _ = fam.perturb_slots(table, N, v_slot, v_col, w_slot, w_col, norm_mode=16, tol=L.solver_tol, maxit=L.solver_maxit, quiet=True)
@@ -229,3 +231,56 @@ def perturb_fast_(sol, L, param, N, mode="compact"):
 def perturb_norm_(sol, L, param, N, mode="compact"):
     """perturb_norm!(sol,L,param,N;mode)"""
     _wrapper(perturb_norm, sol, L, param, N, mode)
+
+
+def solution_tables(sols, L, param, N, mode="compact"):
+    """One coefficient table per solution, each at that solution's own ``params`` with ``active = [sol.eigval, param]`` (what
+    ``_wrapper`` sets up around a single ``_recurrence``, LinOpFam.jl:546-560).  ``L.params``, ``L.active`` and ``L.mode`` are
+    restored also when an exception passes through."""
+    active, params, cur_mode = L.active, L.params, L.mode
+    tables = []
+    try:
+        for sol in sols:
+            L.params = sol.params
+            L.active = [sol.eigval, param]
+            L.mode = mode
+            tables.append(coefficient_table(L, N))
+    finally:
+        L.active, L.mode, L.params = active, cur_mode, params
+    return tables
+
+
+def perturb_many(sols, L, param, N, kind="fast", mode="compact"):
+    """``perturb_`` (kind="plain"), ``perturb_fast_`` ("fast") or ``perturb_norm_`` ("norm") for a list of solutions, expanded in lock-step
+    by ``wae_perturb_batch``: one device call per group of at most the solver's batch width (``fam.batch``) solutions.  Every solution is expanded at its own
+    ``params`` (the pairs may sit at different parameter points), and receives ``eigval_pert`` / ``v_pert`` exactly as from the single call.
+    Returns the per-solution status codes of the library (0: every inner solve of that pair converged)."""
+    norm_mode = {"plain": 0, "fast": 1, "norm": 2}[kind]
+    sols = list(sols)
+    if not sols:
+        return np.zeros(0, dtype=np.int32)
+    householder = mode == "householder"         # eigenvalue series only, as _wrapper
+    if householder:
+        norm_mode = 0
+    tables = solution_tables(sols, L, param, N, mode)
+    fam = L.ensure_solver()
+    cY = L.term_operator(len(L.terms) - 1, -1.0).coeffs if norm_mode == 2 else None
+    width = max(1, int(fam.batch))
+    key = f"{param}/Taylor"
+    status = np.zeros(len(sols), dtype=np.int32)
+    for i0 in range(0, len(sols), width):
+        grp = sols[i0:i0 + width]
+        V0 = np.stack([np.asarray(s.v, dtype=np.complex128) for s in grp], axis=1)
+        W0 = np.stack([np.asarray(s.v_adj, dtype=np.complex128) for s in grp], axis=1)
+        lam, V, st = fam.perturb_batch(np.stack(tables[i0:i0 + width]), N, V0, W0, norm_mode=norm_mode + (16 if householder else 0), coeffsY=cY,
+                                       tol=L.solver_tol, maxit=L.solver_maxit, quiet=householder)
+        status[i0:i0 + len(grp)] = st
+        for j, sol in enumerate(grp):
+            lj = lam[j].copy()
+            lj[0] = sol.params[sol.eigval]
+            if V is None:                       # (the single call returns the zero vectors of the series it did not compute)
+                vj = [np.zeros(fam.d, dtype=np.complex128) for _ in range(N + 1)]
+            else:
+                vj = [V[j][:, i].copy() for i in range(N + 1)]
+            sol.eigval_pert[key], sol.v_pert[key] = lj, vj
+    return status
