@@ -1,766 +1,19 @@
 // libwaehip.so -- family handle, multigrid-preconditioned batched GMRES, Beyn moment loop, C ABI.
 // gfx950 only.  See include/waehip.h for the contract of every exported function.
-#include <algorithm>
-#include <atomic>
-#include <exception>
-#include <future>
-#include <chrono>
 #include <cmath>
-#include <map>
-#include <memory>
-#include <tuple>
 
-#include "amg.h"
-#include "tiles.h"
-#include "wae_internal.h"
+#include "family.h"
 
 static thread_local std::string g_last_error;
 void wae_set_error(const std::string &m) { g_last_error = m; }
 
-// ----------------------------------------------------------------------------------------------------
-// level operators on device
-// ----------------------------------------------------------------------------------------------------
-OpDev LevelOp::dev(int op) const {
-    OpDev o;
-    memset(&o, 0, sizeof(o));
-    o.ngroups = (int)groups.size();
-    o.nplanes_total = nplanes;
-    o.n = n;
-    o.diag = diag.p;
-    o.conj_diag = (op == WAE_OP_C) ? 1 : 0;
-    o.tiles = !tiles.ready ? nullptr : (op == WAE_OP_N || tiles.all_symmetric) ? &tiles.dev : (tiles.ready_t ? &tiles.dev_t : nullptr);
-    {
-        const LongRows &LR = (op == WAE_OP_N) ? long_n : long_t;
-        o.nlong = LR.n;
-        o.long_rows = LR.rows.p; o.long_ptr = LR.ptr.p; o.long_col = LR.col.p; o.long_slot = LR.slot.p;
-        o.long_val = LR.val.p; o.long_acc = LR.acc.p; o.long_part = LR.part.p;
-        o.long_conj = (op == WAE_OP_C) ? 1 : 0;
-    }
-    for (size_t g = 0; g < groups.size(); ++g) {
-        const GroupHost &G = groups[g];
-        GroupDev &D = o.g[g];
-        const bool tr = (op != WAE_OP_N) && !G.symmetric;
-        D.rowptr = tr ? G.rowptr_t.p : G.rowptr.p;
-        D.col = tr ? G.col_t.p : G.col.p;
-        D.vals = tr ? (const void *)G.vals_t.p : (const void *)G.vals.p;
-        D.nplanes = G.nplanes;
-        D.is_real = G.is_real ? 1 : 0;
-        D.plane0 = G.plane0;
-        D.conj_vals = (op == WAE_OP_C && !G.is_real) ? 1 : 0;
-    }
-    return o;
-}
-static OpDev transfer_dev(const DevBuf<int> &ptr, const DevBuf<int> &col, const DevBuf<double> &val, int64_t n) {
-    OpDev o;
-    memset(&o, 0, sizeof(o));
-    o.ngroups = 1;
-    o.nplanes_total = 1;
-    o.n = n;
-    o.g[0].rowptr = ptr.p;
-    o.g[0].col = col.p;
-    o.g[0].vals = val.p;
-    o.g[0].nplanes = 1;
-    o.g[0].is_real = 1;
-    o.tiles = nullptr;
-    o.nlong = 0;
-    return o;
-}
-OpDev Transfer::devP() const { return transfer_dev(p_ptr, p_col, p_val, nf); }
-OpDev Transfer::devR() const {
-    OpDev o = transfer_dev(r_ptr, r_col, r_val, nc);
-    o.tiles = r_tiles.ready ? &r_tiles.dev : nullptr;
-    return o;
-}
-
-struct RbState {                     // snapshot basis of wae_beyn_moments_rb (one per handle)
-    cplx *Q = nullptr;               // store: cap snapshots of d x l (interleaved [row][column]); slots < S are orthonormal per column
-    int cap = 0, l = 0, S = 0;
-    std::vector<int> kact;           // terms that take part in the projection
-    std::vector<zc> Hk;              // Hk[ki][(s*cap + i)*l + c] = q_i^H A_k q_s   (column c's basis)
-    std::vector<zc> g;               // g[i*l + c] = q_i^H v_c
-    DevBuf<cplx> W, Vi, hb, alpha, alpha2, ycoef;   // W_k = A_k Q (resident), probe columns interleaved, small scratch
-    std::future<void> w_job;         // W (20 GB at 1M unknowns: ~0.4 s of hipMalloc) is mapped on a helper thread while the first
-    void wait_w() { if (w_job.valid()) w_job.get(); }       // snapshot systems are solved; whoever touches W waits for it here
-    bool vi_valid = false;           // Vi holds the probe matrix the basis was started with (false after an import)
-    ~RbState() { if (w_job.valid()) w_job.wait(); }
-};
-
-struct wae_family {
-    bool vc_light = false;               // the current solve belongs to the projected phase of a contour integral (1-5 steps from a good guess): vcycle() runs its light form
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int64_t d = 0;
-    int T = 0;
-    std::vector<int> term_plane;     // term k -> plane index (in the order planes were discovered)
-    std::vector<zc> term_scale;      // term k = scale * plane
-    std::vector<int64_t> term_nnz;
-    int nplanes = 0;
-    std::vector<CsrZ> planes0;       // host copies of the fine planes (set-up input), in the library's row numbering
-    // Row renumbering (tiles.h): internal row i is the caller's row perm[i].  Applied to the term matrices at create, to
-    // every vector at the ABI boundary (layout kernels), never visible outside.
-    std::vector<int> perm_h;
-    DevBuf<int> perm_dev;
-    std::vector<int> tile_row_ptr;   // tiles of the fine level (empty: no tiling)
-    const int *perm() const { return perm_dev.p; }
-    std::vector<LevelOp> ops;        // ops[0] = fine level
-    std::vector<std::vector<int>> slot_plane;   // per level: slot -> plane
-    std::vector<Transfer> xfer;
-    // dense coarsest level
-    int64_t nc = 0;
-    DevBuf<cplx> dense_planes, Ainv;
-    DevBuf<int> dstatus;
-    bool solver_ready = false;
-    double jac_w = 0.8;                  // weight of the pre-smoothing sweeps of the full V-cycle (opts[2])
-    double jac_w_post = 0.9;             // ... of its post-smoothing sweeps (opts[10])
-    double jac_w_light = 0.5;            // ... of the single sweep of the light cycle (opts[11]; projected phase of a contour integral)
-    int nsweeps = 1, restart = 30, NB = 64;
-    // workspaces
-    std::vector<DevBuf<cplx>> lx, lb, lt;
-    DevBuf<cplx> V, W, Z, Xs, Bs, U, partial, hdev, ydev, pcdev, one_dev, io_a, io_b, zw_dev;
-    DevBuf<cplx> vsq;                // 1/||v_i||^2 per basis slot and column: the wide-batch GMRES keeps its basis unnormalised
-    DevBuf<cplx> rbQ;                // library-owned snapshot store of wae_beyn_moments_rb
-    RbState rb;                      // the snapshot basis and its projected terms
-    DevBuf<int> plane_col_dev;
-    DevBuf<unsigned char> cmask;     // one byte per 8-column chunk of the current batch (0 = converged)
-    // device-resident recurrence of the wide-batch GMRES (gmres_wide)
-    DevBuf<cplx> gs_R, gs_sn, gs_g, gs_rescale, gs_Hraw, gs_pair;
-    DevBuf<double> gs_sub;
-    DevBuf<double> gs_cs, gs_sv, gs_relres, gs_bnorm, gs_hist;
-    DevBuf<int> gs_int;              // conv | steps | iters | histlen | stalled | status(4)
-    DevBuf<unsigned char> gs_done;
-    // penalty (Dirichlet-like) rows found at set-up: their sub-block as a small operator of its own (see penalty_polish)
-    int64_t n_penalty = 0;
-    LevelOp pen_op;
-    std::vector<int> pen_slot;
-    LevelOp pen_row_op;              // the penalty ROWS of the operator (n_penalty x d): their residual without a full SpMV
-    std::vector<int> pen_row_slot;
-    DevBuf<int> pen_rows;
-    DevBuf<cplx> pen_b, pen_x, pen_t;
-    // device-resident multivectors of the caller ("slots", wae_slot_*): d x ncols, column-major, in the library's row numbering
-    struct Slot { DevBuf<cplx> buf; int ncols = 0; };
-    Slot slots[WAE_NSLOTS];
-    // work space of the Arnoldi processes (kept between calls); after wae_arnoldi_shiftinvert_slots the basis of that call stays in
-    // arn_EV: arn_cols vectors of arn_nsys systems each, interleaved [row][system], for wae_arnoldi_ritz_to_slot
-    DevBuf<cplx> arn_EV, arn_t, arn_pcM, arn_hcol, arn_stage, arn_gdir;
-    int arn_nsys = 0, arn_cols = 0;
-    DevBuf<cplx> pt_ws, pt_Gd, pt_pcd;   // work space of wae_perturb / wae_perturb_slots (kept between calls)
-    cplx *h_pinned = nullptr;        // (restart+2)*NB
-    cplx *h_pin_pair = nullptr;      // staging of the pair steps of the narrow batches (gmres)
-    size_t h_pin_pair_n = 0;
-    size_t pc_stride_level = 0;      // elements per level in pcdev
-    ~wae_family() {                  // every DevBuf member frees itself
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (h_pinned) (void)hipHostFree(h_pinned);
-        if (h_pin_pair) (void)hipHostFree(h_pin_pair);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
 int wae_internal_device(const wae_family *h) { return h->device; }
 hipStream_t wae_internal_stream(const wae_family *h) { return h->stream; }
-
-static bool plane_is_real(const CsrZ &A) {
-    for (const zc &v : A.val)
-        if (v.imag() != 0.0) return false;
-    return true;
-}
-
-// Build the device representation of sum_q pc[q] plane_q from host planes; returns slot -> plane map.
-// sym_tol: when is a plane "symmetric", i.e. applied in its stored orientation for op = T / C?  0: only if mirror entries are equal
-// bit for bit (A' is exactly A').  > 0: if  |a_ij - a_ji| <= sym_tol * min(s_i, s_j),  s_i = the largest OFF-DIAGONAL magnitude of
-// row i -- the rounding scale of a row's assembled sums that a penalty / Dirichlet diagonal entry cannot inflate.
-static std::vector<int> build_levelop(LevelOp &L, const std::vector<CsrZ> &planes, hipStream_t st, double sym_tol) {
-    L.n = planes.empty() ? 0 : planes[0].n;
-    L.nplanes = (int)planes.size();
-    struct Grp { std::vector<int> members; bool real; };
-    std::vector<Grp> grps;
-    for (int q = 0; q < (int)planes.size(); ++q) {
-        const bool re = plane_is_real(planes[q]);
-        bool placed = false;
-        for (auto &g : grps)
-            if (g.real == re && csr_same_pattern(planes[g.members[0]], planes[q])) { g.members.push_back(q); placed = true; break; }
-        if (!placed) grps.push_back(Grp{{q}, re});
-    }
-    if ((int)grps.size() > WAE_MAXG) throw WaeError(WAE_ERR_INVALID, "too many distinct sparsity patterns (max 24)");
-    if ((int)planes.size() > WAE_MAXP) throw WaeError(WAE_ERR_INVALID, "too many distinct term matrices (max 64)");
-    std::vector<int> slot_plane;
-    L.groups.clear();
-    L.groups.resize(grps.size());
-    struct LongEntries {
-        std::map<int, std::vector<std::tuple<int, int, zc>>> rows;      // row -> (column, slot, value)
-        void add(int r, int c, int slot, zc v) { rows[r].emplace_back(c, slot, v); }
-    };
-    LongEntries long_n, long_t;
-    L.long_n = LongRows();
-    L.long_t = LongRows();
-    for (size_t gi = 0; gi < grps.size(); ++gi) {
-        const Grp &g = grps[gi];
-        GroupHost &G = L.groups[gi];
-        const CsrZ &A0 = planes[g.members[0]];
-        const int np = (int)g.members.size();
-        G.nplanes = np;
-        G.is_real = g.real;
-        G.nnz = A0.nnz();
-        G.plane0 = (int)slot_plane.size();
-        for (int q : g.members) slot_plane.push_back(q);
-        const int w = g.real ? 1 : 2;
-        auto pack = [&](const std::vector<const CsrZ *> &mats, std::vector<double> &out) {
-            const int64_t nnz = mats[0]->nnz();
-            out.resize((size_t)nnz * np * w);
-            const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(8, nnz / 262144));      // (host threads: entries in contiguous ranges)
-            std::vector<std::future<void>> jobs;
-            for (int t = 0; t < nth; ++t)
-                jobs.push_back(std::async(nth > 1 ? std::launch::async : std::launch::deferred, [&, t]() {
-                    const int64_t lo = nnz * t / nth, hi = nnz * (t + 1) / nth;
-                    for (int64_t p = lo; p < hi; ++p)
-                        for (int k = 0; k < np; ++k) {
-                            const zc v = mats[k]->val[p];
-                            if (g.real) out[(size_t)p * np + k] = v.real();
-                            else { out[((size_t)p * np + k) * 2] = v.real(); out[((size_t)p * np + k) * 2 + 1] = v.imag(); }
-                        }
-                }));
-            for (auto &j : jobs) j.get();
-        };
-        // long rows go to the level's long-row store (OpDev) and leave the group's CSR arrays
-        auto strip = [&](const std::vector<const CsrZ *> &src, std::vector<CsrZ> &kept, LongEntries &LE) {
-            kept.clear();
-            std::vector<char> is_long(src[0]->n, 0);
-            bool any = false;
-            const int limit = getenv("WAE_LONG_ROW") ? std::max(1, atoi(getenv("WAE_LONG_ROW"))) : WAE_LONG_ROW;   // (tests lower it)
-            for (int64_t i = 0; i < src[0]->n; ++i)
-                if (src[0]->ptr[i + 1] - src[0]->ptr[i] > limit) { is_long[i] = 1; any = true; }
-            if (!any) return false;
-            for (size_t k = 0; k < src.size(); ++k) {
-                const CsrZ &A = *src[k];
-                CsrZ B;
-                B.n = A.n; B.m = A.m;
-                B.ptr.assign(A.n + 1, 0);
-                for (int64_t i = 0; i < A.n; ++i) {
-                    if (is_long[i]) {
-                        for (int p = A.ptr[i]; p < A.ptr[i + 1]; ++p) LE.add((int)i, A.col[p], G.plane0 + (int)k, A.val[p]);
-                    } else {
-                        B.col.insert(B.col.end(), A.col.begin() + A.ptr[i], A.col.begin() + A.ptr[i + 1]);
-                        B.val.insert(B.val.end(), A.val.begin() + A.ptr[i], A.val.begin() + A.ptr[i + 1]);
-                    }
-                    B.ptr[i + 1] = (int)B.col.size();
-                }
-                kept.push_back(std::move(B));
-            }
-            return true;
-        };
-        std::vector<const CsrZ *> own;
-        for (int q : g.members) own.push_back(&planes[q]);
-        // transpose orientation.  Symmetry test: same pattern and mirror entries that agree exactly (sym_tol = 0) or to within sym_tol
-        // of the smaller of the two rows' off-diagonal scales.  Why a tolerance exists at all: a finite-element matrix assembled in
-        // floating point is symmetric only up to the order of its element sums (K and M of the 200k..1M-DoF annulus: mirror entries
-        // differ by 1e-16 of the row scale in half of the positions), and the exact test sends every adjoint product of such a family
-        // through a second, transposed copy of the operator and past the tile kernel.  A plane accepted with sym_tol > 0 is applied
-        // in its stored orientation for op = T / C: the product then differs from the exact transposed one by that assembly
-        // rounding.  The caller asks for it (wae_family_create_opts); the hierarchy's own coarse levels use 1e-14.
-        // The mirror entry a_ji is looked up in row j (sorted columns) on the host threads; the transposed copies are built only for
-        // a group that fails the test (or whose rows are not sorted: then the transpose decides, as it used to).
-        auto row_scales = [](const CsrZ &P) {                    // largest off-diagonal magnitude per row
-            std::vector<double> sc((size_t)P.n, 0.0);
-            const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(16, P.n / 8192));
-            std::vector<std::future<void>> jobs;
-            for (int t = 0; t < nth; ++t)
-                jobs.push_back(std::async(nth > 1 ? std::launch::async : std::launch::deferred, [&, t]() {
-                    const int64_t lo = P.n * t / nth, hi = P.n * (t + 1) / nth;
-                    for (int64_t i = lo; i < hi; ++i) {
-                        double m = 0.0;
-                        for (int p = P.ptr[i]; p < P.ptr[i + 1]; ++p)
-                            if (P.col[p] != (int)i) m = std::max(m, std::norm(P.val[p]));
-                        sc[(size_t)i] = std::sqrt(m);
-                    }
-                }));
-            for (auto &j : jobs) j.get();
-            return sc;
-        };
-        auto mirror_test = [sym_tol, &row_scales](const CsrZ &P) -> int {     // 1 symmetric, 0 not, -1 unsorted rows (undecided)
-            if (P.n != P.m) return 0;
-            std::vector<double> sc;
-            if (sym_tol > 0.0) sc = row_scales(P);
-            const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(16, P.n / 8192));
-            std::vector<int> verdict(nth, 1);
-            std::vector<std::future<void>> jobs;
-            for (int t = 0; t < nth; ++t)
-                jobs.push_back(std::async(nth > 1 ? std::launch::async : std::launch::deferred, [&, t]() {
-                    const int64_t lo = P.n * t / nth, hi = P.n * (t + 1) / nth;
-                    int vd = 1;                                // (thread-local: the per-thread slots share cache lines)
-                    for (int64_t i = lo; i < hi && vd == 1; ++i)
-                        for (int p = P.ptr[i]; p < P.ptr[i + 1]; ++p) {
-                            if (p > P.ptr[i] && P.col[p - 1] >= P.col[p]) { vd = -1; break; }
-                            const int j = P.col[p];
-                            if (j == i) continue;
-                            const int *b = P.col.data() + P.ptr[j], *e = P.col.data() + P.ptr[j + 1];
-                            const int *f = std::lower_bound(b, e, (int)i);
-                            if (f == e || *f != (int)i) { vd = 0; break; }
-                            const zc m = P.val[(size_t)(f - P.col.data())];
-                            if (m == P.val[p]) continue;
-                            if (!(sym_tol > 0.0 && std::abs(P.val[p] - m) <= sym_tol * std::min(sc[(size_t)i], sc[(size_t)j]))) { vd = 0; break; }
-                        }
-                    verdict[t] = vd;
-                }));
-            for (auto &j : jobs) j.get();
-            int v = 1;
-            for (int t = 0; t < nth; ++t) { if (verdict[t] == -1) v = -1; else if (verdict[t] == 0 && v == 1) v = 0; }
-            return v;
-        };
-        std::vector<CsrZ> tr;
-        bool sym = (A0.n == A0.m);
-        bool undecided = false;
-        for (size_t k = 0; k < g.members.size() && sym; ++k) {
-            const int v = mirror_test(planes[g.members[k]]);
-            if (v == 0) sym = false;
-            if (v < 0) { undecided = true; break; }
-        }
-        if (!sym || undecided) {
-            std::vector<std::future<CsrZ>> tj;
-            for (int q : g.members) tj.push_back(std::async(std::launch::async, [&planes, q]() { return csr_transpose(planes[q]); }));
-            for (size_t k = 0; k < tj.size(); ++k) {
-                const int q = g.members[k];
-                tr.push_back(tj[k].get());
-                if (!sym) continue;
-                const CsrZ &P0 = planes[q], &P1 = tr.back();
-                if (!(P1.ptr == P0.ptr && P1.col == P0.col)) { sym = false; continue; }
-                std::vector<double> sc;
-                if (sym_tol > 0.0) sc = row_scales(P0);
-                for (int64_t i = 0; i < P0.n && sym; ++i)          // (same pattern: entry e of P1 is the mirror of entry e of P0)
-                    for (int e = P0.ptr[i]; e < P0.ptr[i + 1]; ++e) {
-                        if (P0.val[e] == P1.val[e]) continue;
-                        const int j = P0.col[e];
-                        if (!(sym_tol > 0.0 && j != i && std::abs(P0.val[e] - P1.val[e]) <= sym_tol * std::min(sc[(size_t)i], sc[(size_t)j]))) { sym = false; break; }
-                    }
-            }
-        }
-        G.symmetric = sym;
-        std::vector<CsrZ> kept;
-        const bool stripped_n = strip(own, kept, long_n);
-        if (stripped_n && sym) {                             // the T orientation aliases these arrays: same rows, same entries
-            std::vector<CsrZ> dummy;
-            strip(own, dummy, long_t);
-        }
-        std::vector<const CsrZ *> mats;
-        if (stripped_n) for (const CsrZ &M : kept) mats.push_back(&M);
-        else mats = own;
-        std::vector<double> packed;
-        pack(mats, packed);
-        G.rowptr.upload(mats[0]->ptr.data(), mats[0]->ptr.size(), st);
-        G.col.upload(mats[0]->col.data(), mats[0]->col.size(), st);
-        G.vals.upload(packed.data(), packed.size(), st);
-        std::vector<CsrZ> kept_t;
-        std::vector<double> tp;
-        if (!sym) {
-            std::vector<const CsrZ *> trp;
-            for (const CsrZ &t : tr) trp.push_back(&t);
-            const bool stripped_t = strip(trp, kept_t, long_t);
-            std::vector<const CsrZ *> tm;
-            if (stripped_t) for (const CsrZ &t : kept_t) tm.push_back(&t);
-            else tm = trp;
-            pack(tm, tp);
-            G.rowptr_t.upload(tm[0]->ptr.data(), tm[0]->ptr.size(), st);
-            G.col_t.upload(tm[0]->col.data(), tm[0]->col.size(), st);
-            G.vals_t.upload(tp.data(), tp.size(), st);
-        }
-        HIP_CHECK(hipStreamSynchronize(st));   // host staging buffers die at scope end
-    }
-    auto upload_long = [&](const LongEntries &LE, LongRows &LR) {
-        LR.n = (int)LE.rows.size();
-        if (!LR.n) return;
-        std::vector<int> rows, ptr(1, 0), col, slot;
-        std::vector<cplx> val;
-        for (const auto &kv : LE.rows) {
-            rows.push_back(kv.first);
-            for (const auto &e : kv.second) { col.push_back(std::get<0>(e)); slot.push_back(std::get<1>(e)); val.push_back(cplx{std::get<2>(e).real(), std::get<2>(e).imag()}); }
-            ptr.push_back((int)col.size());
-        }
-        LR.rows.upload(rows.data(), rows.size(), st); LR.ptr.upload(ptr.data(), ptr.size(), st);
-        LR.col.upload(col.data(), col.size(), st); LR.slot.upload(slot.data(), slot.size(), st);
-        LR.val.upload(val.data(), val.size(), st);
-        LR.acc.alloc((size_t)LR.n * 256);                     // batch widths up to 256 columns
-        LR.part.alloc((size_t)LR.n * WAE_LONG_SPLIT * 256);
-        HIP_CHECK(hipStreamSynchronize(st));
-    };
-    upload_long(long_n, L.long_n);
-    upload_long(long_t, L.long_t);
-    // diagonals [n][nplanes] in slot order
-    std::vector<cplx> dg((size_t)L.n * L.nplanes, cplx{0.0, 0.0});
-    for (int s = 0; s < L.nplanes; ++s) {
-        const CsrZ &A = planes[slot_plane[s]];
-        for (int64_t i = 0; i < A.n; ++i)
-            for (int p = A.ptr[i]; p < A.ptr[i + 1]; ++p)
-                if (A.col[p] == i) dg[(size_t)i * L.nplanes + s] = cplx{A.val[p].real(), A.val[p].imag()};
-    }
-    L.diag.upload(dg.data(), dg.size(), st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    return slot_plane;
-}
-
-// tile-local storage of an operator whose rows have been cut into tiles (tiles.h): windows and the bulk group (two real planes on
-// one pattern).  U: pattern that defines the windows (every column any plane of the operator touches).
-static bool build_tiles_core(TileStore &T, const std::vector<const CsrZ *> &bulk, const Pattern &U, const std::vector<int> &row_ptr, int lpr,
-                             hipStream_t st, const char *what, int nbuf = 2, int nwaves = 8) {
-    T = TileStore();
-    if (row_ptr.size() < 2) return false;
-    const TileWindows W = build_windows(U, row_ptr);
-    const int nt = (int)row_ptr.size() - 1;
-    int wmax = 0;
-    for (int t = 0; t < nt; ++t) wmax = std::max(wmax, W.win_ptr[t + 1] - W.win_ptr[t]);
-    if (wmax > 65535) return false;
-    T.row_ptr.upload(row_ptr.data(), row_ptr.size(), st);
-    T.win_ptr.upload(W.win_ptr.data(), W.win_ptr.size(), st);
-    T.win_cols.upload(W.win_cols.data(), W.win_cols.size(), st);
-    memset(&T.dev, 0, sizeof(T.dev));
-    {
-        const TileGroupHost H = build_tile_group(bulk, true, row_ptr, W, lpr, nwaves);
-        T.sptr.upload(H.sptr.data(), H.sptr.size(), st);
-        T.sidx.upload(H.sidx.data(), H.sidx.size(), st);
-        T.svals.upload(H.svals.data(), H.svals.size(), st);
-        T.dslot.upload(H.dslot.data(), H.dslot.size(), st);
-        HIP_CHECK(hipStreamSynchronize(st));                 // H dies at the end of this scope
-        T.dev.g0.sptr = T.sptr.p;
-        T.dev.g0.sidx = T.sidx.p;
-        T.dev.g0.svals = T.svals.p;
-        T.dev.g0.dslot = T.dslot.p;
-        if (getenv("WAE_SETUP_DEBUG")) {
-            int over = 0, full = 0;                          // slices longer than the register-resident entries per lane
-            for (size_t i = 0; i + 1 < H.sptr.size(); ++i) over += (H.sptr[i + 1] - H.sptr[i]) / 64 > (nwaves == 16 ? 4 : (lpr == 2 ? 8 : 12));
-            for (int t = 0; t < nt; ++t) full += row_ptr[t + 1] - row_ptr[t] == 64 * nwaves / lpr;
-            fprintf(stderr, "[tiles] %s: %d tiles (%d lanes per row, %d window buffers), %.1f rows and %.1f window rows per tile on average, %d full tiles, largest window %d\n",
-                    what, nt, lpr, (nbuf == 3 && lpr == 2 && wmax <= 400) ? 3 : 2, (double)row_ptr[nt] / nt, (double)W.win_ptr[nt] / nt, full, wmax);
-            fprintf(stderr, "[tiles] %s: %lld nonzeros in %lld slots (%.3f filled), %d of %zu slices stream entries\n", what,
-                    (long long)bulk[0]->ptr.back(), (long long)H.sptr.back(), (double)bulk[0]->ptr.back() / (double)std::max(1, H.sptr.back()),
-                    over, H.sptr.size() - 1);
-        }
-    }
-    const std::vector<unsigned> zero(16, 0u);
-    T.counters.upload(zero.data(), zero.size(), st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    T.dev.ntiles = nt;
-    T.dev.wmax = wmax;
-    T.dev.lpr = lpr;
-    T.dev.nwaves = nwaves;
-    T.dev.nbuf = (nbuf == 3 && lpr == 2 && wmax <= 400) ? 3 : 2;
-    T.dev.row_ptr = T.row_ptr.p;
-    T.dev.win_ptr = T.win_ptr.p;
-    T.dev.win_cols = T.win_cols.p;
-    T.dev.counters = T.counters.p;
-    return true;
-}
-// ... of a level operator; planes in the level's numbering
-static void build_level_tiles(LevelOp &L, const std::vector<CsrZ> &planes, const std::vector<int> &slot_plane, const std::vector<int> &row_ptr,
-                              hipStream_t st, int lpr = 2, int nbuf = 2, int nwaves = 8) {
-    TileStore &T = L.tiles;
-    T = TileStore();
-    if (L.groups.empty() || !L.groups[0].is_real || L.groups[0].nplanes != 2) return;   // the tile kernel's bulk group: two real planes
-    const size_t ng = L.groups.size();
-    {
-        const GroupHost &G = L.groups[0];
-        std::vector<const CsrZ *> mats;
-        for (int q = 0; q < G.nplanes; ++q) mats.push_back(&planes[slot_plane[G.plane0 + q]]);
-        if (!build_tiles_core(T, mats, union_pattern(planes), row_ptr, lpr, st, "operator", nbuf, nwaves)) return;
-    }
-    T.all_symmetric = true;
-    for (size_t g = 0; g < ng; ++g) T.all_symmetric = T.all_symmetric && L.groups[g].symmetric;
-    // side rows: every entry of the other groups, row by row (level numbering), plane slot and complex value per entry.  transposed:
-    // the entries of the groups' transposes (symmetric groups as they are); rows longer than the long-row limit keep an empty CSR row
-    // and go to the long list instead
-    struct SideHost {
-        std::vector<int> of_row, ptr, col, slot, ls_ptr, ls_col, ls_slot, ls_side;
-        std::vector<cplx> val, ls_val;
-        int nside = 0;
-    };
-    auto build_side = [&](bool transposed) {
-        SideHost S;
-        const int64_t n = L.n;
-        const int limit = getenv("WAE_LONG_ROW") ? std::max(1, atoi(getenv("WAE_LONG_ROW"))) : WAE_LONG_ROW;
-        std::vector<CsrZ> trs;                                 // transposes of the non-symmetric planes, in (group, plane) order
-        std::vector<const CsrZ *> src;                         // per (group >= 1, plane): the matrix to take rows from
-        std::vector<int> src_slot;
-        for (size_t g = 1; g < ng; ++g)
-            for (int q = 0; q < L.groups[g].nplanes; ++q) {
-                const CsrZ &A = planes[slot_plane[L.groups[g].plane0 + q]];
-                src_slot.push_back(L.groups[g].plane0 + q);
-                if (transposed && !L.groups[g].symmetric) trs.push_back(csr_transpose(A));
-            }
-        size_t it = 0;
-        for (size_t g = 1; g < ng; ++g)
-            for (int q = 0; q < L.groups[g].nplanes; ++q)
-                src.push_back(transposed && !L.groups[g].symmetric ? &trs[it++] : &planes[slot_plane[L.groups[g].plane0 + q]]);
-        std::vector<int> count((size_t)n, 0);
-        for (const CsrZ *A : src)
-            for (int64_t i = 0; i < n; ++i) count[(size_t)i] += A->ptr[i + 1] - A->ptr[i];
-        S.of_row.assign((size_t)n, -1);
-        S.ptr.assign(1, 0);
-        S.ls_ptr.assign(1, 0);
-        std::vector<char> is_long((size_t)n, 0);
-        for (int64_t i = 0; i < n; ++i)
-            if (count[(size_t)i]) {
-                S.of_row[(size_t)i] = (int)S.ptr.size() - 1;
-                is_long[(size_t)i] = transposed && count[(size_t)i] > limit;
-                S.ptr.push_back(S.ptr.back() + (is_long[(size_t)i] ? 0 : count[(size_t)i]));
-            }
-        S.nside = (int)S.ptr.size() - 1;
-        S.col.resize((size_t)S.ptr.back()); S.slot.resize((size_t)S.ptr.back()); S.val.resize((size_t)S.ptr.back());
-        std::vector<int> fill(S.ptr.begin(), S.ptr.end() - 1);
-        for (int64_t i = 0; i < n; ++i) {                      // (long rows: one list per row, entries in (plane, column) order)
-            if (!is_long[(size_t)i]) continue;
-            for (size_t k = 0; k < src.size(); ++k)
-                for (int p = src[k]->ptr[i]; p < src[k]->ptr[i + 1]; ++p) {
-                    S.ls_col.push_back(src[k]->col[p]); S.ls_slot.push_back(src_slot[k]);
-                    S.ls_val.push_back(cplx{src[k]->val[p].real(), src[k]->val[p].imag()});
-                }
-            S.ls_ptr.push_back((int)S.ls_col.size());
-            S.ls_side.push_back(S.of_row[(size_t)i]);
-        }
-        for (size_t k = 0; k < src.size(); ++k) {
-            const CsrZ &A = *src[k];
-            for (int64_t i = 0; i < n; ++i) {
-                if (is_long[(size_t)i]) continue;
-                for (int p = A.ptr[i]; p < A.ptr[i + 1]; ++p) {
-                    const int e = fill[(size_t)S.of_row[(size_t)i]]++;
-                    S.col[(size_t)e] = A.col[p]; S.slot[(size_t)e] = src_slot[k]; S.val[(size_t)e] = cplx{A.val[p].real(), A.val[p].imag()};
-                }
-            }
-        }
-        return S;
-    };
-    {
-        const SideHost S = build_side(false);
-        T.side_of_row.upload(S.of_row.data(), S.of_row.size(), st);
-        T.side_ptr.upload(S.ptr.data(), S.ptr.size(), st);
-        if (S.nside) {
-            T.side_col.upload(S.col.data(), S.col.size(), st);
-            T.side_slot.upload(S.slot.data(), S.slot.size(), st);
-            T.side_val.upload(S.val.data(), S.val.size(), st);
-            T.side_acc.alloc((size_t)S.nside * 256);         // batch widths up to 256 columns
-        }
-        HIP_CHECK(hipStreamSynchronize(st));
-        T.dev.nside = S.nside;
-        T.dev.side_of_row = T.side_of_row.p;
-        T.dev.side_ptr = T.side_ptr.p; T.dev.side_col = T.side_col.p; T.dev.side_slot = T.side_slot.p;
-        T.dev.side_val = T.side_val.p; T.dev.side_acc = T.side_acc.p;
-        T.dev.nlong_side = 0;
-        if (getenv("WAE_SETUP_DEBUG"))
-            fprintf(stderr, "[tiles] %d side rows with %d entries of the other %zu groups\n", S.nside, S.ptr.back(), ng - 1);
-    }
-    // The transposed orientation (op = T / C on a family with a non-symmetric term -- the flame term of the adjoint solves): the bulk
-    // group must be symmetric (the tile storage itself is shared), the side rows are those of the other groups' transposes.
-    static const bool tile_t_on = !(getenv("WAE_TILE_TRANSPOSED") && atoi(getenv("WAE_TILE_TRANSPOSED")) == 0);
-    if (!T.all_symmetric && L.groups[0].symmetric && tile_t_on) {
-        const SideHost S = build_side(true);
-        T.t_side_of_row.upload(S.of_row.data(), S.of_row.size(), st);
-        T.t_side_ptr.upload(S.ptr.data(), S.ptr.size(), st);
-        if (S.nside) {
-            T.t_side_col.upload(S.col.data(), S.col.size(), st);
-            T.t_side_slot.upload(S.slot.data(), S.slot.size(), st);
-            T.t_side_val.upload(S.val.data(), S.val.size(), st);
-            T.t_side_acc.alloc((size_t)S.nside * 256);
-        }
-        const int nls = (int)S.ls_side.size();
-        if (nls) {
-            T.t_ls_ptr.upload(S.ls_ptr.data(), S.ls_ptr.size(), st);
-            T.t_ls_col.upload(S.ls_col.data(), S.ls_col.size(), st);
-            T.t_ls_slot.upload(S.ls_slot.data(), S.ls_slot.size(), st);
-            T.t_ls_val.upload(S.ls_val.data(), S.ls_val.size(), st);
-            T.t_ls_side.upload(S.ls_side.data(), S.ls_side.size(), st);
-            T.t_ls_part.alloc((size_t)nls * WAE_LONG_SPLIT * 256);
-        }
-        HIP_CHECK(hipStreamSynchronize(st));
-        T.dev_t = T.dev;
-        T.dev_t.nside = S.nside;
-        T.dev_t.side_of_row = T.t_side_of_row.p;
-        T.dev_t.side_ptr = T.t_side_ptr.p; T.dev_t.side_col = T.t_side_col.p; T.dev_t.side_slot = T.t_side_slot.p;
-        T.dev_t.side_val = T.t_side_val.p; T.dev_t.side_acc = T.t_side_acc.p;
-        T.dev_t.nlong_side = nls;
-        T.dev_t.ls_ptr = T.t_ls_ptr.p; T.dev_t.ls_col = T.t_ls_col.p; T.dev_t.ls_slot = T.t_ls_slot.p; T.dev_t.ls_val = T.t_ls_val.p;
-        T.dev_t.ls_side = T.t_ls_side.p;
-        T.dev_t.ls_part = T.t_ls_part.p;
-        T.ready_t = true;
-        if (getenv("WAE_SETUP_DEBUG"))
-            fprintf(stderr, "[tiles] transposed orientation: %d side rows with %d entries, %d long rows with %d entries\n", S.nside, S.ptr.back(), nls,
-                    S.ls_ptr.back());
-    }
-    T.ready = true;
-}
-
-// ----------------------------------------------------------------------------------------------------
-// input conversion
-// ----------------------------------------------------------------------------------------------------
-// body(lo, hi) over contiguous ranges of [0, n) on up to nth host threads; an exception of any range is rethrown here
-template <class F> static void host_ranges(int64_t n, int nth, F &&body) {
-    nth = (int)std::max<int64_t>(1, std::min<int64_t>(nth, n / 65536 + 1));
-    if (nth == 1) { body((int64_t)0, n); return; }
-    std::vector<std::future<void>> jobs;
-    for (int t = 0; t < nth; ++t) {
-        const int64_t lo = n * t / nth, hi = n * (t + 1) / nth;
-        jobs.push_back(std::async(std::launch::async, [&body, lo, hi]() { body(lo, hi); }));
-    }
-    std::exception_ptr first;
-    for (auto &j : jobs) {
-        try { j.get(); } catch (...) { if (!first) first = std::current_exception(); }
-    }
-    if (first) std::rethrow_exception(first);
-}
-
-static CsrZ term_to_csr(int64_t d, int index_bytes, int base, int orientation, const void *ptr, const void *idx, const double *val) {
-    auto getp = [&](int64_t i) -> int64_t { return index_bytes == 4 ? (int64_t)((const uint32_t *)ptr)[i] : ((const int64_t *)ptr)[i]; };
-    auto geti = [&](int64_t i) -> int64_t { return index_bytes == 4 ? (int64_t)((const uint32_t *)idx)[i] : ((const int64_t *)idx)[i]; };
-    CsrZ A;
-    A.n = A.m = d;
-    const int64_t nnz = getp(d) - base;
-    WAE_REQUIRE(nnz >= 0 && nnz < (int64_t)2147483647, "term nnz out of range");
-    A.ptr.resize(d + 1);
-    A.col.resize(nnz);
-    A.val.resize(nnz);
-    // (four threads per term, the terms themselves side by side in wae_family_create_opts: copying and checking 30 M entries of a
-    // 1M-unknown family on one thread was 1.0 s of the 1.7 s a family takes to create)
-    constexpr int NTH = 4;
-    host_ranges(d + 1, NTH, [&](int64_t lo, int64_t hi) {
-        for (int64_t i = lo; i < hi; ++i) {
-            const int64_t p = getp(i) - base;
-            WAE_REQUIRE(p >= 0 && p <= nnz, "pointer array out of range");
-            A.ptr[i] = (int)p;
-        }
-    });
-    host_ranges(nnz, NTH, [&](int64_t lo, int64_t hi) {
-        for (int64_t p = lo; p < hi; ++p) {
-            const int64_t j = geti(p) - base;
-            WAE_REQUIRE(j >= 0 && j < d, "index out of range");
-            A.col[p] = (int)j;
-            A.val[p] = zc(val[2 * p], val[2 * p + 1]);
-        }
-    });
-    // rows already sorted without duplicates (what scipy and SparseArrays hand over): taken as they are
-    std::atomic<bool> canonical{true};
-    host_ranges(d, NTH, [&](int64_t lo, int64_t hi) {
-        bool ok = true;
-        for (int64_t i = lo; i < hi; ++i) {
-            WAE_REQUIRE(A.ptr[i] <= A.ptr[i + 1], "pointer array not monotone");
-            for (int p = A.ptr[i] + 1; p < A.ptr[i + 1]; ++p) ok = ok && A.col[p - 1] < A.col[p];
-        }
-        if (!ok) canonical = false;
-    });
-    if (canonical) return orientation == WAE_CSC ? csr_transpose(A) : A;
-    // sort + merge duplicates per row
-    CsrZ S;
-    S.n = S.m = d;
-    S.ptr.assign(d + 1, 0);
-    std::vector<std::pair<int, zc>> row;
-    for (int64_t i = 0; i < d; ++i) {
-        row.clear();
-        for (int p = A.ptr[i]; p < A.ptr[i + 1]; ++p) row.emplace_back(A.col[p], A.val[p]);
-        std::stable_sort(row.begin(), row.end(), [](const std::pair<int, zc> &a, const std::pair<int, zc> &b) { return a.first < b.first; });
-        for (size_t k = 0; k < row.size(); ++k) {
-            if (!S.col.empty() && (int)S.col.size() > S.ptr[i] && S.col.back() == row[k].first) S.val.back() += row[k].second;
-            else { S.col.push_back(row[k].first); S.val.push_back(row[k].second); }
-        }
-        S.ptr[i + 1] = (int)S.col.size();
-    }
-    if (orientation == WAE_CSC) return csr_transpose(S);
-    return S;
-}
-
-// term k == s * plane q exactly?
-static bool proportional(const CsrZ &A, const CsrZ &P, zc &s) {
-    if (!csr_same_pattern(A, P) || A.nnz() == 0) return false;
-    int64_t p0 = -1;
-    for (int64_t p = 0; p < P.nnz(); ++p)
-        if (P.val[p] != zc(0)) { p0 = p; break; }
-    if (p0 < 0) return false;
-    s = A.val[p0] / P.val[p0];
-    for (int64_t p = 0; p < P.nnz(); ++p)
-        if (A.val[p] != s * P.val[p]) return false;
-    return true;
-}
-
-// ... of the restriction R (rows: the coarse level's tile numbering, columns: the fine level's): consecutive rows are cut into tiles
-// whose fine-level window fits LDS
-static void build_restriction_tiles(Transfer &X, const CsrD &R, int wcap, hipStream_t st) {
-    X.r_tiles = TileStore();
-    CsrZ Rz, Zz;                                             // plane 0 = R, plane 1 = 0 (the kernel's bulk group has two planes)
-    Rz.n = R.n; Rz.m = R.m; Rz.ptr = R.ptr; Rz.col = R.col;
-    Rz.val.resize(R.val.size());
-    for (size_t i = 0; i < R.val.size(); ++i) Rz.val[i] = zc(R.val[i], 0.0);
-    Zz.n = R.n; Zz.m = R.m; Zz.ptr = R.ptr; Zz.col = R.col;
-    Zz.val.assign(R.val.size(), zc(0.0, 0.0));
-    Pattern U;
-    U.n = R.n; U.ptr = R.ptr; U.col = R.col;
-    std::vector<int> row_ptr(1, 0), stamp((size_t)R.m, -1);
-    int rows = 0, win = 0;
-    for (int64_t i = 0; i < R.n; ++i) {
-        if (R.ptr[i + 1] - R.ptr[i] > wcap) return;          // (a row that does not fit a window)
-        int fresh = 0;
-        const int t = (int)row_ptr.size() - 1;
-        for (int p = R.ptr[i]; p < R.ptr[i + 1]; ++p) fresh += stamp[(size_t)R.col[p]] != t;
-        if (rows == 128 || win + fresh > wcap) {
-            row_ptr.push_back((int)i);
-            rows = 0; win = 0;
-        }
-        const int t2 = (int)row_ptr.size() - 1;
-        for (int p = R.ptr[i]; p < R.ptr[i + 1]; ++p)
-            if (stamp[(size_t)R.col[p]] != t2) { stamp[(size_t)R.col[p]] = t2; ++win; }
-        ++rows;
-    }
-    row_ptr.push_back((int)R.n);
-    if (!build_tiles_core(X.r_tiles, {&Rz, &Zz}, U, row_ptr, 4, st, "restriction")) return;
-    X.r_tiles.dev.unit = 1;
-    X.r_tiles.ready = true;
-}
-
-// The prolongation by fine tile (wae_internal.h XferTiles): P (fine x coarse, rows in the fine level's tile order), row_ptr = the fine tiles.
-static void build_transfer_tiles(Transfer &X, const CsrD &P, const std::vector<int> &row_ptr, hipStream_t st) {
-    XferTiles &F = X.ft;
-    F.ready = false;
-    const int nt = (int)row_ptr.size() - 1;
-    if (nt <= 0 || row_ptr.back() != P.n) return;
-    std::vector<int> tptr(nt + 1, 0), clist, stamp((size_t)P.m, -1), slot((size_t)P.m, 0);
-    std::vector<unsigned short> ploc(P.col.size());
-    int maxslots = 0, maxent = 0;
-    std::vector<int> cols;
-    for (int t = 0; t < nt; ++t) {
-        const int a = row_ptr[t], b = row_ptr[t + 1];
-        if (b - a > 256) return;                             // (the kernel walks at most 256 fine rows per workgroup)
-        cols.clear();
-        for (int p = P.ptr[a]; p < P.ptr[b]; ++p)
-            if (stamp[(size_t)P.col[p]] != t) { stamp[(size_t)P.col[p]] = t; cols.push_back(P.col[p]); }
-        std::sort(cols.begin(), cols.end());
-        const int ns = (int)cols.size();
-        maxslots = std::max(maxslots, ns);
-        maxent = std::max(maxent, P.ptr[b] - P.ptr[a]);
-        for (int k = 0; k < ns; ++k) slot[(size_t)cols[k]] = k;
-        clist.insert(clist.end(), cols.begin(), cols.end());
-        tptr[t + 1] = (int)clist.size();
-        for (int p = P.ptr[a]; p < P.ptr[b]; ++p) ploc[p] = (unsigned short)slot[(size_t)P.col[p]];
-    }
-    maxent = (maxent + 3) & ~3;
-    if ((size_t)maxslots * 128 + (size_t)maxent * 10 + 1100 > 60 * 1024) return;       // (LDS of the kernel)
-    F.row_ptr.upload(row_ptr.data(), row_ptr.size(), st);
-    F.tptr.upload(tptr.data(), tptr.size(), st);
-    F.clist.upload(clist.data(), clist.size(), st);
-    F.pptr.upload(P.ptr.data(), P.ptr.size(), st);
-    F.ploc.upload(ploc.data(), ploc.size(), st);
-    F.pval.upload(P.val.data(), P.val.size(), st);
-    HIP_CHECK(hipStreamSynchronize(st));                     // (the host vectors die at scope end)
-    XferTilesDev &D = F.dev;
-    D.ntiles = nt; D.maxslots = maxslots; D.maxent = maxent; D.nslots = (int64_t)clist.size(); D.nf = P.n; D.nc = P.m;
-    D.row_ptr = F.row_ptr.p; D.tptr = F.tptr.p; D.clist = F.clist.p; D.pptr = F.pptr.p; D.ploc = F.ploc.p; D.pval = F.pval.p;
-    F.ready = true;
-}
-// WAE_XFER_TILES=0: the older prolongation kernel (A/B measurements, tests)
-static bool xfer_tiles_on() { const char *e = getenv("WAE_XFER_TILES"); return !(e && atoi(e) == 0); }
 
 // ----------------------------------------------------------------------------------------------------
 // coefficient tables
 // ----------------------------------------------------------------------------------------------------
-// plane coefficients for one system from term coefficients (aliased terms folded in), conj for op = C
-static void plane_coeffs(const wae_family *h, const double *coeffs, int op, std::vector<zc> &pc) {
-    pc.assign(h->nplanes, zc(0));
-    for (int k = 0; k < h->T; ++k) pc[h->term_plane[k]] += h->term_scale[k] * zc(coeffs[2 * k], coeffs[2 * k + 1]);
-    if (op == WAE_OP_C)
-        for (auto &c : pc) c = std::conj(c);
-}
-// upload [level][sys][slot] tables
+// upload [level][sys][slot] tables (plane_coeffs: family.h)
 static void upload_pc(wae_family *h, const std::vector<std::vector<zc>> &pcs) {
     const int nsys = (int)pcs.size();
     const int nl = (int)h->ops.size();
@@ -784,13 +37,6 @@ static inline const cplx *pc_level(const wae_family *h, int l) { return h->pcdev
 // ----------------------------------------------------------------------------------------------------
 // multigrid V-cycle (all columns in lock-step)
 // ----------------------------------------------------------------------------------------------------
-struct Batch {
-    int nb;     // columns (leading dimension of every multivector)
-    int cps;    // columns per system
-    int nsys;
-    int op;
-};
-
 static void dense_setup(wae_family *h, const Batch &bt) {
     const int L = (int)h->ops.size() - 1;
     if (h->nc <= 0) return;
@@ -974,7 +220,6 @@ static void penalty_polish(wae_family *h, const Batch &bt, const cplx *B, cplx *
 }
 
 // The solver's environment switches, read once per process
-static int env_int(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
 struct GmresEnv {
     bool lazy = env_int("WAE_LAZY", 1) != 0;                  // 0: the normalisation pass instead of the unnormalised basis
     double lazy_limit = getenv("WAE_LAZY_LIMIT") ? atof(getenv("WAE_LAZY_LIMIT")) : 1e100;   // range guard of the unnormalised basis
@@ -997,7 +242,6 @@ static const GmresEnv &gmres_env() { static const GmresEnv e; return e; }
 // the solution is x = V y + alpha g with alpha = (u^H r0 - sum_j y_j c_j)/||u||, which cancels the u^ component of
 // the residual exactly.  Close to an eigenvalue of the NLEVP the operator is nearly singular along g: the undeflated
 // solves needed 50-100 iterations of a long recurrence there, the deflated operator behaves like a regular shift.
-static double now_s();
 struct Gmres {
     wae_family *h;
     const Batch &bt;
@@ -1655,26 +899,6 @@ static int gmres(wae_family *h, const Batch &bt, const cplx *B, cplx *X, double 
 // ----------------------------------------------------------------------------------------------------
 // helpers
 // ----------------------------------------------------------------------------------------------------
-static void require_solver(const wae_family *h) {
-    if (!h->solver_ready) throw WaeError(WAE_ERR_INVALID, "wae_solver_setup has not been called");
-}
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-template <class F> static int guarded(F &&f) {
-    try {
-        return f();
-    } catch (const WaeError &e) {
-        wae_set_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        wae_set_error("out of host memory");
-        return WAE_ERR_INVALID;
-    } catch (const std::exception &e) {
-        wae_set_error(e.what());
-        return WAE_ERR_INVALID;
-    }
-}
-
 static int info_code(wae_solve_info &i) {   // also clears the internal stagnation marker bit
 
     const bool stag = (i.levels & (1 << 16)) != 0;
@@ -1951,106 +1175,6 @@ int wae_device_count(int *n) {
     });
 }
 
-int wae_family_create(wae_family **out, int64_t d, int32_t T, int32_t index_bytes, int32_t base, int32_t orientation,
-                      const void *const *ptr, const void *const *idx, const double *const *val, int32_t device) {
-    return wae_family_create_opts(out, d, T, index_bytes, base, orientation, ptr, idx, val, device, nullptr, 0);
-}
-
-int wae_family_create_opts(wae_family **out, int64_t d, int32_t T, int32_t index_bytes, int32_t base, int32_t orientation,
-                           const void *const *ptr, const void *const *idx, const double *const *val, int32_t device, const double *opts,
-                           int32_t nopts) {
-    return guarded([&]() {
-        WAE_REQUIRE(out && d > 0 && T > 0 && T <= 64, "bad d/T");
-        WAE_REQUIRE(nopts >= 0 && (nopts == 0 || opts), "bad opts");
-        const double sym_tol = nopts > 0 ? opts[0] : 0.0;
-        WAE_REQUIRE(sym_tol >= 0.0 && sym_tol <= 1e-8, "opts[0] (symmetry tolerance) must lie in [0, 1e-8]");
-        WAE_REQUIRE(index_bytes == 4 || index_bytes == 8, "index_bytes must be 4 or 8");
-        WAE_REQUIRE(base == 0 || base == 1, "base must be 0 or 1");
-        WAE_REQUIRE(d < 2147483647, "d too large for 32-bit indices");
-        int ndev = 0;
-        HIP_CHECK(hipGetDeviceCount(&ndev));
-        WAE_REQUIRE(device >= 0 && device < ndev, "no such HIP device");
-        HIP_CHECK(hipSetDevice(device));
-        std::unique_ptr<wae_family> h(new wae_family);
-        h->device = device;
-        h->d = d;
-        h->T = T;
-        HIP_CHECK(hipStreamCreate(&h->stream));
-        h->term_plane.resize(T);
-        h->term_scale.resize(T);
-        h->term_nnz.resize(T);
-        const bool cdbg = getenv("WAE_SETUP_DEBUG") != nullptr;
-        double tc = now_s();
-        auto clap = [&](const char *what) { if (cdbg) { const double t = now_s(); fprintf(stderr, "[create] %-34s %.3f s\n", what, t - tc); tc = t; } };
-        std::vector<std::future<CsrZ>> conv;                     // the terms' conversions side by side
-        for (int k = 0; k < T; ++k)
-            conv.push_back(std::async(std::launch::async, [&, k]() { return term_to_csr(d, index_bytes, base, orientation, ptr[k], idx[k], val[k]); }));
-        std::vector<CsrZ> conv_out(T);
-        {
-            std::exception_ptr first;
-            for (int k = 0; k < T; ++k) {
-                try { conv_out[k] = conv[k].get(); } catch (...) { if (!first) first = std::current_exception(); }
-            }
-            if (first) std::rethrow_exception(first);
-        }
-        for (int k = 0; k < T; ++k) {
-            CsrZ A = std::move(conv_out[k]);
-            h->term_nnz[k] = A.nnz();
-            bool found = false;
-            for (int q = 0; q < (int)h->planes0.size() && !found; ++q) {
-                zc s;
-                if (proportional(A, h->planes0[q], s)) { h->term_plane[k] = q; h->term_scale[k] = s; found = true; }
-            }
-            if (!found) {
-                h->term_plane[k] = (int)h->planes0.size();
-                h->term_scale[k] = 1.0;
-                h->planes0.push_back(std::move(A));
-            }
-        }
-        h->nplanes = (int)h->planes0.size();
-        clap("terms to CSR, distinct planes");
-        // renumber the rows into compact tiles (tiles.h); WAE_REORDER=0 keeps the caller's numbering (A/B measurements)
-        static const bool reorder_on = !(getenv("WAE_REORDER") && atoi(getenv("WAE_REORDER")) == 0);
-        if (reorder_on) {
-            // fine level: two window buffers of 608 rows x 128 B.  WAE_TILE_NBUF=3: three of 400 (two windows in flight while a
-            // third is read) -- measured slower, 966 vs 733 us at 1M unknowns and 64 columns: a chunk costs a wavefront the same
-            // ~10 k cycles whether its tile has 174 rows or 256 (lane = row), the gather was not what it waited for.
-            const int nbuf0 = getenv("WAE_TILE_NBUF") ? atoi(getenv("WAE_TILE_NBUF")) : 2;          // (read per call: the tests switch it)
-            const int wcap = getenv("WAE_TILE_WCAP") ? atoi(getenv("WAE_TILE_WCAP")) : (nbuf0 == 3 ? 400 : 608);
-            static const int thick = getenv("WAE_TILE_THICK") ? atoi(getenv("WAE_TILE_THICK")) : 6;
-            const double tq0 = now_s();
-            TilePlan plan = plan_tiles(union_pattern(h->planes0), 256, wcap, thick);
-            const double tq1 = now_s();
-            if (!plan.perm.empty()) {
-                std::vector<std::future<CsrZ>> jobs;
-                for (size_t q = 0; q < h->planes0.size(); ++q)
-                    jobs.push_back(std::async(std::launch::async, [&, q]() { return permute_symmetric(h->planes0[q], plan.perm, plan.iperm); }));
-                for (size_t q = 0; q < h->planes0.size(); ++q) h->planes0[q] = jobs[q].get();
-                h->perm_h = plan.perm;
-                h->perm_dev.upload(h->perm_h.data(), h->perm_h.size(), h->stream);
-                h->tile_row_ptr = plan.row_ptr;
-            }
-            if (getenv("WAE_SETUP_DEBUG"))
-                fprintf(stderr, "[create] tile plan %.3f s (%zu tiles, largest window %d), permutation of the planes %.3f s\n", tq1 - tq0,
-                        plan.row_ptr.empty() ? (size_t)0 : plan.row_ptr.size() - 1, plan.wmax, now_s() - tq1);
-        }
-        h->ops.resize(1);
-        h->slot_plane.resize(1);
-        tc = now_s();
-        h->slot_plane[0] = build_levelop(h->ops[0], h->planes0, h->stream, sym_tol);
-        clap("operator groups (CSR, both orientations)");
-        if (!h->tile_row_ptr.empty()) {
-            build_level_tiles(h->ops[0], h->planes0, h->slot_plane[0], h->tile_row_ptr, h->stream, 2, getenv("WAE_TILE_NBUF") ? atoi(getenv("WAE_TILE_NBUF")) : 2);
-            clap("tile storage");
-        }
-        cplx one = {1.0, 0.0};
-        h->one_dev.upload(&one, 1, h->stream);
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-        *out = h.release();
-        return WAE_OK;
-    });
-}
-
 int wae_family_destroy(wae_family *h) {
     return guarded([&]() {
         if (h) {
@@ -2226,337 +1350,6 @@ int wae_spmv_sum_multi(wae_family *h, const double *coeffs, const double *X, dou
         HIP_CHECK(hipMemcpyAsync(Y, h->io_b.p, (size_t)h->d * sizeof(cplx), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         xi.release(); yi.release(); acc.release(); pcd.release();
-        return WAE_OK;
-    });
-}
-
-int wae_solver_setup(wae_family *h, const double *coeffs_ref, const double *opts, int32_t nopts) {
-    return guarded([&]() {
-        WAE_REQUIRE(h && coeffs_ref, "bad argument");
-        HIP_CHECK(hipSetDevice(h->device));
-        AmgOptions ao;
-        auto opt = [&](int i, double dflt) { return (opts && i < nopts && opts[i] > 0) ? opts[i] : dflt; };
-        ao.theta = opt(0, 0.02);
-        ao.max_coarse = (int64_t)opt(1, 128);
-        h->jac_w = opt(2, 0.8);
-        // Post-smoothing and light-cycle weights (round 4; measured at 1M unknowns, pass in seconds, pre / post / light): 0.8 / 0.8 / 0.8
-        // 2.02; 0.8 / 0.9 / 0.8 1.93; 0.9 / 1.0 / 0.8 2.07 (better snapshot solves, worse projected ones); 0.8 / 0.9 / 0.65 1.88;
-        // 0.8 / 0.9 / 0.5 1.84; 0.8 / 0.9 / 0.3 1.80.  The light cycle's ONE sweep wants a small weight: its job is only to keep the
-        // coarse correction honest on the components the coarse level cannot see.  0.5 is the default (eigenpair residuals and rank
-        // gap of the benchmark unchanged: 6.6e-9, 1.3e9).
-        h->jac_w_post = opt(10, 0.9);
-        h->jac_w_light = opt(11, 0.5);
-        h->nsweeps = (int)opt(3, 1);
-        h->restart = (int)opt(4, 30);
-        ao.penalty_ratio = opt(5, 1e8);
-        h->NB = (int)opt(6, 64);
-        WAE_REQUIRE(h->NB >= 1 && h->NB <= 256, "batch width must be in 1..256");
-        WAE_REQUIRE(h->restart >= 2 && h->restart <= 200, "restart must be in 2..200");
-        // drop a previous hierarchy
-        for (size_t l = 1; l < h->ops.size(); ++l) {
-            h->ops[l].diag.release();
-            for (auto &G : h->ops[l].groups) { G.rowptr.release(); G.col.release(); G.rowptr_t.release(); G.col_t.release(); G.vals.release(); G.vals_t.release(); }
-        }
-        h->ops.resize(1);
-        h->slot_plane.resize(1);
-        for (auto &X : h->xfer) { X.p_ptr.release(); X.p_col.release(); X.r_ptr.release(); X.r_col.release(); X.p_val.release(); X.r_val.release(); }
-        h->xfer.clear();
-        std::vector<zc> pc;
-        plane_coeffs(h, coeffs_ref, WAE_OP_N, pc);
-        std::vector<AmgLevel> lv;
-        std::vector<char> pen;
-        // opts[7]: bit k set = term k stays out of the shape matrix (strength graph, aggregation, prolongator smoothing)
-        const uint64_t excl = (uint64_t)opt(7, 0.0);
-        std::vector<zc> pc_shape;
-        if (excl) {
-            std::vector<double> cs(coeffs_ref, coeffs_ref + (size_t)2 * h->T);
-            for (int k = 0; k < h->T && k < 52; ++k)
-                if (excl >> k & 1) cs[2 * k] = cs[2 * k + 1] = 0.0;
-            plane_coeffs(h, cs.data(), WAE_OP_N, pc_shape);
-        }
-        const double t_amg0 = now_s();
-        // The Krylov basis -- (restart + 1) vectors of d x NB complex numbers, 42 GB at 1M unknowns -- takes the driver about a
-        // second to map: it is requested now, on a helper thread, and is there when the host part of the set-up is done.
-        // opts[8], opts[9] (hints): probe columns and snapshot capacity of the contour integrals to come -- their snapshot store
-        // (5 GB at 1M unknowns x 8 columns x 40 snapshots) and the resident term products (20 GB) are then mapped here as well,
-        // behind the host work, instead of in the first pass (0.4 s of its snapshot phase).
-        std::future<void> basis_job;
-        {
-            const size_t vec = (size_t)h->d * h->NB, need = vec * (size_t)(h->restart + 1);
-            const size_t hint_l = (size_t)opt(8, 0.0), hint_s = (size_t)opt(9, 0.0);
-            const size_t need_q = hint_l > 0 && hint_s > 0 && hint_l <= (size_t)h->NB ? (size_t)h->d * hint_l * hint_s : 0;
-            const size_t need_w = need_q * (size_t)h->nplanes;
-            h->rb.wait_w();
-            if (h->V.n != need || h->rbQ.n < need_q || h->rb.W.n < need_w)
-                basis_job = std::async(std::launch::async, [h, need, need_q, need_w]() {
-                    HIP_CHECK(hipSetDevice(h->device));
-                    if (h->V.n != need) h->V.alloc(need);
-                    // (the snapshot stores are written once here as well: the first kernels that touch freshly mapped device memory
-                    // ran slower -- 0.14 s over the first pass's snapshot phase on some boxes; behind the host work it costs nothing)
-                    const bool new_q = h->rbQ.n < need_q, new_w = h->rb.W.n < need_w;
-                    if (new_q) h->rbQ.alloc(need_q);
-                    if (new_w) h->rb.W.alloc(need_w);
-                    if (new_q && need_q) HIP_CHECK(hipMemset(h->rbQ.p, 0, need_q * sizeof(cplx)));
-                    if (new_w && need_w) HIP_CHECK(hipMemset(h->rb.W.p, 0, need_w * sizeof(cplx)));
-                    HIP_CHECK(hipDeviceSynchronize());
-                });
-        }
-        struct Join { std::future<void> &f; ~Join() { if (f.valid()) f.wait(); } } basis_join{basis_job};     // (also on an exception)
-        // fine-level aggregation in the caller's node order (iperm[o] = internal index of the caller's node o)
-        std::vector<int> visit0;
-        if (!h->perm_h.empty()) { visit0.resize(h->perm_h.size()); for (size_t i = 0; i < h->perm_h.size(); ++i) visit0[h->perm_h[i]] = (int)i; }
-        // Everything of level 1 -- tile plan, renumbering, operator groups, tile storage, the transfer operators of level 0 and the tile
-        // storage of the restriction -- needs only that level's planes and the first prolongator: it runs on a helper thread, with a
-        // stream of its own, while the host builds the deeper levels (round 3, second half: 0.7 s of work of which 0.15 s used to be
-        // hidden).  The level's operator is built into a local object and moved into the handle once the number of levels is known.
-        const int tile1 = getenv("WAE_TILE_LEVEL1") ? atoi(getenv("WAE_TILE_LEVEL1")) : 1;      // (read per call: the tests switch it)
-        const bool want_plan = tile1 && !h->tile_row_ptr.empty();
-        struct Level1Work {
-            std::vector<int> row_ptr, perm, iperm;      // tile plan of level 1 (empty: no tiles)
-            int wmax = 0;
-            std::vector<CsrZ> planes;                    // the level's planes in the new numbering (amg_setup still reads the old ones)
-            LevelOp op;                                  // level-1 operator (groups + tiles)
-            std::vector<int> slot_plane;
-            Transfer xfer0;                              // P / R of level 0 (+ restriction tiles)
-            bool built = false;
-            double seconds = 0.0;
-        } l1;
-        std::future<void> l1_job;
-        struct JoinL1 { std::future<void> &f; ~JoinL1() { if (f.valid()) f.wait(); } } l1_join{l1_job};
-        auto upload_transfer = [](Transfer &X, const AmgLevel &L, hipStream_t s2) {
-            X.nf = L.P.n; X.nc = L.P.m;
-            X.p_ptr.upload(L.P.ptr.data(), L.P.ptr.size(), s2);
-            X.p_col.upload(L.P.col.data(), L.P.col.size(), s2);
-            X.p_val.upload(L.P.val.data(), L.P.val.size(), s2);
-            X.r_ptr.upload(L.R.ptr.data(), L.R.ptr.size(), s2);
-            X.r_col.upload(L.R.col.data(), L.R.col.size(), s2);
-            X.r_val.upload(L.R.val.data(), L.R.val.size(), s2);
-            HIP_CHECK(hipStreamSynchronize(s2));
-        };
-        auto rename_cols = [](CsrD &A, const std::vector<int> &ip) {            // column c -> ip[c], rows re-sorted
-            std::vector<std::pair<int, double>> row;
-            for (int64_t i = 0; i < A.n; ++i) {
-                row.clear();
-                for (int p = A.ptr[i]; p < A.ptr[i + 1]; ++p) row.emplace_back(ip[A.col[p]], A.val[p]);
-                std::sort(row.begin(), row.end(), [](const std::pair<int, double> &x, const std::pair<int, double> &y) { return x.first < y.first; });
-                for (int p = A.ptr[i], k = 0; p < A.ptr[i + 1]; ++p, ++k) { A.col[p] = row[k].first; A.val[p] = row[k].second; }
-            }
-        };
-        auto permute_rows = [](CsrD &A, const std::vector<int> &pm) {           // new row i = old row pm[i]
-            CsrD B;
-            B.n = A.n; B.m = A.m;
-            B.ptr.assign(A.n + 1, 0);
-            B.col.reserve(A.col.size()); B.val.reserve(A.val.size());
-            for (int64_t i = 0; i < A.n; ++i) {
-                const int o = pm[i];
-                B.col.insert(B.col.end(), A.col.begin() + A.ptr[o], A.col.begin() + A.ptr[o + 1]);
-                B.val.insert(B.val.end(), A.val.begin() + A.ptr[o], A.val.begin() + A.ptr[o + 1]);
-                B.ptr[i + 1] = (int)B.col.size();
-            }
-            A = std::move(B);
-        };
-        amg_setup(h->planes0, pc, ao, lv, &pen, excl ? &pc_shape : nullptr, visit0.empty() ? nullptr : &visit0,
-                  [&](const AmgLevel &L) {
-                      if (!want_plan || l1_job.valid() || &L != &lv[0]) return;
-                      // (the level object stays where it is -- amg_setup reserves its levels -- and nothing else touches it until the join)
-                      l1_job = std::async(std::launch::async, [&, h]() {
-                          const double tq0 = now_s();
-                          HIP_CHECK(hipSetDevice(h->device));
-                          hipStream_t s3;
-                          HIP_CHECK(hipStreamCreate(&s3));
-                          struct Del { hipStream_t s; ~Del() { (void)hipStreamDestroy(s); } } del{s3};
-                          const int wcap = getenv("WAE_TILE_WCAP1") ? atoi(getenv("WAE_TILE_WCAP1")) : 608;        // (two window buffers)
-                          const int thick = getenv("WAE_TILE_THICK") ? atoi(getenv("WAE_TILE_THICK")) : 6;
-                          AmgLevel &L0 = lv[0];
-                          const bool jdbg = getenv("WAE_SETUP_DEBUG") != nullptr;
-                          double tj = now_s();
-                          auto jlap = [&](const char *what) { if (jdbg) { const double t = now_s(); fprintf(stderr, "[setup]   (level-1 thread) %-22s %.3f s\n", what, t - tj); tj = t; } };
-                          TilePlan plan = plan_tiles(union_pattern(L0.coarse_planes), 128, wcap, thick);
-                          l1.wmax = plan.wmax;
-                          jlap("tile plan");
-                          if (!plan.perm.empty()) {
-                              // Level 1 renumbered into tiles as well (the numbering of a coarse level is nobody's business but the
-                              // hierarchy's): P of level 0 changes its columns, R its rows; the transfer to level 2 the other way round
-                              // (after the join, when it exists).
-                              l1.perm = plan.perm; l1.iperm = plan.iperm; l1.row_ptr = plan.row_ptr;
-                              std::vector<std::future<void>> pj;
-                              l1.planes.resize(L0.coarse_planes.size());
-                              for (size_t q = 0; q < L0.coarse_planes.size(); ++q)
-                                  pj.push_back(std::async(std::launch::async, [&L0, q, this_l1 = &l1]() {
-                                      this_l1->planes[q] = permute_symmetric(L0.coarse_planes[q], this_l1->perm, this_l1->iperm);
-                                  }));
-                              auto j1 = std::async(std::launch::async, [&]() { rename_cols(L0.P, l1.iperm); });
-                              permute_rows(L0.R, l1.perm);
-                              j1.get();
-                              for (auto &j : pj) j.get();
-                          }
-                          jlap("permutation");
-                          // the transfer operators and the restriction's tile storage beside the operator (a thread and a stream of their own)
-                          const bool with_tiles = !l1.row_ptr.empty();
-                          auto xj = std::async(std::launch::async, [&, h, with_tiles, wcap]() {
-                              HIP_CHECK(hipSetDevice(h->device));
-                              hipStream_t s2;
-                              HIP_CHECK(hipStreamCreate(&s2));
-                              struct Del2 { hipStream_t s; ~Del2() { (void)hipStreamDestroy(s); } } del2{s2};
-                              upload_transfer(l1.xfer0, L0, s2);
-                              const int tile_r = getenv("WAE_TILE_RESTRICT") ? atoi(getenv("WAE_TILE_RESTRICT")) : 1;
-                              if (with_tiles && tile_r) build_restriction_tiles(l1.xfer0, L0.R, wcap, s2);
-                              if (!h->tile_row_ptr.empty() && xfer_tiles_on()) build_transfer_tiles(l1.xfer0, L0.P, h->tile_row_ptr, s2);
-                          });
-                          const std::vector<CsrZ> &pl1 = l1.planes.empty() ? L0.coarse_planes : l1.planes;
-                          l1.slot_plane = build_levelop(l1.op, pl1, s3, WAE_LEVEL_SYM_TOL);
-                          jlap("operator groups");
-                          if (with_tiles) build_level_tiles(l1.op, pl1, l1.slot_plane, l1.row_ptr, s3, 4);
-                          HIP_CHECK(hipStreamSynchronize(s3));
-                          jlap("tile storage");
-                          xj.get();
-                          jlap("wait for the transfer");
-                          l1.built = true;
-                          l1.seconds = now_s() - tq0;
-                      });
-                  });
-        const double t_amg1 = now_s();
-        if (getenv("WAE_SETUP_DEBUG")) {
-            fprintf(stderr, "[setup] amg_setup (host) %.3f s\n", t_amg1 - t_amg0);
-            fprintf(stderr, "[setup] level 0: n=%lld nnz/plane:", (long long)h->planes0[0].n);
-            for (const CsrZ &A : h->planes0) fprintf(stderr, " %lld", (long long)A.nnz());
-            fprintf(stderr, "\n");
-            for (size_t l = 0; l < lv.size(); ++l) {
-                fprintf(stderr, "[setup] level %zu: n=%lld P nnz=%lld nnz/plane:", l + 1, (long long)lv[l].P.m, (long long)lv[l].P.col.size());
-                for (const CsrZ &A : lv[l].coarse_planes) fprintf(stderr, " %lld", (long long)A.nnz());
-                fprintf(stderr, "\n");
-            }
-        }
-        hipStream_t st = h->stream;
-        double t_lap = now_s();
-        auto lap = [&](const char *what) {
-            if (!getenv("WAE_SETUP_DEBUG")) return;
-            HIP_CHECK(hipStreamSynchronize(st));
-            const double t = now_s();
-            fprintf(stderr, "[setup] %-34s %.3f s\n", what, t - t_lap);
-            t_lap = t;
-        };
-        if (l1_job.valid()) l1_job.get();                                   // (rethrows)
-        if (!l1.planes.empty()) lv[0].coarse_planes = std::move(l1.planes);
-        if (l1.built && !l1.perm.empty() && lv.size() >= 2) {              // the transfer to level 2 in the new numbering of level 1
-            auto j3 = std::async(std::launch::async, [&]() { permute_rows(lv[1].P, l1.perm); });
-            rename_cols(lv[1].R, l1.iperm);
-            j3.get();
-        }
-        const bool l1_dense = lv.size() < 2;                                // (a two-level hierarchy: level 1 is the dense one; its tiles are not used)
-        if (getenv("WAE_SETUP_DEBUG") && l1.built)
-            fprintf(stderr, "[setup] level 1 on the helper thread: plan + permutation + operator + tiles + transfer %.3f s (%zu tiles, largest window %d)\n",
-                    l1.seconds, l1.row_ptr.empty() ? (size_t)0 : l1.row_ptr.size() - 1, l1.wmax);
-        lap("wait for level 1 (helper thread)");
-        {   // the penalty rows' own sub-block, plane by plane (compact numbering)
-            std::vector<int> rows, loc(pen.size(), -1);
-            for (size_t i = 0; i < pen.size(); ++i)
-                if (pen[i]) { loc[i] = (int)rows.size(); rows.push_back((int)i); }
-            h->n_penalty = (int64_t)rows.size();
-            if (!rows.empty()) {
-                std::vector<CsrZ> sub(h->planes0.size());
-                for (size_t q = 0; q < h->planes0.size(); ++q) {
-                    const CsrZ &A = h->planes0[q];
-                    CsrZ &B = sub[q];
-                    B.n = B.m = (int64_t)rows.size();
-                    B.ptr.assign(rows.size() + 1, 0);
-                    for (size_t i = 0; i < rows.size(); ++i) {
-                        for (int pp = A.ptr[rows[i]]; pp < A.ptr[rows[i] + 1]; ++pp)
-                            if (loc[A.col[pp]] >= 0) { B.col.push_back(loc[A.col[pp]]); B.val.push_back(A.val[pp]); }
-                        B.ptr[i + 1] = (int)B.col.size();
-                    }
-                }
-                h->pen_slot = build_levelop(h->pen_op, sub, st, WAE_LEVEL_SYM_TOL);
-                for (size_t q = 0; q < h->planes0.size(); ++q) {      // the same rows with ALL their columns (global numbering)
-                    const CsrZ &A = h->planes0[q];
-                    CsrZ &B = sub[q];
-                    B = CsrZ();
-                    B.n = (int64_t)rows.size();
-                    B.m = A.m;
-                    B.ptr.assign(rows.size() + 1, 0);
-                    for (size_t i = 0; i < rows.size(); ++i) {
-                        B.col.insert(B.col.end(), A.col.begin() + A.ptr[rows[i]], A.col.begin() + A.ptr[rows[i] + 1]);
-                        B.val.insert(B.val.end(), A.val.begin() + A.ptr[rows[i]], A.val.begin() + A.ptr[rows[i] + 1]);
-                        B.ptr[i + 1] = (int)B.col.size();
-                    }
-                }
-                h->pen_row_slot = build_levelop(h->pen_row_op, sub, st, WAE_LEVEL_SYM_TOL);
-                h->pen_rows.upload(rows.data(), rows.size(), st);
-                const size_t cnt = rows.size() * (size_t)h->NB;
-                h->pen_b.alloc(cnt); h->pen_x.alloc(cnt); h->pen_t.alloc(cnt);
-                HIP_CHECK(hipStreamSynchronize(st));
-            }
-        }
-        lap("penalty operators");
-        h->ops.resize(lv.size() + 1);
-        h->slot_plane.resize(lv.size() + 1);
-        h->xfer.resize(lv.size());
-        for (size_t l = 0; l < lv.size(); ++l) {
-            if (l == 0 && l1.built) {
-                h->slot_plane[1] = l1.slot_plane;
-                if (l1_dense) l1.op.tiles = TileStore();                   // (not reached in practice: a tiled fine level has a large level 1)
-                h->ops[1] = std::move(l1.op);
-                h->xfer[0] = std::move(l1.xfer0);
-                continue;
-            }
-            h->slot_plane[l + 1] = build_levelop(h->ops[l + 1], lv[l].coarse_planes, st, WAE_LEVEL_SYM_TOL);
-            upload_transfer(h->xfer[l], lv[l], st);
-            if (l == 0 && !h->tile_row_ptr.empty() && xfer_tiles_on()) build_transfer_tiles(h->xfer[0], lv[0].P, h->tile_row_ptr, st);
-        }
-        lap("levels >= 2");
-        // dense planes of the coarsest level (plane order, row-major)
-        const std::vector<CsrZ> &last = lv.empty() ? h->planes0 : lv.back().coarse_planes;
-        h->nc = last[0].n;
-        WAE_REQUIRE(h->nc <= 2048, "coarsest level too large for the dense solver (increase levels / lower max_coarse)");
-        {
-            const size_t nn = (size_t)h->nc * h->nc;
-            std::vector<cplx> dp(nn * h->nplanes, cplx{0.0, 0.0});
-            const std::vector<int> &sp = h->slot_plane.back();
-            for (int s = 0; s < h->nplanes; ++s) {
-                const CsrZ &A = last[sp[s]];
-                for (int64_t i = 0; i < A.n; ++i)
-                    for (int p = A.ptr[i]; p < A.ptr[i + 1]; ++p) dp[(size_t)s * nn + (size_t)i * h->nc + A.col[p]] = cplx{A.val[p].real(), A.val[p].imag()};
-            }
-            h->dense_planes.upload(dp.data(), dp.size(), st);
-            HIP_CHECK(hipStreamSynchronize(st));
-            h->Ainv.alloc(nn * h->NB);
-            h->dstatus.alloc(1);
-        }
-        lap("dense coarsest level");
-        // workspaces
-        const int NB = h->NB, m = h->restart;
-        const int nl = (int)h->ops.size();
-        h->lx.resize(nl); h->lb.resize(nl); h->lt.resize(nl);
-        for (int l = 0; l < nl; ++l) {
-            const size_t cnt = (size_t)h->ops[l].n * NB;
-            h->lx[l].alloc(cnt); h->lb[l].alloc(cnt); h->lt[l].alloc(cnt);
-        }
-        const size_t vec = (size_t)h->d * NB;
-        lap("level workspaces");
-        if (basis_job.valid()) basis_job.get();                      // (rethrows an allocation failure)
-        lap("wait for the Krylov basis");
-        if (h->V.n != vec * (m + 1)) h->V.alloc(vec * (m + 1));
-        h->W.alloc(vec); h->Xs.alloc(vec); h->Bs.alloc(vec); h->U.alloc(vec);
-        // masked (converged) columns keep stale data: make sure "stale" is never an uninitialised NaN pattern
-        HIP_CHECK(hipMemsetAsync(h->V.p, 0, vec * (m + 1) * sizeof(cplx), st));
-        HIP_CHECK(hipMemsetAsync(h->W.p, 0, vec * sizeof(cplx), st));
-        HIP_CHECK(hipMemsetAsync(h->U.p, 0, vec * sizeof(cplx), st));
-        for (int l = 0; l < nl; ++l) {
-            const size_t cnt = (size_t)h->ops[l].n * NB;
-            HIP_CHECK(hipMemsetAsync(h->lx[l].p, 0, cnt * sizeof(cplx), st));
-            HIP_CHECK(hipMemsetAsync(h->lb[l].p, 0, cnt * sizeof(cplx), st));
-            HIP_CHECK(hipMemsetAsync(h->lt[l].p, 0, cnt * sizeof(cplx), st));
-        }
-        HIP_CHECK(hipStreamSynchronize(st));
-        h->partial.alloc((size_t)1024 * 32 * NB);   // DOT_BLOCKS x 32 vectors x NB columns
-        h->hdev.alloc((size_t)2 * (m + 3) * NB);     // second half: scratch for the re-orthogonalisation pass
-        h->vsq.alloc((size_t)(m + 3) * NB);
-        h->ydev.alloc((size_t)(m + 1) * NB);
-        if (h->h_pinned) { (void)hipHostFree(h->h_pinned); h->h_pinned = nullptr; }
-        HIP_CHECK(hipHostMalloc((void **)&h->h_pinned, (size_t)(m + 2) * NB * sizeof(cplx)));
-        h->solver_ready = true;
-        lap("other workspaces + memsets");
-        if (getenv("WAE_SETUP_DEBUG")) fprintf(stderr, "[setup] uploads + workspaces %.3f s\n", now_s() - t_amg1);
         return WAE_OK;
     });
 }

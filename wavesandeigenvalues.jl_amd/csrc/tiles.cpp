@@ -287,6 +287,30 @@ CsrZ permute_symmetric(const CsrZ &A, const std::vector<int> &perm, const std::v
     return B;
 }
 
+void rename_cols(CsrD &A, const std::vector<int> &ip) {
+    std::vector<std::pair<int, double>> row;
+    for (int64_t i = 0; i < A.n; ++i) {
+        row.clear();
+        for (int p = A.ptr[i]; p < A.ptr[i + 1]; ++p) row.emplace_back(ip[A.col[p]], A.val[p]);
+        std::sort(row.begin(), row.end(), [](const std::pair<int, double> &x, const std::pair<int, double> &y) { return x.first < y.first; });
+        for (int p = A.ptr[i], k = 0; p < A.ptr[i + 1]; ++p, ++k) { A.col[p] = row[k].first; A.val[p] = row[k].second; }
+    }
+}
+
+void permute_rows(CsrD &A, const std::vector<int> &pm) {
+    CsrD B;
+    B.n = A.n; B.m = A.m;
+    B.ptr.assign(A.n + 1, 0);
+    B.col.reserve(A.col.size()); B.val.reserve(A.val.size());
+    for (int64_t i = 0; i < A.n; ++i) {
+        const int o = pm[i];
+        B.col.insert(B.col.end(), A.col.begin() + A.ptr[o], A.col.begin() + A.ptr[o + 1]);
+        B.val.insert(B.val.end(), A.val.begin() + A.ptr[o], A.val.begin() + A.ptr[o + 1]);
+        B.ptr[i + 1] = (int)B.col.size();
+    }
+    A = std::move(B);
+}
+
 TileWindows build_windows(const Pattern &U, const std::vector<int> &row_ptr) {
     TileWindows W;
     const size_t nt = row_ptr.size() - 1;

@@ -24,6 +24,9 @@ TilePlan plan_tiles(const Pattern &U, int tile_rows, int wcap, int thick);
 
 // B = P A P^T with P the permutation new -> old (columns re-sorted)
 CsrZ permute_symmetric(const CsrZ &A, const std::vector<int> &perm, const std::vector<int> &iperm);
+// the two halves of that for a rectangular real matrix (the transfer operators of a renumbered coarse level), in place:
+void rename_cols(CsrD &A, const std::vector<int> &iperm);    // column c -> iperm[c], rows re-sorted
+void permute_rows(CsrD &A, const std::vector<int> &perm);    // new row i = old row perm[i]
 
 // Tile-local storage of one pattern group: per (tile, wavefront) a slice of 64 / lpr rows, lpr lanes per row (lane lpr i + h
 // holds the entries h, h + lpr, ... of row i), padded to 1 / lpr of the longest row of the slice and stored entry-major
