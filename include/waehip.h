@@ -103,7 +103,8 @@ int wae_spmv_sum_multi(wae_family *h, const double *coeffs, const double *X, dou
  * Re(sum_k c_ref_k A_k); every term is Galerkin-projected so that coarse operators are again families).
  * Replaces the symbolic analysis UMFPACK repeats at every `\`/`lu` call (beyn.jl:65,257; perturbation.jl:329).
  * Must be called once before wae_solve / wae_beyn_moments / wae_arnoldi_shiftinvert / wae_perturb.
- * opts (may be NULL -> defaults): [0] strength threshold (0.02), [1] max coarse size (128),
+ * opts (may be NULL -> defaults): [0] strength threshold (0.02), [1] max coarse size (128; the coarsest
+ *   level is inverted dense by one workgroup per system and may have at most 2048 unknowns: WAE_ERR_INVALID beyond),
  *   [2] Jacobi weight (0.8), [3] pre/post sweeps (1), [4] GMRES restart (30), [5] penalty-row ratio (1e8),
  *   [6] batch width (columns solved in lock-step, 64).
  *   [7] bit mask (as a double) of terms kept OUT of the shape matrix that the strength graph, the aggregates and the
@@ -414,6 +415,51 @@ int wae_bench_triad(int32_t device, int64_t n, int32_t reps, double *gbs_out);
 int wae_debug_spmv(wae_family *h, int32_t which, int32_t level, int32_t mode, const double *coeffs, int32_t ncoef, const double *X,
                    const double *B, double *Y, double *B2, int32_t r, int32_t op, double jac_w, const uint8_t *cmask, int32_t flags,
                    int64_t *n_in_q, int64_t *n_out_q);
+
+/* The streaming and reduction kernels under the lock-step GMRES, the snapshot basis, the Beyn accumulation, the batched
+ * perturbation and the dense coarse level, ONE library launch per call (the dense level: assemble, invert, apply), so that tests/
+ * can compare each with a reference of its own.  Needs no family and no solver set-up: the entry uploads the caller's arrays to
+ * `device`, allocates the scratch of the reductions as the solver set-up sizes it, runs the launch on a stream of its own, copies
+ * every array back and synchronises.
+ *   op     one of WAE_VEC_* below; sz[0..nsz) its sizes, bufs[0..nbuf) its arrays in the order listed (complex128, lens[i] entries
+ *          each; NULL = an optional argument left out).  Multivectors are in the library's interleaved layout: vector i of an
+ *          [nv][n][nb] array starts `stride` entries after vector i-1, entry (row, b) of a vector at row*nb + b.
+ *   cmask  NULL or one byte per 8-column chunk (only the operations marked `m`); perm: NULL or d row indices (BEYN_ACCUM only);
+ *          status_out: NULL or the status word of the dense inversion (DENSE only; 0 = every pivot non-zero).
+ *   A size outside the ranges a launcher accepts, or an array shorter than the sizes need: WAE_ERR_INVALID, nothing is launched
+ *   past the point of the refusal.
+ * Contract of a masked chunk (cmask byte 0), as the consumers rely on it (kernels.hip gmres_step_kernel, gmres_pair_coef_kernel read
+ * the reductions of every column, retired ones included, and take 0 for "column retired": 1/norm = 0 keeps it out of every later
+ * coefficient): vector outputs of its columns keep what they held; every reduction output of its columns (dots, norms, 1/norm^2,
+ * Gram entries) is WRITTEN as exact 0.  Columns never mix: a NaN in one column changes no output of another.
+ *                          sz                                   bufs
+ *   DOTS            m   n nb nv stride          V W out[nv][nb] scale[nv][nb]?      (scale given: launch_dots_scaled)
+ *   NORMS           m   n nb                    X out[nb]
+ *   DOTS_MULTI          n nb nv nw sv sw        V W out[nv][nw][nb]
+ *   AXPY_NEG        m   n nb nv stride          V h[nv][nb] W                       W -= sum_i h_i V_i  (nv = 0 allowed)
+ *   LINCOMB / _ADD      n nb nv stride          V y[nv][nb] Y                       Y (+)= sum_i y_i V_i
+ *   AXPY_NEG_NORM   m   n nb nv stride          V h W norms[nb] base? inv[nb]?      W = (base or W) - V h, its norms, 1/norm^2
+ *   AXPY_NEG_MULTI      n nb nv stride cnt ws   V h[nv][cnt][nb] W (cnt vectors, ws apart)
+ *   DOTS2           m   n nb nv stride          V W1 W2 out1 out2 gram[3][nb] scale[nv][nb]
+ *   AXPY2           m   n nb nv stride          V c1 c2m alpha[nb] W1 W2 norms[2][nb] inv[2][nb]
+ *   LINCOMB_REP         n nb nv stride l        Q (vectors of n x l) y[nv][nb] X
+ *   SCALE_INV       m   n nb                    X alpha[nb] Y
+ *   MASK_COLS           n nb                    X keep[nb]
+ *   EXTRACT_COLS        n nb off l              X out (n x l)
+ *   BEYN_ACCUM          d nb l nsys npow lA c0  X w[nsys] z[nsys] A[npow][lA][d]    (lA = 0: l)
+ *   GEMV_MULTI          d 1 k stride T          V (k single vectors) G[k][T] X (d x T)
+ *   PT_GEMM_BATCH       d nb k stride T         V G[k][T][nb] U (d x T x nb)
+ *   PT_AXPBY_COLS       d nb                    coef[2][nb] x y out
+ *   PT_PROJECT          d nb nd                 vk v0 dots[nd][nb]
+ *   DENSE           m   n nb nsys nplanes op cps   planes[nplanes][n][n] pc[nsys][nplanes] Ainv[nsys][n][n] X? Y?   (n <= 2048; the mask
+ *                                               is the apply's; pc conjugated by the caller for op = C, as the solver passes it) */
+enum {
+    WAE_VEC_DOTS = 0, WAE_VEC_NORMS, WAE_VEC_DOTS_MULTI, WAE_VEC_AXPY_NEG, WAE_VEC_LINCOMB, WAE_VEC_LINCOMB_ADD, WAE_VEC_AXPY_NEG_NORM,
+    WAE_VEC_AXPY_NEG_MULTI, WAE_VEC_DOTS2, WAE_VEC_AXPY2, WAE_VEC_LINCOMB_REP, WAE_VEC_SCALE_INV, WAE_VEC_MASK_COLS, WAE_VEC_EXTRACT_COLS,
+    WAE_VEC_BEYN_ACCUM, WAE_VEC_GEMV_MULTI, WAE_VEC_PT_GEMM_BATCH, WAE_VEC_PT_AXPBY_COLS, WAE_VEC_PT_PROJECT, WAE_VEC_DENSE
+};
+int wae_debug_vec(int32_t device, int32_t op, const int64_t *sz, int32_t nsz, double *const *bufs, const int64_t *lens, int32_t nbuf,
+                  const uint8_t *cmask, const int32_t *perm, int32_t *status_out);
 
 #ifdef __cplusplus
 }

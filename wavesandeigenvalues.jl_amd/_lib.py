@@ -36,8 +36,13 @@ _lib = None
 EXPORTS = [
     "wae_last_error", "wae_device_count", "wae_version", "wae_family_create", "wae_family_create_opts", "wae_family_destroy",
     "wae_family_info", "wae_family_spmv_bytes", "wae_spmv_sum", "wae_spmv_sum_cols", "wae_spmv_sum_multi", "wae_solver_setup",
-    "wae_solve", "wae_solve_guess", "wae_beyn_moments", "wae_beyn_moments_mgpu", "wae_beyn_moments_rb", "wae_rb_export", "wae_rb_import", "wae_eig_residuals", "wae_arnoldi_shiftinvert", "wae_arnoldi_shiftinvert_batch", "wae_perturb", "wae_slot_write", "wae_slot_read", "wae_slot_axpby", "wae_slot_forms", "wae_arnoldi_shiftinvert_slots", "wae_arnoldi_ritz_to_slot", "wae_perturb_slots", "wae_perturb_batch", "wae_perturb_batch_slots", "wae_p1_assemble", "wae_p1_assemble_boundary", "wae_p1_assemble_flame", "wae_p1_info", "wae_p1_get", "wae_p1_free", "wae_p1_shape_sensitivity", "wae_p1_shape_sensitivity_flame", "wae_bench_spmv", "wae_bench_spmv_level", "wae_bench_triad", "wae_debug_spmv",
+    "wae_solve", "wae_solve_guess", "wae_beyn_moments", "wae_beyn_moments_mgpu", "wae_beyn_moments_rb", "wae_rb_export", "wae_rb_import", "wae_eig_residuals", "wae_arnoldi_shiftinvert", "wae_arnoldi_shiftinvert_batch", "wae_perturb", "wae_slot_write", "wae_slot_read", "wae_slot_axpby", "wae_slot_forms", "wae_arnoldi_shiftinvert_slots", "wae_arnoldi_ritz_to_slot", "wae_perturb_slots", "wae_perturb_batch", "wae_perturb_batch_slots", "wae_p1_assemble", "wae_p1_assemble_boundary", "wae_p1_assemble_flame", "wae_p1_info", "wae_p1_get", "wae_p1_free", "wae_p1_shape_sensitivity", "wae_p1_shape_sensitivity_flame", "wae_bench_spmv", "wae_bench_spmv_level", "wae_bench_triad", "wae_debug_spmv", "wae_debug_vec",
 ]
+
+# operation codes of wae_debug_vec (include/waehip.h WAE_VEC_*)
+(VEC_DOTS, VEC_NORMS, VEC_DOTS_MULTI, VEC_AXPY_NEG, VEC_LINCOMB, VEC_LINCOMB_ADD, VEC_AXPY_NEG_NORM, VEC_AXPY_NEG_MULTI, VEC_DOTS2, VEC_AXPY2,
+ VEC_LINCOMB_REP, VEC_SCALE_INV, VEC_MASK_COLS, VEC_EXTRACT_COLS, VEC_BEYN_ACCUM, VEC_GEMV_MULTI, VEC_PT_GEMM_BATCH, VEC_PT_AXPBY_COLS,
+ VEC_PT_PROJECT, VEC_DENSE) = range(20)
 
 
 def lib():
@@ -118,6 +123,8 @@ def lib():
     L.wae_bench_spmv_level.argtypes = [C.c_void_p, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(C.c_int64)]
     L.wae_debug_spmv.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, C.c_double,
                                  C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.wae_debug_vec.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.c_int32,
+                                C.POINTER(C.c_uint8), ip, ip]
     _lib = L
     return L
 
@@ -138,3 +145,25 @@ def device_count():
     n = C.c_int(0)
     check(lib().wae_device_count(C.byref(n)))
     return n.value
+
+
+def debug_vec(op, sizes, bufs, cmask=None, perm=None, device=0, raise_on_error=True):
+    """wae_debug_vec (test hook, the family-free companion of DeviceFamily.debug_spmv): ONE launch of a streaming / reduction kernel
+    on host arrays.  ``bufs``: C-contiguous complex128 arrays in the order include/waehip.h lists (None = an optional argument left
+    out); every array is updated in place with what the device holds after the launch.  Returns (code, status word of the dense
+    inversion); with raise_on_error=False a negative code is returned instead of raised."""
+    for a in bufs:
+        assert a is None or (a.dtype == np.complex128 and a.flags.c_contiguous and a.flags.writeable)
+    sz = (C.c_int64 * len(sizes))(*[int(s) for s in sizes])
+    dp = C.POINTER(C.c_double)
+    ptrs = (dp * len(bufs))(*[None if a is None else zptr(a) for a in bufs])
+    lens = (C.c_int64 * len(bufs))(*[0 if a is None else a.size for a in bufs])
+    nb = int(sizes[1])
+    cm = None if cmask is None else (C.c_uint8 * ((nb + 7) // 8))(*[1 if x else 0 for x in cmask])
+    pm = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+    status = C.c_int32(0)
+    code = lib().wae_debug_vec(device, op, sz, len(sizes), ptrs, lens, len(bufs), cm,
+                               None if pm is None else pm.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(status))
+    if raise_on_error:
+        check(code)
+    return code, status.value

@@ -1655,7 +1655,8 @@ void launch_dense_assemble(const cplx *planes, int nplanes, int n, const cplx *p
 }
 
 // In-place Gauss-Jordan inversion with partial pivoting, one 1024-thread workgroup per system (matrix in
-// global memory / L2; pivot column and row staged in LDS).  n <= 2048.
+// global memory / L2; pivot column and row staged in LDS: 36 n bytes of dynamic LDS beside 12 KB of static).  n <= 2048, which
+// the launcher makes launchable by raising the kernel's dynamic-LDS limit (the default of 64 KB ends near n = 1 478).
 __global__ __launch_bounds__(1024) void dense_invert_kernel(cplx *__restrict__ Aall, int n, int *__restrict__ status) {
     extern __shared__ unsigned char smraw[];
     cplx *colk = (cplx *)smraw;            // n
@@ -1744,6 +1745,18 @@ void launch_dense_invert(cplx *Ainv, int n, int nsys, int *status, hipStream_t s
     if (n <= 0 || nsys <= 0) return;
     if (n > 2048) throw WaeError(WAE_ERR_INVALID, "dense coarse level too large (n > 2048)");
     size_t shm = (size_t)n * (2 * sizeof(cplx) + sizeof(int));
+    if (shm > 48 * 1024) {                          // (as launch_axpy2_norm: once per device)
+        static std::mutex mu;
+        static bool attr_done[64] = {false};
+        int dev_now = 0;
+        HIP_CHECK(hipGetDevice(&dev_now));
+        std::lock_guard<std::mutex> lock(mu);
+        if (!attr_done[dev_now & 63]) {
+            HIP_CHECK(hipFuncSetAttribute((const void *)dense_invert_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          2048 * (2 * sizeof(cplx) + sizeof(int))));
+            attr_done[dev_now & 63] = true;
+        }
+    }
     hipLaunchKernelGGL(dense_invert_kernel, dim3(nsys), dim3(1024), shm, st, Ainv, n, status);
     HIP_CHECK(hipGetLastError());
 }
