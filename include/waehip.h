@@ -257,6 +257,11 @@ int wae_arnoldi_shiftinvert_batch(wae_family *h, int32_t nsys, const double *coe
  *   norm_mode   0: perturb (no `c` normalisation)  1: perturb_disk  2: perturb_norm with Y = sum cY_k A_k;
  *               +16: eigenvalue series only (skip the solve at order N; what householder/mslp need, Householder.jl:115-116)
  * Outputs lambda_out[N+1] (entry 0 untouched, the wrappers overwrite it: LinOpFam.jl:555), v_out d x (N+1).
+ * wae_perturb and wae_perturb_slots are the nsys = 1 form of wae_perturb_batch (below): one recurrence in the library serves all four.
+ * What the single-pair calls keep of their own: with norm_mode + 16 they still return v_0 .. v_{N-1} in v_out (column N is not written:
+ * it keeps what the caller passed; at N = 0, v_0 is written), and their work space stays in the family between calls.  If the
+ * normalisation of the pair or an eigenvalue coefficient is not finite the call returns WAE_ERR_NAN (lambda_out holds the coefficients
+ * found before that, zeros after); otherwise WAE_OK, or WAE_WARN_MAXITER / WAE_WARN_STAGNATION if an inner solve ended above tol.
  */
 int wae_perturb(wae_family *h, const double *coeff_table, int32_t N, const double *v0, const double *v0adj,
                 int32_t norm_mode, const double *coeffsY, double tol, int32_t maxit, double *lambda_out,
@@ -304,13 +309,13 @@ int wae_perturb_slots(wae_family *h, const double *coeff_table, int32_t N, int32
                       wae_solve_info *info);
 
 /* -- batched adjoint perturbation -----------------------------------------------------------------------------------
- * The recurrence of wae_perturb (perturbation.jl:319-367,374-444,487-560; the wrappers LinOpFam.jl:546-618) for nsys eigenpairs in
+ * The recurrence behind wae_perturb (perturbation.jl:319-367,374-444,487-560; the wrappers LinOpFam.jl:546-618) for nsys eigenpairs in
  * lock-step: what a user does with the handful of modes a Beyn solve returned (expand each of them in tau, n, ...).  Every system has
  * its own base eigenvalue and parameter point -- its own coefficient table --, its own right and left vector; per order the library
  * runs ONE tall-skinny product, ONE multi-input operator product and ONE lock-step solve with nsys coefficient sets for the whole
  * batch, where nsys calls of wae_perturb run nsys one-column solves one after another.
- *   nsys          1 .. the solver batch width (opts[6] of wae_solver_setup); anything else: WAE_ERR_INVALID.  nsys = 1 computes what
- *                 wae_perturb computes.
+ *   nsys          1 .. the solver batch width (opts[6] of wae_solver_setup); anything else: WAE_ERR_INVALID.  nsys = 1 is what
+ *                 wae_perturb runs.
  *   coeff_tables  nsys tables, each laid out as wae_perturb's coeff_table, one after the other
  *   v0, v0adj     d x nsys column-major, host   (wae_perturb_batch)
  *   v_slot, v_cols, vadj_slot, vadj_cols   the same vectors as nsys slot columns each   (wae_perturb_batch_slots)
@@ -447,7 +452,6 @@ int wae_debug_spmv(wae_family *h, int32_t which, int32_t level, int32_t mode, co
  *   MASK_COLS           n nb                    X keep[nb]
  *   EXTRACT_COLS        n nb off l              X out (n x l)
  *   BEYN_ACCUM          d nb l nsys npow lA c0  X w[nsys] z[nsys] A[npow][lA][d]    (lA = 0: l)
- *   GEMV_MULTI          d 1 k stride T          V (k single vectors) G[k][T] X (d x T)
  *   PT_GEMM_BATCH       d nb k stride T         V G[k][T][nb] U (d x T x nb)
  *   PT_AXPBY_COLS       d nb                    coef[2][nb] x y out
  *   PT_PROJECT          d nb nd                 vk v0 dots[nd][nb]
@@ -456,7 +460,7 @@ int wae_debug_spmv(wae_family *h, int32_t which, int32_t level, int32_t mode, co
 enum {
     WAE_VEC_DOTS = 0, WAE_VEC_NORMS, WAE_VEC_DOTS_MULTI, WAE_VEC_AXPY_NEG, WAE_VEC_LINCOMB, WAE_VEC_LINCOMB_ADD, WAE_VEC_AXPY_NEG_NORM,
     WAE_VEC_AXPY_NEG_MULTI, WAE_VEC_DOTS2, WAE_VEC_AXPY2, WAE_VEC_LINCOMB_REP, WAE_VEC_SCALE_INV, WAE_VEC_MASK_COLS, WAE_VEC_EXTRACT_COLS,
-    WAE_VEC_BEYN_ACCUM, WAE_VEC_GEMV_MULTI, WAE_VEC_PT_GEMM_BATCH, WAE_VEC_PT_AXPBY_COLS, WAE_VEC_PT_PROJECT, WAE_VEC_DENSE
+    WAE_VEC_BEYN_ACCUM, WAE_VEC_PT_GEMM_BATCH, WAE_VEC_PT_AXPBY_COLS, WAE_VEC_PT_PROJECT, WAE_VEC_DENSE
 };
 int wae_debug_vec(int32_t device, int32_t op, const int64_t *sz, int32_t nsz, double *const *bufs, const int64_t *lens, int32_t nbuf,
                   const uint8_t *cmask, const int32_t *perm, int32_t *status_out);

@@ -369,8 +369,10 @@ function eigs(A::Operator, M::Operator; nev::Int=1, v0=nothing, tol::Float64=1e-
     return last[1], last[2], gap
 end
 
-"λ_k, v_k of `perturb` / `perturb_disk` / `perturb_norm` (perturbation.jl:319-367,374-444,487-560) as ONE device call (wae_perturb).
-norm_mode 0/1/2 as in include/waehip.h (+16: eigenvalue series only)."
+"λ_k, v_k of `perturb` / `perturb_disk` / `perturb_norm` (perturbation.jl:319-367,374-444,487-560) as ONE device call (wae_perturb: the
+library's one recurrence, that of wae_perturb_batch, for a single pair).  norm_mode 0/1/2 as in include/waehip.h (+16: eigenvalue series
+only; v_0 .. v_{N-1} are still returned, column N keeps its zeros).  A pair whose normalisation or coefficients are not finite throws
+(WAE_ERR_NAN)."
 function perturb_device(fam::DeviceFamily, N::Int, v0::Vector{ComplexF64}, v0Adj::Vector{ComplexF64}, norm_mode::Int; cY=nothing, quiet::Bool=false)
     ensure_solver!(fam)
     L = fam.L; T = length(L.terms); d = length(v0)

@@ -92,12 +92,6 @@ def pt_gemm(V, G):
     return out, mag
 
 
-def gemv_multi(V, G):
-    """X[row][t] = sum_i G[i][t] V_i[row];  V: (k, d), G: (k, T)"""
-    out, mag = pt_gemm(V[:, :, None], G[:, :, None])
-    return out[:, :, 0], mag[:, :, 0]
-
-
 def axpby_cols(coef, x, y):
     """a[b] x + c[b] y per column, a column with a = c = 0 is exact zero;  coef: (2, nb)"""
     a, c = coef[0].astype(LD)[None, :], coef[1].astype(LD)[None, :]

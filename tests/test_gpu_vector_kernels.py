@@ -488,11 +488,12 @@ def test_beyn_accum(nb, l, nsys):
         check_beyn(rng, 2 * 4096 * tr + tr + 1, nb, l, nsys, 2, False, True)
 
 
-def check_pt_gemm(rng, d, nb, k, T, nan_col=None):
+def check_pt_gemm(rng, d, nb, k, T, nan_col=None, stride_pad=0):
     C = Cols(nb, None, nan_col)
-    V, G, U = R.rand(rng, k, d, nb), R.rand(rng, k, T, nb), R.sentinel(d, T, nb)
+    Vs, G, U = R.rand(rng, k, d * nb + stride_pad), R.rand(rng, k, T, nb), R.sentinel(d, T, nb)
+    V = Vs[:, :d * nb].reshape(k, d, nb)
     C.poison(V, G)
-    call(_lib.VEC_PT_GEMM_BATCH, [d, nb, k, d * nb, T], [V, G, U])
+    call(_lib.VEC_PT_GEMM_BATCH, [d, nb, k, d * nb + stride_pad, T], [Vs, G, U])
     ref, mag = R.pt_gemm(V, G)
     assert_close(U, ref, upd_tol(mag, k), C.ok, f"pt_gemm_batch d={d} nb={nb} k={k} T={T}")
 
@@ -511,25 +512,16 @@ def test_pt_gemm_batch(nb):
     if nb == 64:
         check_pt_gemm(rng, 9, nb, 7, 16)                    # 1024 weights per vector: three vectors per launch
         check_pt_gemm(rng, capped(nb, 2048), nb, 3, 2)
-    if nb == 1:
+    if nb == 1:                                             # one column: the shape of the single-pair calls wae_perturb / wae_perturb_slots
         check_pt_gemm(rng, capped(nb, 2048), nb, 2, 2)
-
-
-def test_gemv_multi():
-    rng = np.random.default_rng(12)
-    for d in (1, 255, 257, 9477):
-        for k in (1, 31):
-            for T in (1, 5):
-                stride = d + 3
-                Vs, G, X = R.rand(rng, k, stride), R.rand(rng, k, T), R.sentinel(d, T)
-                call(_lib.VEC_GEMV_MULTI, [d, 1, k, stride, T], [Vs, G, X])
-                ref, mag = R.gemv_multi(Vs[:, :d], G)
-                assert_close(X, ref, upd_tol(mag, k), np.ones(T, dtype=bool), f"gemv_multi d={d} k={k} T={T}")
-    d, k, T = 2 * 4096 * 256 // 5 + 11, 2, 5                 # past the grid cap of 4096 workgroups
-    V, G, X = R.rand(rng, k, d), R.rand(rng, k, T), R.sentinel(d, T)
-    call(_lib.VEC_GEMV_MULTI, [d, 1, k, d, T], [V, G, X])
-    ref, mag = R.gemv_multi(V, G)
-    assert_close(X, ref, upd_tol(mag, k), np.ones(T, dtype=bool), "gemv_multi past the grid cap")
+        check_pt_gemm(rng, capped(nb, 2048), nb, 2, 5)
+        check_pt_gemm(rng, 257, nb, 192, 16)                # 3072 weights per launch: k = 192 fits at T = 16, k = 193 takes a second launch
+        check_pt_gemm(rng, 257, nb, 193, 16)
+        check_pt_gemm(rng, 257, nb, 193, 17)
+        for d in (1, 255, 257, 9477):                       # a series whose vectors lie further apart than their length
+            for k in (1, 31):
+                for T in (1, 5):
+                    check_pt_gemm(rng, d, nb, k, T, stride_pad=3)
 
 
 def check_pt_axpby(rng, d, nb, nan_col=None, dead=()):

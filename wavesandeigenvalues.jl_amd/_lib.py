@@ -41,8 +41,8 @@ EXPORTS = [
 
 # operation codes of wae_debug_vec (include/waehip.h WAE_VEC_*)
 (VEC_DOTS, VEC_NORMS, VEC_DOTS_MULTI, VEC_AXPY_NEG, VEC_LINCOMB, VEC_LINCOMB_ADD, VEC_AXPY_NEG_NORM, VEC_AXPY_NEG_MULTI, VEC_DOTS2, VEC_AXPY2,
- VEC_LINCOMB_REP, VEC_SCALE_INV, VEC_MASK_COLS, VEC_EXTRACT_COLS, VEC_BEYN_ACCUM, VEC_GEMV_MULTI, VEC_PT_GEMM_BATCH, VEC_PT_AXPBY_COLS,
- VEC_PT_PROJECT, VEC_DENSE) = range(20)
+ VEC_LINCOMB_REP, VEC_SCALE_INV, VEC_MASK_COLS, VEC_EXTRACT_COLS, VEC_BEYN_ACCUM, VEC_PT_GEMM_BATCH, VEC_PT_AXPBY_COLS,
+ VEC_PT_PROJECT, VEC_DENSE) = range(19)
 
 
 def lib():

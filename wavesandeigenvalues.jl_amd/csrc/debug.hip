@@ -137,12 +137,6 @@ extern "C" int wae_debug_vec(int32_t device, int32_t op, const int64_t *sz, int3
                               (int)S(5), (int)c0, perm ? pm.p : nullptr);
             break;
         }
-        case WAE_VEC_GEMV_MULTI: {                // sz: d, 1, k, stride, T   bufs: V (k single vectors), G[k][T], X (d x T)
-            const int k = count_of(2), T = count_of(4);
-            WAE_REQUIRE(k >= 1 && T >= 1, "k >= 1, T >= 1");
-            launch_gemv_multi(need(0, span(k, S(3), n)), (size_t)S(3), k, need(1, (int64_t)k * T), need(2, n * T), n, T, st);
-            break;
-        }
         case WAE_VEC_PT_GEMM_BATCH: {             // sz: d, nb, k, stride, T   bufs: V, G[k][T][nb], U (d x T x nb)
             const int k = count_of(2), T = count_of(4);
             WAE_REQUIRE(k >= 1 && T >= 1, "k >= 1, T >= 1");

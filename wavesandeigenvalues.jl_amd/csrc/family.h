@@ -79,7 +79,8 @@ struct wae_family {
     // arn_EV: arn_cols vectors of arn_nsys systems each, interleaved [row][system], for wae_arnoldi_ritz_to_slot
     DevBuf<cplx> arn_EV, arn_t, arn_pcM, arn_hcol, arn_stage, arn_gdir;
     int arn_nsys = 0, arn_cols = 0;
-    DevBuf<cplx> pt_ws, pt_Gd, pt_pcd;   // work space of wae_perturb / wae_perturb_slots (kept between calls)
+    DevBuf<cplx> pt_ws;              // work space of wae_perturb / wae_perturb_slots (grow-only, kept between calls)
+    DevBuf<cplx> pt_Gd, pt_pcd;      // results and plane tables of wae_slot_forms
     cplx *h_pinned = nullptr;        // (restart+2)*NB
     cplx *h_pin_pair = nullptr;      // staging of the pair steps of the narrow batches (gmres)
     size_t h_pin_pair_n = 0;

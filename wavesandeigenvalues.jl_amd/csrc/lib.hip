@@ -1896,206 +1896,6 @@ int wae_arnoldi_shiftinvert(wae_family *h, const double *coeffsA, const double *
     return wae_arnoldi_shiftinvert_batch(h, 1, coeffsA, coeffsM, m, v0, op, tol, maxit, 0.0, H_out, V_out, info);
 }
 
-// wae_perturb (v0, v0adj, v_out in host memory) and wae_perturb_slots (v0d, v0adjd: device columns in the library's row numbering;
-// v_out may be null: eigenvalue series only)
-static int perturb_core(wae_family *h, const double *coeff_table, int32_t N, const double *v0, const double *v0adj, const cplx *v0d, const cplx *v0adjd,
-                        int32_t norm_mode_in, const double *coeffsY, double tol, int32_t maxit, double *lambda_out, double *v_out, wae_solve_info *info) {
-    {
-        const bool skip_last = (norm_mode_in & 16) != 0;    // eigenvalue series only: no solve at order N
-        const int norm_mode = norm_mode_in & 15;
-        WAE_REQUIRE(norm_mode >= 0 && norm_mode <= 2 && (norm_mode != 2 || coeffsY), "bad norm_mode");
-        require_solver(h);
-        HIP_CHECK(hipSetDevice(h->device));
-        hipStream_t st = h->stream;
-        wae_solve_info li;
-        memset(&li, 0, sizeof(li));
-        const double t0 = now_s();
-        const int64_t d = h->d;
-        const int T = h->T;
-        auto F = [&](int m, int n, int k) { return zc(coeff_table[((size_t)(m * (N + 1) + n) * T + k) * 2], coeff_table[((size_t)(m * (N + 1) + n) * T + k) * 2 + 1]); };
-        // (one allocation of the family, carved up and kept: twelve hipMalloc / hipFree pairs per call otherwise -- a Newton step of the
-        // Householder iteration calls this once per start value)
-        struct Span { cplx *p = nullptr; } PV, Ub, rb, rhs, u10, wl, tmp, tmp2, tmp3, sc;
-        ensure(h->pt_ws, (size_t)d * (N + 1) + (size_t)d * T + (size_t)7 * d + 8);
-        {
-            cplx *q = h->pt_ws.p;
-            PV.p = q; q += (size_t)d * (N + 1);
-            Ub.p = q; q += (size_t)d * T;
-            for (Span *sp : {&rb, &rhs, &u10, &wl, &tmp, &tmp2, &tmp3}) { sp->p = q; q += d; }
-            sc.p = q;
-        }
-        DevBuf<cplx> &Gd = h->pt_Gd, &pcd = h->pt_pcd;
-        ensure(Gd, (size_t)(N + 1) * T + 4);
-        const OpDev A0 = h->ops[0].dev(WAE_OP_N);
-        cplx hs[4];
-        auto plane_tab = [&](const double *coeffs, int op) {     // level-0 plane table for an spmv
-            std::vector<zc> pc;
-            plane_coeffs(h, coeffs, op, pc);
-            std::vector<cplx> tab(h->nplanes);
-            for (int q = 0; q < h->nplanes; ++q) { const zc c = pc[h->slot_plane[0][q]]; tab[q] = cplx{c.real(), c.imag()}; }
-            pcd.upload(tab.data(), tab.size(), st);
-            HIP_CHECK(hipStreamSynchronize(st));
-        };
-        auto apply = [&](const double *coeffs, int op, const cplx *x, cplx *y) {
-            plane_tab(coeffs, op);
-            launch_spmv(h->ops[0].dev(op), pcd.p, 1 << 30, x, y, nullptr, 0.0, 1, MODE_AX, st);
-            HIP_CHECK(hipStreamSynchronize(st));
-        };
-        auto dot = [&](const cplx *a, const cplx *b) -> zc {      // a^H b
-            launch_dots(a, 0, 1, b, d, 1, h->partial.p, sc.p, st);
-            HIP_CHECK(hipMemcpyAsync(hs, sc.p, sizeof(cplx), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            return zc(hs[0].x, hs[0].y);
-        };
-        auto axpby = [&](zc a, const cplx *x, zc b, const cplx *y, cplx *out) {   // out = a x + b y (out may alias x or y)
-            cplx co[2] = {cplx{a.real(), a.imag()}, cplx{b.real(), b.imag()}};
-            Gd.upload(co, 2, st);
-            launch_lincomb(x, 0, 1, Gd.p, tmp2.p, d, 1, st);            // tmp2 = a x
-            launch_lincomb(y, 0, 1, Gd.p + 1, tmp3.p, d, 1, st);        // tmp3 = b y
-            launch_add(tmp2.p, tmp3.p, (size_t)d, st);
-            launch_copy(tmp3.p, out, (size_t)d, st);
-            HIP_CHECK(hipStreamSynchronize(st));
-        };
-        auto ipY = [&](const cplx *a, const cplx *b) -> zc {      // a^H Y b  (mode 2) or a^H b
-            if (norm_mode != 2) return dot(a, b);
-            apply(coeffsY, WAE_OP_N, b, tmp.p);
-            return dot(a, tmp.p);
-        };
-        std::vector<double> c00(2 * T), c10(2 * T);
-        for (int k = 0; k < T; ++k) {
-            const zc a = F(0, 0, k), b = N >= 1 ? F(1, 0, k) : zc(0);
-            c00[2 * k] = a.real(); c00[2 * k + 1] = a.imag();
-            c10[2 * k] = b.real(); c10[2 * k + 1] = b.imag();
-        }
-        // v[0] = v0 / sqrt(ip(v0,v0))
-        cplx *V0 = PV.p;
-        if (v0d) {
-            launch_copy(v0d, V0, (size_t)d, st);
-            launch_copy(v0adjd, wl.p, (size_t)d, st);
-        } else {
-            ensure(h->io_a, (size_t)2 * d);                               // caller's row numbering -> the library's
-            HIP_CHECK(hipMemcpyAsync(h->io_a.p, v0, (size_t)d * sizeof(cplx), hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(h->io_a.p + d, v0adj, (size_t)d * sizeof(cplx), hipMemcpyHostToDevice, st));
-            launch_colmajor_to_inter(h->io_a.p, d, 1, V0, 1, st, h->perm());
-            launch_colmajor_to_inter(h->io_a.p + d, d, 1, wl.p, 1, st, h->perm());
-        }
-        {
-            const zc nn = ipY(V0, V0);
-            axpby(1.0 / std::sqrt(nn), V0, 0.0, V0, V0);
-        }
-        std::vector<zc> lam(N + 1, zc(0));
-        if (N >= 1) {
-            apply(c10.data(), WAE_OP_N, V0, u10.p);                                  // u10 = L(1,0) v0
-            Batch bt;
-            bt.nb = 1; bt.cps = 1; bt.nsys = 1; bt.op = WAE_OP_N;
-            std::vector<std::vector<zc>> pcs(1);
-            if (norm_mode == 2) {                                                    // perturbation.jl:493-494
-                plane_coeffs(h, coeffsY, WAE_OP_N, pcs[0]);
-                solve_chunk(h, bt, pcs, wl.p, tmp.p, tol, maxit, &li);               // v0Adj = Y \ v0Adj
-                apply(coeffsY, WAE_OP_N, u10.p, tmp2.p);
-                const zc sN = dot(tmp.p, tmp2.p);                                    // v0Adj' Y L10 v0
-                launch_copy(tmp.p, rb.p, (size_t)d, st);
-                axpby(1.0 / sN, rb.p, 0.0, rb.p, rb.p);                              // v0Adj /= s
-                apply(coeffsY, WAE_OP_C, rb.p, wl.p);                                // wl = Y' v0Adj
-            } else {
-                const zc sN = dot(wl.p, u10.p);                                      // v0Adj' L10 v0
-                axpby(1.0 / sN, wl.p, 0.0, wl.p, wl.p);
-            }
-            const zc denom = dot(wl.p, u10.p);
-            plane_coeffs(h, c00.data(), WAE_OP_N, pcs[0]);
-            bool l00_ready = false;      // set up lazily: order-1 Newton steps (skip_last) never solve with L(0,0), which is
-                                         // exactly singular for small dense families (the reference would throw there)
-            // plane passes for the multi-input SpMV (coefficient 1 per term: the weights live in G)
-            std::vector<std::vector<int>> plane_terms(h->nplanes);
-            for (int k = 0; k < T; ++k) plane_terms[h->term_plane[k]].push_back(k);
-            size_t npass = 0;
-            for (auto &v : plane_terms) npass = std::max(npass, v.size());
-            std::vector<zc> G;
-            for (int k = 1; k <= N; ++k) {
-                G.assign((size_t)k * T, zc(0));
-                auto addF = [&](int i, int m, int n, zc coeff) {
-                    for (int t = 0; t < T; ++t) G[(size_t)i * T + t] += coeff * F(m, n, t);
-                };
-                for (int n = 1; n <= k; ++n) addF(k - n, 0, n, 1.0);
-                for (int mw = 1; mw <= k; ++mw)
-                    for_each_partition(mw, [&](const int *p, int len) {
-                        if (len == 1 && p[0] == k) return;
-                        std::vector<int> mu(mw, 0);
-                        for (int i = 0; i < len; ++i) mu[p[i] - 1]++;
-                        double mn = std::tgamma((double)len + 1.0);
-                        zc coeff = 1.0;
-                        for (int g = 0; g < mw; ++g)
-                            if (mu[g]) {
-                                mn /= std::tgamma((double)mu[g] + 1.0);
-                                coeff *= std::pow(lam[g + 1], mu[g]);
-                            }
-                        coeff *= mn;
-                        for (int n = 0; n <= k - mw; ++n) {
-                            if (k == 1 && len == 1) continue;
-                            addF(k - n - mw, len, n, coeff);
-                        }
-                    });
-                std::vector<cplx> Gc((size_t)k * T);
-                for (size_t i = 0; i < Gc.size(); ++i) Gc[i] = cplx{G[i].real(), G[i].imag()};
-                Gd.upload(Gc.data(), Gc.size(), st);
-                launch_gemv_multi(PV.p, (size_t)d, k, Gd.p, Ub.p, d, T, st);
-                HIP_CHECK(hipStreamSynchronize(st));
-                launch_fill_zero(rb.p, (size_t)d, st);
-                std::vector<cplx> tab(h->nplanes);
-                std::vector<int> pcol(h->nplanes);
-                for (size_t ps = 0; ps < npass; ++ps) {
-                    for (int sidx = 0; sidx < h->nplanes; ++sidx) {
-                        const int q = h->slot_plane[0][sidx];
-                        if (ps < plane_terms[q].size()) {
-                            const int kk = plane_terms[q][ps];
-                            const zc c = h->term_scale[kk];
-                            tab[sidx] = cplx{c.real(), c.imag()};
-                            pcol[sidx] = kk;
-                        } else { tab[sidx] = cplx{0.0, 0.0}; pcol[sidx] = 0; }
-                    }
-                    pcd.upload(tab.data(), tab.size(), st);
-                    h->plane_col_dev.upload(pcol.data(), pcol.size(), st);
-                    launch_spmv_multi(A0, pcd.p, h->plane_col_dev.p, Ub.p, tmp.p, T, st);
-                    launch_add(tmp.p, rb.p, (size_t)d, st);
-                    HIP_CHECK(hipStreamSynchronize(st));
-                }
-                lam[k] = -dot(wl.p, rb.p) / denom;
-                if (skip_last && k == N) break;
-                axpby(-1.0, rb.p, -lam[k], u10.p, rhs.p);                             // rhs = -(r + lam_k L10 v0)
-                cplx *vk = PV.p + (size_t)k * d;
-                if (!l00_ready) { upload_pc(h, pcs); dense_setup(h, bt); l00_ready = true; }
-                gmres(h, bt, rhs.p, vk, tol, maxit, &li);
-                const zc pr = ipY(V0, vk);
-                axpby(1.0, vk, -pr, V0, vk);                                          // v_k -= (v0' [Y] v_k) v0
-                if (norm_mode >= 1) {
-                    zc c = 0;
-                    for (int l = 1; l < k; ++l) c -= 0.5 * ipY(PV.p + (size_t)l * d, PV.p + (size_t)(k - l) * d);
-                    axpby(1.0, vk, c, V0, vk);
-                }
-            }
-        }
-        if (v_out) {
-            ensure(h->io_b, (size_t)d * (N + 1));
-            for (int k = 0; k <= N; ++k) launch_inter_to_colmajor(PV.p + (size_t)k * d, 1, d, 1, h->io_b.p + (size_t)k * d, st, h->perm());
-            HIP_CHECK(hipMemcpyAsync(v_out, h->io_b.p, (size_t)d * (N + 1) * sizeof(cplx), hipMemcpyDeviceToHost, st));
-        }
-        HIP_CHECK(hipStreamSynchronize(st));
-        for (int k = 1; k <= N; ++k) { lambda_out[2 * k] = lam[k].real(); lambda_out[2 * k + 1] = lam[k].imag(); }
-        li.seconds = now_s() - t0;
-        const int rc_ = info_code(li);
-        if (info) *info = li;
-        return rc_;
-    }
-}
-
-int wae_perturb(wae_family *h, const double *coeff_table, int32_t N, const double *v0, const double *v0adj, int32_t norm_mode_in, const double *coeffsY,
-                double tol, int32_t maxit, double *lambda_out, double *v_out, wae_solve_info *info) {
-    return guarded([&]() {
-        WAE_REQUIRE(h && coeff_table && v0 && v0adj && lambda_out && v_out && N >= 0 && N <= 200, "bad argument");
-        return perturb_core(h, coeff_table, N, v0, v0adj, nullptr, nullptr, norm_mode_in, coeffsY, tol, maxit, lambda_out, v_out, info);
-    });
-}
-
 // ----------------------------------------------------------------------------------------------------
 // Device-resident multivectors ("slots").  The Newton-type solvers iterate on a handful of vectors per start value (right and left
 // eigenvector estimates, the Ritz vectors of the step): with the processes' inputs and outputs in host memory a Householder step of 8
@@ -2252,24 +2052,18 @@ int wae_arnoldi_ritz_to_slot(wae_family *h, int32_t nsys, int32_t ny, const doub
     });
 }
 
-int wae_perturb_slots(wae_family *h, const double *coeff_table, int32_t N, int32_t v_slot, int32_t v_col, int32_t vadj_slot, int32_t vadj_col,
-                      int32_t norm_mode_in, const double *coeffsY, double tol, int32_t maxit, double *lambda_out, double *v_out, wae_solve_info *info) {
-    return guarded([&]() {
-        WAE_REQUIRE(h && coeff_table && lambda_out && N >= 0 && N <= 200, "bad argument");
-        return perturb_core(h, coeff_table, N, nullptr, nullptr, slot_col(h, v_slot, v_col), slot_col(h, vadj_slot, vadj_col), norm_mode_in, coeffsY,
-                            tol, maxit, lambda_out, v_out, info);
-    });
-}
-
 // ----------------------------------------------------------------------------------------------------
-// Batched adjoint perturbation: wae_perturb_batch / wae_perturb_batch_slots.  The recurrence of perturb_core for nsys eigenpairs in
-// lock-step; every vector of the batch is an interleaved block [row][system] of leading dimension nb, the series is N+1 such blocks.
+// Adjoint perturbation: the one recurrence behind wae_perturb / wae_perturb_slots (nsys = 1) and wae_perturb_batch /
+// wae_perturb_batch_slots, for nsys eigenpairs in lock-step.  Every vector of the batch is an interleaved block [row][system] of
+// leading dimension nb, the series is N+1 such blocks.
 // Per order: the partition weights of every system on the host (they need lambda_1..k-1 of that system), ONE tall-skinny product, ONE
 // multi-input SpMV per plane pass, ONE inner product with the left vectors, ONE read-back of the nsys numerators -- the only host
 // synchronisation of an order outside the solve --, ONE fused right-hand side, ONE lock-step solve, the projection dots and ONE fused
-// projection update.  All work space is local to the call.
+// projection update.  All device work space is carved out of ONE buffer the entry point hands in: a buffer of its own, released on
+// return (the batched calls), or the family's grow-only pt_ws (the single-pair calls: a Newton step of the Householder iteration makes
+// one per start value, and a dozen hipMalloc / hipFree pairs per call showed up there).
 // ----------------------------------------------------------------------------------------------------
-// G[i*T + t] = weight of v_i in the input column of term t at order k (perturbation.jl:394-415 regrouped; the loop of perturb_core)
+// G[i*T + t] = weight of v_i in the input column of term t at order k (perturbation.jl:394-415 regrouped)
 static void perturb_weights(int k, int N, int T, const double *coeff_table, const std::vector<zc> &lam, std::vector<zc> &G) {
     auto F = [&](int m, int n, int t) { const size_t e = ((size_t)(m * (N + 1) + n) * T + t) * 2; return zc(coeff_table[e], coeff_table[e + 1]); };
     G.assign((size_t)k * T, zc(0));
@@ -2306,10 +2100,11 @@ static int perturb_batch_width(const wae_family *h, int nsys) {
     return (pad && nsys >= 2 && nsys < 8 && h->NB >= 8) ? 8 : nsys;
 }
 
-// v0c / v0adjc: d x nsys column-major on the DEVICE; in the caller's row numbering if `permuted` (host vectors), else the library's (slots)
+// v0c / v0adjc: d x nsys column-major on the DEVICE; in the caller's row numbering if `permuted` (host vectors), else the library's (slots).
+// nvec_out: v_0 .. v_{nvec_out-1} of every system go to v_out (if not null); ws: see above
 static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_tables, int32_t N, const cplx *v0c, const cplx *v0adjc, bool permuted,
-                              int32_t norm_mode_in, const double *coeffsY, double tol, int32_t maxit, double *lambda_out, double *v_out,
-                              int32_t *status_out, wae_solve_info *info) {
+                              int32_t norm_mode_in, const double *coeffsY, double tol, int32_t maxit, double *lambda_out, double *v_out, int nvec_out,
+                              int32_t *status_out, wae_solve_info *info, DevBuf<cplx> &ws) {
     const bool skip_last = (norm_mode_in & 16) != 0;
     const int norm_mode = norm_mode_in & 15;
     WAE_REQUIRE(norm_mode >= 0 && norm_mode <= 2 && (norm_mode != 2 || coeffsY), "bad norm_mode");
@@ -2323,22 +2118,32 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
     const size_t vec = (size_t)d * nb;
     const size_t tsz = (size_t)(N + 1) * (N + 1) * T * 2;         // doubles per coefficient table
     const int *perm = permuted ? h->perm() : nullptr;
-    DevBuf<cplx> PV, Ub, work, Gd, coef, dotsd, pc1, pcY, pcM;
-    DevBuf<int> pcolM;
-    PV.alloc(vec * (skip_last ? std::max(N, 1) : N + 1));         // (the eigenvalue series needs v_0..v_{N-1} only)
-    Ub.alloc(vec * T);
-    work.alloc(vec * 5);
-    cplx *rb = work.p, *rhs = rb + vec, *u10 = rhs + vec, *wl = u10 + vec, *tmp = wl + vec;
-    Gd.alloc((size_t)std::max(N, 1) * T * nb);
-    coef.alloc((size_t)2 * nb);
-    dotsd.alloc((size_t)(N + 2) * nb);
-    cplx *V0 = PV.p;
+    const int nser = skip_last ? std::max(N, 1) : N + 1;          // (the eigenvalue series needs v_0..v_{N-1} only)
+    WAE_REQUIRE(nvec_out >= 0 && nvec_out <= nser, "bad argument");
+    // plane passes of the multi-input SpMV (coefficient term_scale per term: the weights live in G), the same for every order
+    std::vector<std::vector<int>> plane_terms(npl);
+    for (int t = 0; t < T; ++t) plane_terms[h->term_plane[t]].push_back(t);
+    size_t npass = 0;
+    for (auto &v : plane_terms) npass = std::max(npass, v.size());
+    // the work space: series | T input columns | five vectors | weights | coefficients | dots | plane tables (L(1,0), Y, passes) | pass columns
+    const size_t sizes[] = {vec * nser, vec * T, vec * 5, (size_t)std::max(N, 1) * T * nb, (size_t)2 * nb, (size_t)(N + 2) * nb,
+                            (size_t)nb * npl, (size_t)nb * npl, npass * npl, (npass * npl * sizeof(int) + sizeof(cplx) - 1) / sizeof(cplx)};
+    size_t total = 0;
+    for (size_t n : sizes) total += n;
+    ensure(ws, total);
+    const size_t *next = sizes;
+    cplx *carve = ws.p;
+    auto take = [&]() { cplx *p = carve; carve += *next++; return p; };
+    cplx *PV = take(), *Ub = take(), *rb = take(), *Gd = take(), *coef = take(), *dotsd = take(), *pc1 = take(), *pcY = take(), *pcM = take();
+    int *pcolM = (int *)take();
+    cplx *rhs = rb + vec, *u10 = rhs + vec, *wl = u10 + vec, *tmp = wl + vec, *V0 = PV;
+    auto put = [&](auto *dst, const auto &src) { HIP_CHECK(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(src[0]), hipMemcpyHostToDevice, st)); };
     std::vector<cplx> hc((size_t)2 * nb), hd((size_t)nb), Gc;
     std::vector<unsigned char> dead(ns, 0);
     std::vector<int> status(ns, WAE_OK);
 
     // level-0 plane table of `n` coefficient rows (row i from coeffs(i)); rows n..nb-1 repeat row 0
-    auto plane_table = [&](DevBuf<cplx> &dst, int n, auto &&coeffs, int op) {
+    auto plane_table = [&](cplx *dst, int n, auto &&coeffs, int op) {
         std::vector<cplx> tab((size_t)nb * npl);
         std::vector<zc> pc;
         for (int i = 0; i < nb; ++i) {
@@ -2348,11 +2153,11 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
                 else tab[(size_t)i * npl + q] = tab[q];
             }
         }
-        dst.upload(tab.data(), tab.size(), st);
+        put(dst, tab);
         HIP_CHECK(hipStreamSynchronize(st));                        // (tab is a stack vector)
     };
     auto applyY = [&](int op, const cplx *x, cplx *y) {            // pcY holds the table of that op
-        launch_spmv(h->ops[0].dev(op), pcY.p, 1 << 30, x, y, nullptr, 0.0, nb, MODE_AX, st);
+        launch_spmv(h->ops[0].dev(op), pcY, 1 << 30, x, y, nullptr, 0.0, nb, MODE_AX, st);
     };
     auto dots_to = [&](const cplx *a, const cplx *b, cplx *out) { launch_dots(a, 0, 1, b, d, nb, h->partial.p, out, st); };   // out[s] = a_s^H b_s
     auto ipY_to = [&](const cplx *a, const cplx *b, cplx *out) {   // a^H Y b (mode 2) or a^H b
@@ -2371,8 +2176,8 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
             hc[s] = on ? cplx{a[s].real(), a[s].imag()} : cplx{0.0, 0.0};
             hc[nb + s] = (on && c) ? cplx{(*c)[s].real(), (*c)[s].imag()} : cplx{0.0, 0.0};
         }
-        coef.upload(hc.data(), hc.size(), st);
-        launch_pt_axpby_cols(coef.p, x, y ? y : x, out, d, nb, st);
+        put(coef, hc);
+        launch_pt_axpby_cols(coef, x, y ? y : x, out, d, nb, st);
     };
     auto give_up = [&](int s, int code) { dead[s] = 1; status[s] = code; };
     auto finite = [](zc z) { return std::isfinite(z.real()) && std::isfinite(z.imag()); };
@@ -2382,8 +2187,8 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
     if (norm_mode == 2) plane_table(pcY, 1, [&](int) { return coeffsY; }, WAE_OP_N);
     std::vector<zc> fac(ns), fac2(ns);
     {                                                               // v0 /= sqrt(ip(v0, v0))
-        ipY_to(V0, V0, dotsd.p);
-        read_dots(dotsd.p);
+        ipY_to(V0, V0, dotsd);
+        read_dots(dotsd);
         for (int s = 0; s < ns; ++s) {
             fac[s] = 1.0 / std::sqrt(zc(hd[s].x, hd[s].y));
             if (!finite(fac[s])) give_up(s, WAE_ERR_NAN);
@@ -2394,7 +2199,7 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
     std::vector<int> order_iters;
     if (N >= 1) {
         plane_table(pc1, ns, [&](int s) { return coeff_tables + (size_t)s * tsz + (size_t)(1 * (N + 1) + 0) * T * 2; }, WAE_OP_N);
-        launch_spmv(h->ops[0].dev(WAE_OP_N), pc1.p, 1, V0, u10, nullptr, 0.0, nb, MODE_AX, st);          // u10_s = L_s(1,0) v0_s
+        launch_spmv(h->ops[0].dev(WAE_OP_N), pc1, 1, V0, u10, nullptr, 0.0, nb, MODE_AX, st);          // u10_s = L_s(1,0) v0_s
         Batch bt;
         bt.nb = nb; bt.op = WAE_OP_N;
         if (norm_mode == 2) {                                       // perturbation.jl:493-494
@@ -2403,33 +2208,29 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
             plane_coeffs(h, coeffsY, WAE_OP_N, pcs[0]);
             solve_chunk(h, bt, pcs, wl, tmp, tol, maxit, &li);      // v0Adj = Y \ v0Adj
             applyY(WAE_OP_N, u10, rhs);
-            dots_to(tmp, rhs, dotsd.p);                             // v0Adj' Y L10 v0
-            read_dots(dotsd.p);
+            dots_to(tmp, rhs, dotsd);                             // v0Adj' Y L10 v0
+            read_dots(dotsd);
             for (int s = 0; s < ns; ++s) { fac[s] = 1.0 / zc(hd[s].x, hd[s].y); if (!finite(fac[s])) give_up(s, WAE_ERR_NAN); }
             scale_cols(fac, tmp, nullptr, nullptr, rb);             // v0Adj /= s
             plane_table(pcY, 1, [&](int) { return coeffsY; }, WAE_OP_C);
             applyY(WAE_OP_C, rb, wl);                               // wl = Y' v0Adj
             plane_table(pcY, 1, [&](int) { return coeffsY; }, WAE_OP_N);
         } else {
-            dots_to(wl, u10, dotsd.p);                              // v0Adj' L10 v0
-            read_dots(dotsd.p);
+            dots_to(wl, u10, dotsd);                              // v0Adj' L10 v0
+            read_dots(dotsd);
             for (int s = 0; s < ns; ++s) { fac[s] = 1.0 / zc(hd[s].x, hd[s].y); if (!finite(fac[s])) give_up(s, WAE_ERR_NAN); }
             scale_cols(fac, wl, nullptr, nullptr, wl);
         }
-        dots_to(wl, u10, dotsd.p);
-        read_dots(dotsd.p);
+        dots_to(wl, u10, dotsd);
+        read_dots(dotsd);
         std::vector<zc> denom(ns);
         for (int s = 0; s < ns; ++s) denom[s] = zc(hd[s].x, hd[s].y);
         // the solves: one coefficient set L_s(0,0) per column
         bt.cps = 1; bt.nsys = nb;
         std::vector<std::vector<zc>> pcs(nb);
         for (int s = 0; s < nb; ++s) plane_coeffs(h, coeff_tables + (size_t)(s < ns ? s : 0) * tsz, WAE_OP_N, pcs[s]);
-        bool l00_ready = false;                                     // (as in perturb_core: an order-1 eigenvalue series never solves)
-        // plane passes of the multi-input SpMV (coefficient term_scale per term: the weights live in G), the same for every order
-        std::vector<std::vector<int>> plane_terms(npl);
-        for (int t = 0; t < T; ++t) plane_terms[h->term_plane[t]].push_back(t);
-        size_t npass = 0;
-        for (auto &v : plane_terms) npass = std::max(npass, v.size());
+        bool l00_ready = false;      // set up lazily: order-1 Newton steps (skip_last) never solve with L(0,0), which is exactly
+                                     // singular for small dense families (the reference would throw there)
         {
             std::vector<cplx> tab(npass * npl);
             std::vector<int> pcol(npass * npl);
@@ -2443,8 +2244,8 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
                         pcol[ps * npl + sidx] = t;
                     } else { tab[ps * npl + sidx] = cplx{0.0, 0.0}; pcol[ps * npl + sidx] = 0; }
                 }
-            pcM.upload(tab.data(), tab.size(), st);
-            pcolM.upload(pcol.data(), pcol.size(), st);
+            put(pcM, tab);
+            put(pcolM, pcol);
             HIP_CHECK(hipStreamSynchronize(st));
         }
         const OpDev A0 = h->ops[0].dev(WAE_OP_N);
@@ -2457,12 +2258,12 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
                 perturb_weights(k, N, T, coeff_tables + (size_t)s * tsz, lam[s], G);
                 for (size_t e = 0; e < (size_t)k * T; ++e) Gc[e * nb + s] = cplx{G[e].real(), G[e].imag()};
             }
-            Gd.upload(Gc.data(), Gc.size(), st);                    // (complete before this order's read-back returns)
-            launch_pt_gemm_batch(PV.p, vec, k, Gd.p, Ub.p, d, T, nb, st);
+            put(Gd, Gc);                                            // (complete before this order's read-back returns)
+            launch_pt_gemm_batch(PV, vec, k, Gd, Ub, d, T, nb, st);
             for (size_t ps = 0; ps < npass; ++ps)
-                launch_pt_spmv_batch(A0, pcM.p + ps * npl, pcolM.p + ps * npl, Ub.p, T, rb, nb, ps > 0, st);
-            dots_to(wl, rb, dotsd.p);
-            read_dots(dotsd.p);                                     // the order's one read-back: lambda_k of every system
+                launch_pt_spmv_batch(A0, pcM + ps * npl, pcolM + ps * npl, Ub, T, rb, nb, ps > 0, st);
+            dots_to(wl, rb, dotsd);
+            read_dots(dotsd);                                     // the order's one read-back: lambda_k of every system
             for (int s = 0; s < ns; ++s) {
                 if (dead[s]) continue;
                 lam[s][k] = -zc(hd[s].x, hd[s].y) / denom[s];
@@ -2471,23 +2272,23 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
             }
             if (skip_last && k == N) break;
             scale_cols(minus_one, rb, &mlam, u10, rhs);             // rhs = -(r + lam_k L10 v0)
-            cplx *vk = PV.p + (size_t)k * vec;
+            cplx *vk = PV + (size_t)k * vec;
             if (!l00_ready) { upload_pc(h, pcs); dense_setup(h, bt); l00_ready = true; }
             order_iters.push_back(gmres(h, bt, rhs, vk, tol, maxit, &li, nullptr, false, rr.data()));
             for (int s = 0; s < ns; ++s)
                 if (!dead[s] && !(rr[s] <= tol) && status[s] == WAE_OK) status[s] = WAE_WARN_MAXITER;
-            ipY_to(V0, vk, dotsd.p);                                // v0' [Y] v_k
+            ipY_to(V0, vk, dotsd);                                // v0' [Y] v_k
             int nd = 1;
             if (norm_mode >= 1)
-                for (int l = 1; l < k; ++l, ++nd) ipY_to(PV.p + (size_t)l * vec, PV.p + (size_t)(k - l) * vec, dotsd.p + (size_t)nd * nb);
-            launch_pt_project(vk, V0, dotsd.p, nd, d, nb, st);      // v_k -= (v0' [Y] v_k) v0;  v_k += c v0
+                for (int l = 1; l < k; ++l, ++nd) ipY_to(PV + (size_t)l * vec, PV + (size_t)(k - l) * vec, dotsd + (size_t)nd * nb);
+            launch_pt_project(vk, V0, dotsd, nd, d, nb, st);      // v_k -= (v0' [Y] v_k) v0;  v_k += c v0
         }
     }
-    if (v_out && !skip_last) {                                      // nsys blocks of d x (N+1), the caller's row numbering
-        for (int k = 0; k <= N; ++k) {
-            launch_inter_to_colmajor(PV.p + (size_t)k * vec, nb, d, ns, Ub.p, st, h->perm());
+    if (v_out) {                                                    // nsys blocks of d x (N+1), the caller's row numbering
+        for (int k = 0; k < nvec_out; ++k) {
+            launch_inter_to_colmajor(PV + (size_t)k * vec, nb, d, ns, Ub, st, h->perm());
             for (int s = 0; s < ns; ++s)
-                HIP_CHECK(hipMemcpyAsync(v_out + ((size_t)s * (N + 1) + k) * d * 2, Ub.p + (size_t)s * d, (size_t)d * sizeof(cplx), hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipMemcpyAsync(v_out + ((size_t)s * (N + 1) + k) * d * 2, Ub + (size_t)s * d, (size_t)d * sizeof(cplx), hipMemcpyDeviceToHost, st));
         }
     }
     HIP_CHECK(hipStreamSynchronize(st));
@@ -2513,6 +2314,40 @@ static void perturb_batch_check(wae_family *h, int32_t nsys, const double *coeff
     HIP_CHECK(hipSetDevice(h->device));
 }
 
+// the single-pair calls: one system, the family's work space, v_0..v_{N-1} also with norm_mode + 16 (no solve at order N); a system
+// the recurrence gave up is an error of the call
+static int perturb_single(wae_family *h, const double *coeff_table, int32_t N, const cplx *v0c, const cplx *v0adjc, bool permuted, int32_t norm_mode,
+                          const double *coeffsY, double tol, int32_t maxit, double *lambda_out, double *v_out, wae_solve_info *info) {
+    int32_t status = WAE_OK;
+    const int rc = perturb_batch_core(h, 1, coeff_table, N, v0c, v0adjc, permuted, norm_mode, coeffsY, tol, maxit, lambda_out, v_out,
+                                      (norm_mode & 16) ? std::max(N, 1) : N + 1, &status, info, h->pt_ws);
+    if (status == WAE_ERR_NAN) throw WaeError(WAE_ERR_NAN, "perturbation: a normalisation or an eigenvalue coefficient is not finite");
+    return rc;
+}
+
+int wae_perturb(wae_family *h, const double *coeff_table, int32_t N, const double *v0, const double *v0adj, int32_t norm_mode, const double *coeffsY,
+                double tol, int32_t maxit, double *lambda_out, double *v_out, wae_solve_info *info) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && coeff_table && v0 && v0adj && lambda_out && v_out && N >= 0 && N <= 200, "bad argument");
+        perturb_batch_check(h, 1, coeff_table, N, lambda_out);
+        const size_t d = (size_t)h->d;
+        ensure(h->io_a, 2 * d);
+        HIP_CHECK(hipMemcpyAsync(h->io_a.p, v0, d * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->io_a.p + d, v0adj, d * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
+        return perturb_single(h, coeff_table, N, h->io_a.p, h->io_a.p + d, true, norm_mode, coeffsY, tol, maxit, lambda_out, v_out, info);
+    });
+}
+
+int wae_perturb_slots(wae_family *h, const double *coeff_table, int32_t N, int32_t v_slot, int32_t v_col, int32_t vadj_slot, int32_t vadj_col,
+                      int32_t norm_mode, const double *coeffsY, double tol, int32_t maxit, double *lambda_out, double *v_out, wae_solve_info *info) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && coeff_table && lambda_out && N >= 0 && N <= 200, "bad argument");
+        perturb_batch_check(h, 1, coeff_table, N, lambda_out);
+        return perturb_single(h, coeff_table, N, slot_col(h, v_slot, v_col), slot_col(h, vadj_slot, vadj_col), false, norm_mode, coeffsY, tol, maxit,
+                              lambda_out, v_out, info);
+    });
+}
+
 int wae_perturb_batch(wae_family *h, int32_t nsys, const double *coeff_tables, int32_t N, const double *v0, const double *v0adj, int32_t norm_mode,
                       const double *coeffsY, double tol, int32_t maxit, double *lambda_out, double *v_out, int32_t *status_out, wae_solve_info *info) {
     return guarded([&]() {
@@ -2523,7 +2358,9 @@ int wae_perturb_batch(wae_family *h, int32_t nsys, const double *coeff_tables, i
         in.alloc(2 * cnt);
         HIP_CHECK(hipMemcpyAsync(in.p, v0, cnt * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
         HIP_CHECK(hipMemcpyAsync(in.p + cnt, v0adj, cnt * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
-        return perturb_batch_core(h, nsys, coeff_tables, N, in.p, in.p + cnt, true, norm_mode, coeffsY, tol, maxit, lambda_out, v_out, status_out, info);
+        DevBuf<cplx> ws;
+        return perturb_batch_core(h, nsys, coeff_tables, N, in.p, in.p + cnt, true, norm_mode, coeffsY, tol, maxit, lambda_out, v_out,
+                                  (norm_mode & 16) ? 0 : N + 1, status_out, info, ws);
     });
 }
 
@@ -2536,7 +2373,9 @@ int wae_perturb_batch_slots(wae_family *h, int32_t nsys, const double *coeff_tab
         DevBuf<cplx> sv, sw;                                        // (non-consecutive columns are gathered into these)
         const cplx *v = slot_cols_ptr(h, v_slot, v_cols, nsys, sv, h->stream);
         const cplx *w = slot_cols_ptr(h, vadj_slot, vadj_cols, nsys, sw, h->stream);
-        return perturb_batch_core(h, nsys, coeff_tables, N, v, w, false, norm_mode, coeffsY, tol, maxit, lambda_out, v_out, status_out, info);
+        DevBuf<cplx> ws;
+        return perturb_batch_core(h, nsys, coeff_tables, N, v, w, false, norm_mode, coeffsY, tol, maxit, lambda_out, v_out,
+                                  (norm_mode & 16) ? 0 : N + 1, status_out, info, ws);
     });
 }
 

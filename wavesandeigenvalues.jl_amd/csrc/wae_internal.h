@@ -310,9 +310,7 @@ void launch_mask_cols(cplx *X, const cplx *keep, int64_t n, int nb, hipStream_t 
 // Beyn accumulation: A[(p*lA+c0+c)*d + row] += sum_s w[s] z[s]^p X[row][s*l+c], s < nsys, p < npow  (lA columns in A; 0 = l)
 void launch_beyn_accum(const cplx *Xi, int nb, int64_t d, int l, int nsys, const cplx *w, const cplx *z, int npow, cplx *A, hipStream_t s,
                        int lA = 0, int c0 = 0, const int *perm = nullptr);
-// X[row][t] = sum_i G[i][t] V_i[row], V_i = V + i*stride (single vectors), X interleaved with leading dimension T
-void launch_gemv_multi(const cplx *V, size_t stride, int k, const cplx *G, cplx *X, int64_t d, int T, hipStream_t s);
-// batched perturbation recurrence (nb systems interleaved; kernels.hip "Batched adjoint perturbation")
+// perturbation recurrence (nb systems interleaved; kernels.hip "Batched adjoint perturbation")
 // U[row][t][b] = sum_{i<k} G[i][t][b] V_i[row][b], V_i = V + i*stride (interleaved blocks), G: [k][T][nb]; every V_i is read once
 void launch_pt_gemm_batch(const cplx *V, size_t stride, int k, const cplx *G, cplx *U, int64_t d, int T, int nb, hipStream_t s);
 // Y[row][b] (+)= sum_q pc[q] plane_q U[:, plane_col[q], b]  (U: [row][nin][nb]; pc shared by the systems)
