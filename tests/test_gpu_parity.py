@@ -486,6 +486,41 @@ def test_beyn_moments_with_projected_guesses_match_plain_and_oracle():
     Lp._drop_device()
 
 
+def test_plain_beyn_moments_leave_the_snapshot_basis_alone():
+    """wae_beyn_moments shares its loop with wae_beyn_moments_rb but owns no part of the handle's snapshot basis: a plain
+    call between the snapshot phase (mode 0) and the projected phase (mode 2, V=None: the probe matrix kept on the device)
+    leaves wae_rb_export unchanged to the bit, and the three calls together give the moments of the plain path."""
+    import json
+    import os
+    from wae_amd.helmholtz.family import annulus_family
+    from wae_amd.nlevp.beyn import coefficient_table, gauss_points, snapshot_split, spread_order
+    gold = json.load(open(os.path.join(F.GOLDEN_DIR, "annulus_small_beyn.json")))
+    Lp, pb = annulus_family("small", n=gold["n"], tau=gold["tau"])
+    Lp.solver_tol = 1e-11
+    Lp.solver_ref = 2 * np.pi * 500.0
+    Gam = np.array([150 - 150j, 1000 - 150j, 1000 + 150j, 150 + 150j]) * 2 * np.pi
+    d, l, S = pb["d"], 8, 12
+    V = np.random.default_rng(gold["seed_V"]).standard_normal((d, l)) + 0j
+    A0 = compute_moment_matrices(Lp, Gam, V, K=1, N=8, rb=0)
+    fam = Lp.device()
+    zs, ws = gauss_points(Gam, 8)
+    ct = coefficient_table(Lp, zs)
+    idx, rest = snapshot_split(len(zs), S)
+    idx = spread_order(idx)
+    four, rest = rest[::5][:4], np.setdiff1d(rest, rest[::5][:4])
+    assert len(four) == 4 and len(idx) + len(four) + len(rest) == len(zs)
+    kw = dict(K=1, tol=Lp.solver_tol, maxit=Lp.solver_maxit)
+    A = fam.beyn_moments_rb(zs[idx], ws[idx], ct[idx], V, 0, S, **kw)
+    before = fam.rb_export()
+    A = A + fam.beyn_moments(zs[four], ws[four], ct[four], V, **kw)
+    after = fam.rb_export()
+    assert all(np.array_equal(a, b) for a, b in zip(before, after)) and before[1].shape[1:] == (S, S, l)
+    A = A + fam.beyn_moments_rb(zs[rest], ws[rest], ct[rest], None, 2, S, l_total=l, **kw)
+    assert fam.last_info["n_unconverged"] == 0
+    assert relerr(A, A0) < 1e-8
+    Lp._drop_device()
+
+
 def test_eig_residuals_entry(rijke):
     """wae_eig_residuals against the same quantity assembled from the oracle's matrices; host and device inputs."""
     import torch

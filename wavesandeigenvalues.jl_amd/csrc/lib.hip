@@ -906,6 +906,17 @@ static int info_code(wae_solve_info &i) {   // also clears the internal stagnati
     if (i.n_unconverged > 0) return stag ? WAE_WARN_STAGNATION : WAE_WARN_MAXITER;
     return WAE_OK;
 }
+// the wae_solve_info of one public call: zeroed, timed from here, handed to the caller with the call's return code
+struct CallInfo {
+    wae_solve_info li{};
+    double t0 = now_s();
+    int finish(wae_solve_info *out) {
+        li.seconds = now_s() - t0;
+        const int rc = info_code(li);
+        if (out) *out = li;
+        return rc;
+    }
+};
 
 // ----------------------------------------------------------------------------------------------------
 // C ABI
@@ -1375,9 +1386,7 @@ int wae_solve_guess(wae_family *h, const double *coeffs, int32_t ncoef, const do
         require_solver(h);
         HIP_CHECK(hipSetDevice(h->device));
         hipStream_t st = h->stream;
-        wae_solve_info li;
-        memset(&li, 0, sizeof(li));
-        const double t0 = now_s();
+        CallInfo ci;
         const int64_t d = h->d;
         const size_t cnt = (size_t)d * r;
         ensure(h->io_a, cnt); ensure(h->io_b, cnt);
@@ -1404,16 +1413,12 @@ int wae_solve_guess(wae_family *h, const double *coeffs, int32_t ncoef, const do
             }
             launch_colmajor_to_inter(h->io_a.p + (size_t)c0 * d, d, nb, h->Bs.p, nb, st, h->perm());
             if (Gd) launch_colmajor_to_inter(gcol.p + (size_t)c0 * d, d, nb, gint.p, nb, st, h->perm());
-            solve_chunk(h, bt, pcs, h->Bs.p, h->Xs.p, tol, maxit, &li, Gd ? gint.p : nullptr);
+            solve_chunk(h, bt, pcs, h->Bs.p, h->Xs.p, tol, maxit, &ci.li, Gd ? gint.p : nullptr);
             launch_inter_to_colmajor(h->Xs.p, nb, d, nb, h->io_b.p + (size_t)c0 * d, st, h->perm());
         }
         HIP_CHECK(hipMemcpyAsync(X, h->io_b.p, cnt * sizeof(cplx), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        gcol.release(); gint.release();
-        li.seconds = now_s() - t0;
-        const int rc_ = info_code(li);
-        if (info) *info = li;
-        return rc_;
+        return ci.finish(info);
     });
 }
 
@@ -1422,165 +1427,159 @@ int wae_solve(wae_family *h, const double *coeffs, int32_t ncoef, const double *
     return wae_solve_guess(h, coeffs, ncoef, B, nullptr, X, r, op, tol, maxit, info);
 }
 
-int wae_beyn_moments(wae_family *h, int32_t npts, const double *z, const double *w, const double *coeff_table, const double *V, int32_t l, int32_t K,
-                     double tol, int32_t maxit, double *A_out, uint64_t out_dev, wae_solve_info *info) {
-    return guarded([&]() {
-        WAE_REQUIRE(h && npts >= 0 && (npts == 0 || (z && w && coeff_table)) && V && l > 0 && K > 0, "bad argument");
-        WAE_REQUIRE(A_out || out_dev, "no output buffer");
-        require_solver(h);
-        HIP_CHECK(hipSetDevice(h->device));
-        hipStream_t st = h->stream;
-        wae_solve_info li;
-        memset(&li, 0, sizeof(li));
-        const double t0 = now_s();
-        const int64_t d = h->d;
-        const int npow = 2 * K;
-        const size_t acnt = (size_t)d * l * npow;
-        DevBuf<cplx> Aown;
-        cplx *Ad = (cplx *)(uintptr_t)out_dev;
-        if (!Ad) { Aown.alloc(acnt); Ad = Aown.p; }
-        launch_fill_zero(Ad, acnt, st);
-        ensure(h->io_a, (size_t)d * l);
-        HIP_CHECK(hipMemcpyAsync(h->io_a.p, V, (size_t)d * l * sizeof(cplx), hipMemcpyHostToDevice, st));
-        // the reference accepts any l (beyn.jl:39-57): probe columns beyond the batch width are handled in groups of <= NB
-        for (int cg = 0; cg < l; cg += h->NB) {
-            const int lg = std::min(h->NB, l - cg);
-            const int spc = std::max(1, h->NB / lg);   // systems per chunk
-            ensure(h->zw_dev, (size_t)2 * spc);
-            int rep_nb = -1;
-            for (int p0 = 0; p0 < npts; p0 += spc) {
-                const int ns = std::min(spc, npts - p0);
-                Batch bt;
-                bt.nb = ns * lg; bt.cps = lg; bt.nsys = ns; bt.op = WAE_OP_N;
-                std::vector<std::vector<zc>> pcs(ns);
-                std::vector<cplx> zw(2 * ns);
-                for (int s = 0; s < ns; ++s) {
-                    plane_coeffs(h, coeff_table + (size_t)(p0 + s) * 2 * h->T, WAE_OP_N, pcs[s]);
-                    zw[s] = cplx{w[2 * (p0 + s)], w[2 * (p0 + s) + 1]};
-                    zw[ns + s] = cplx{z[2 * (p0 + s)], z[2 * (p0 + s) + 1]};
-                }
-                h->zw_dev.upload(zw.data(), zw.size(), st);
-                HIP_CHECK(hipStreamSynchronize(st));
-                if (bt.nb != rep_nb) { launch_replicate(h->io_a.p + (size_t)cg * d, d, lg, h->Bs.p, bt.nb, st, h->perm()); rep_nb = bt.nb; }   // same right-hand sides for every chunk
-                solve_chunk(h, bt, pcs, h->Bs.p, h->Xs.p, tol, maxit, &li);
-                launch_beyn_accum(h->Xs.p, bt.nb, d, lg, ns, h->zw_dev.p, h->zw_dev.p + ns, npow, Ad, st, l, cg, h->perm());
-            }
-        }
-        if (A_out) HIP_CHECK(hipMemcpyAsync(A_out, Ad, acnt * sizeof(cplx), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        Aown.release();
-        li.seconds = now_s() - t0;
-        const int rc_ = info_code(li);
-        if (info) *info = li;
-        return rc_;
-    });
+// What one call of the contour pass does, and on what.  wae_beyn_moments and every mode of wae_beyn_moments_rb are values of
+// this struct (beyn_pass_for_mode); beyn_pass_core tests its fields, never a mode number.
+struct BeynPass {
+    enum Keep { nothing, into_basis, raw_to_store };
+    bool new_basis = false;          // start an empty basis on the store (else a pass with guesses continues the handle's basis)
+    int absorb = 0;                  // raw snapshots that already lie in the store and are orthonormalised into the new basis
+    bool solve = true;               // false: return once the basis stands -- no system is solved, the moments are not touched
+    bool guess = false;              // a chunk starts from the Galerkin projection on the basis, as soon as that holds a snapshot
+    Keep keep = nothing;             // a chunk's solutions: dropped | appended to the basis | written raw into the slots slot0 + point
+    int enrich_its = 1 << 30;        // keep == nothing: a chunk that took more iterations than this joins the basis all the same
+    bool light_cycle = false;        // solves that start from a guess run the light form of vcycle()
+    bool progressive = false;        // a chunk takes no more points than the basis holds snapshots (at first: 16 columns' worth)
+    bool prefetch_coeffs = false;    // the basis is fixed: a helper thread computes the next chunk's guess coefficients
+    // operands
+    int npts = 0;
+    const double *z = nullptr, *w = nullptr, *coeff_table = nullptr;
+    const double *V = nullptr;       // d x l column-major on the host; nullptr: the probe matrix the handle's basis was started with
+    int l = 0, l_total = 0, col0 = 0;   // V holds the columns col0 .. col0+l-1 of a moment tensor with l_total columns
+    int K = 1, maxit = 0;
+    double tol = 0.0;
+    cplx *Q = nullptr;               // snapshot store of nbasis slots (nullptr: the store the handle owns); this call's slots start at slot0
+    int nbasis = 0, slot0 = 0;
+    double *A_out = nullptr;
+    cplx *out_dev = nullptr;
+    bool accumulate = false;         // add to the moments in out_dev instead of zeroing them first
+};
+
+// the public mode of wae_beyn_moments_rb (include/waehip.h) as a pass, with the argument checks that belong to the mode
+static BeynPass beyn_pass_for_mode(int mode, bool have_V, int npts, int nbasis, int slot0) {
+    WAE_REQUIRE(have_V || mode == 2, "bad argument");
+    WAE_REQUIRE(mode >= 0 && mode <= 4, "mode must be 0 (take snapshots), 1 (rebuild the basis from the store, use it), 2 (use it), "
+                                        "3 (solve from zero, store raw) or 4 (build the basis from the store, solve nothing)");
+    WAE_REQUIRE(nbasis >= 0 && slot0 >= 0 && (mode == 2 || slot0 + ((mode == 0 || mode == 3) ? npts : 0) <= nbasis), "snapshot slots out of range");
+    // adaptive enrichment is off by default: on the C2 contour the orthogonalisation and projection of the extra
+    // vectors cost more than the iterations they saved (measured with thresholds 3, 6, 9); WAE_RB_ENRICH=<its> enables
+    static const int enrich_its = getenv("WAE_RB_ENRICH") ? atoi(getenv("WAE_RB_ENRICH")) : (1 << 30);
+    BeynPass p;
+    switch (mode) {
+    case 0:                          // progressive: later snapshot chunks start from the earlier ones
+        p.new_basis = slot0 == 0; p.guess = true; p.keep = BeynPass::into_basis; p.progressive = true;
+        break;
+    case 1:                          // the store holds slot0 raw snapshots (e.g. gathered from other ranks)
+        p.new_basis = true; p.absorb = slot0;
+        [[fallthrough]];
+    case 2:                          // the projected phase; enrichment would add to the basis where the guesses were poor (a
+                                     // region of the contour close to poles outside it) while the store has room
+        p.guess = true; p.light_cycle = true; p.enrich_its = enrich_its; p.prefetch_coeffs = enrich_its >= (1 << 30);
+        break;
+    case 3:                          // raw solutions into the caller's slots; no basis work (another rank builds it)
+        p.keep = BeynPass::raw_to_store;
+        break;
+    case 4:                          // (the coefficient table only says which terms take part)
+        p.new_basis = true; p.absorb = slot0; p.solve = false;
+        break;
+    }
+    return p;
 }
 
-int wae_beyn_moments_rb(wae_family *h, int32_t npts, const double *z, const double *w, const double *coeff_table, const double *V, int32_t l, int32_t K,
-                        double tol, int32_t maxit, int32_t mode, int32_t nbasis, int32_t slot0, uint64_t Q_dev, double *A_out, uint64_t out_dev,
-                        int32_t accumulate, int32_t l_total, int32_t col0, wae_solve_info *info) {
-    return guarded([&]() {
-        WAE_REQUIRE(h && npts >= 0 && (npts == 0 || (z && w && coeff_table)) && (V || mode == 2) && l > 0 && K > 0, "bad argument");
-        WAE_REQUIRE(A_out || out_dev, "no output buffer");
-        WAE_REQUIRE(mode >= 0 && mode <= 4, "mode must be 0 (take snapshots), 1 (rebuild the basis from the store, use it), 2 (use it), "
-                                            "3 (solve from zero, store raw) or 4 (build the basis from the store, solve nothing)");
-        WAE_REQUIRE(nbasis >= 0 && slot0 >= 0 && (mode == 2 || slot0 + ((mode == 0 || mode == 3) ? npts : 0) <= nbasis), "snapshot slots out of range");
-        WAE_REQUIRE(!accumulate || out_dev, "accumulate needs a device-resident moment buffer");
-        if (l_total <= 0) { l_total = l; col0 = 0; }
-        WAE_REQUIRE(col0 >= 0 && col0 + l <= l_total, "column slice out of range");
-        require_solver(h);
-        WAE_REQUIRE(l <= h->NB, "l exceeds the solver batch width");
-        HIP_CHECK(hipSetDevice(h->device));
-        hipStream_t st = h->stream;
-        wae_solve_info li;
-        memset(&li, 0, sizeof(li));
-        const double t0 = now_s();
-        const int64_t d = h->d;
-        const int npow = 2 * K;
-        const size_t acnt = (size_t)d * l_total * npow;      // the moment tensor has l_total columns; this call fills l of them
-        const size_t vecl = (size_t)d * l;
-        const int T = h->T;
-        RbState &R = h->rb;
-        DevBuf<cplx> Aown;
-        cplx *Ad = (cplx *)(uintptr_t)out_dev;
-        if (!Ad) { Aown.alloc(acnt); Ad = Aown.p; }
-        if (!accumulate) launch_fill_zero(Ad, acnt, st);
-        cplx *Q = (cplx *)(uintptr_t)Q_dev;
-        if (!Q) {                                    // library-owned snapshot store (single-process use)
-            if (mode == 0 && slot0 == 0 && h->rbQ.n < vecl * (size_t)nbasis) h->rbQ.alloc(vecl * (size_t)nbasis);
-            WAE_REQUIRE(h->rbQ.n >= vecl * (size_t)nbasis, "no snapshots stored in the handle: run mode 0 first");
-            Q = h->rbQ.p;
-        }
-        ensure(h->io_a, vecl);
-        if (V) {
-            HIP_CHECK(hipMemcpyAsync(h->io_a.p, V, vecl * sizeof(cplx), hipMemcpyHostToDevice, st));
-        } else {                                     // mode 2 on the basis this handle started: its probe matrix is still in HBM
-            WAE_REQUIRE(mode == 2 && R.vi_valid && R.l == l && R.Vi.n >= vecl, "V may be NULL only in mode 2 after a mode 0/1 call with the same l on this handle");
-            launch_inter_to_colmajor(R.Vi.p, l, d, l, h->io_a.p, st, h->perm());      // (io_a holds the caller's numbering, like an uploaded V)
-        }
-        const int spc = std::max(1, h->NB / l);   // systems per chunk
+// One chunk made ready: the plane coefficients of its ns points (returned), their weights and points on the device
+// (zw_dev = [w | z]) and, when the chunk width changed, the lg probe columns from column cg on replicated into Bs.
+static std::vector<std::vector<zc>> beyn_chunk_prepare(wae_family *h, const BeynPass &p, int p0, int ns, int cg, int lg, int &rep_nb) {
+    hipStream_t st = h->stream;
+    std::vector<std::vector<zc>> pcs(ns);
+    std::vector<cplx> zw(2 * ns);
+    for (int s = 0; s < ns; ++s) {
+        plane_coeffs(h, p.coeff_table + (size_t)(p0 + s) * 2 * h->T, WAE_OP_N, pcs[s]);
+        zw[s] = cplx{p.w[2 * (p0 + s)], p.w[2 * (p0 + s) + 1]};
+        zw[ns + s] = cplx{p.z[2 * (p0 + s)], p.z[2 * (p0 + s) + 1]};
+    }
+    h->zw_dev.upload(zw.data(), zw.size(), st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (ns * lg != rep_nb) {         // same right-hand sides for every chunk
+        launch_replicate(h->io_a.p + (size_t)cg * h->d, h->d, lg, h->Bs.p, ns * lg, st, h->perm());
+        rep_nb = ns * lg;
+    }
+    return pcs;
+}
+
+static int beyn_pass_core(wae_family *h, const BeynPass &p, wae_solve_info *info) {
+    require_solver(h);
+    // a pass without a store takes any l (as the reference does, beyn.jl:39-57); a basis is one per call and spans one batch
+    const bool store = p.new_basis || p.guess || p.keep != BeynPass::nothing;
+    WAE_REQUIRE(!store || p.l <= h->NB, "l exceeds the solver batch width");
+    HIP_CHECK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    CallInfo ci;
+    const int64_t d = h->d;
+    const int l = p.l, T = h->T, npts = p.npts, npow = 2 * p.K;
+    const size_t acnt = (size_t)d * p.l_total * npow;        // the moment tensor has l_total columns; this call fills l of them
+    const size_t vecl = (size_t)d * l;
+    RbState &R = h->rb;                                      // (touched only where a field of the pass asks for the store or the basis)
+    DevBuf<cplx> Aown;
+    cplx *Ad = p.out_dev;
+    if (!Ad) { Aown.alloc(acnt); Ad = Aown.p; }
+    if (!p.accumulate) launch_fill_zero(Ad, acnt, st);
+    cplx *Q = p.Q;
+    if (store && !Q) {                           // library-owned snapshot store (single-process use)
+        if (p.new_basis && p.keep == BeynPass::into_basis && h->rbQ.n < vecl * (size_t)p.nbasis) h->rbQ.alloc(vecl * (size_t)p.nbasis);
+        WAE_REQUIRE(h->rbQ.n >= vecl * (size_t)p.nbasis, "no snapshots stored in the handle: run mode 0 first");
+        Q = h->rbQ.p;
+    }
+    ensure(h->io_a, vecl);
+    if (p.V) {
+        HIP_CHECK(hipMemcpyAsync(h->io_a.p, p.V, vecl * sizeof(cplx), hipMemcpyHostToDevice, st));
+    } else {                                     // the probe matrix of the basis this handle started is still in HBM
+        WAE_REQUIRE(R.vi_valid && R.l == l && R.Vi.n >= vecl, "V may be NULL only in mode 2 after a mode 0/1 call with the same l on this handle");
+        launch_inter_to_colmajor(R.Vi.p, l, d, l, h->io_a.p, st, h->perm());      // (io_a holds the caller's numbering, like an uploaded V)
+    }
+    if (p.guess && R.ycoef.n < (size_t)std::max(p.nbasis, 1) * h->NB) R.ycoef.alloc((size_t)std::max(p.nbasis, 1) * h->NB);
+    if (p.new_basis) {
+        launch_colmajor_to_inter(h->io_a.p, d, l, h->W.p, l, st, h->perm());
+        rb_reset(h, Q, p.nbasis, l, p.coeff_table, npts, h->W.p);
+        if (p.absorb > 0) rb_append(h, p.absorb);
+    } else if (p.guess) {
+        WAE_REQUIRE(R.Q == Q && R.l == l && R.cap == p.nbasis, "the basis in the handle belongs to another store / shape");
+        WAE_REQUIRE(p.keep != BeynPass::into_basis || p.slot0 == R.S, "mode 0 appends: slot0 must equal the number of snapshots taken so far");
+        WAE_REQUIRE(p.keep == BeynPass::into_basis || R.S > 0, "mode 2 needs a basis: run mode 0 (or 1) first");
+    }
+    if (!p.solve) {
+        HIP_CHECK(hipStreamSynchronize(st));
+        ci.li.levels = (int)h->ops.size();
+        return ci.finish(info);
+    }
+
+    static const bool rbdbg = getenv("WAE_GMRES_DEBUG") && atoi(getenv("WAE_GMRES_DEBUG"));
+    double t_guess = 0.0, t_solve = 0.0, t_append = 0.0;
+    // A progressive pass should start with small chunks: a chunk never takes more points than the basis already
+    // holds, starting with 16 columns' worth (1, 1, 2, 4, 4, ... points for l = 16; 16, 16, 32 for l = 1).  Measured on
+    // the snapshot phase: C2 0.695 -> 0.668 s, C3 2.71 -> 2.56 s; one rank's share of C3 when the probe columns are split
+    // over 8 / 4 / 2 GPUs (1 / 2 / 4 columns x 64 points): 0.97 -> 0.63, 1.19 -> 0.97, 1.79 -> 1.69 s (dev/c3_rank_share.py).
+    // WAE_RB_DOUBLING=0 restores full chunks, WAE_RB_C0COLS sets the starting width (4, 8, 32 measured: slower).
+    static const int doubling = getenv("WAE_RB_DOUBLING") ? atoi(getenv("WAE_RB_DOUBLING")) : 1;
+    static const int c0cols = getenv("WAE_RB_C0COLS") ? std::max(1, atoi(getenv("WAE_RB_C0COLS"))) : 16;
+    struct LightOff { bool &on; ~LightOff() { on = false; } } light_off{h->vc_light};      // set before every solve; off again however the loop ends
+    for (int cg = 0; cg < l; cg += h->NB) {      // probe columns in groups of <= NB (one group whenever there is a store)
+        const int lg = std::min(h->NB, l - cg);
+        const int spc = std::max(1, h->NB / lg);   // systems per chunk
+        const int c0 = doubling ? std::max(1, c0cols / lg) : spc;
         ensure(h->zw_dev, (size_t)2 * spc);
-        if (R.ycoef.n < (size_t)std::max(nbasis, 1) * h->NB) R.ycoef.alloc((size_t)std::max(nbasis, 1) * h->NB);
-
-        static const bool rbdbg = getenv("WAE_GMRES_DEBUG") && atoi(getenv("WAE_GMRES_DEBUG"));
-        // adaptive enrichment is off by default: on the C2 contour the orthogonalisation and projection of the extra
-        // vectors cost more than the iterations they saved (measured with thresholds 3, 6, 9); WAE_RB_ENRICH=<its> enables
-        static const int enrich_its = getenv("WAE_RB_ENRICH") ? atoi(getenv("WAE_RB_ENRICH")) : (1 << 30);
-        double t_guess = 0.0, t_solve = 0.0, t_append = 0.0;
-        if ((mode == 0 && slot0 == 0) || mode == 1 || mode == 4) {
-            launch_colmajor_to_inter(h->io_a.p, d, l, h->W.p, l, st, h->perm());
-            rb_reset(h, Q, nbasis, l, coeff_table, npts, h->W.p);
-            if (mode == 1 || mode == 4) rb_append(h, slot0);    // the store holds slot0 raw snapshots (e.g. gathered from other ranks)
-            if (mode == 4) {                       // basis built (the coefficient table only said which terms take part): nothing to solve
-                HIP_CHECK(hipStreamSynchronize(st));
-                Aown.release();
-                li.seconds = now_s() - t0;
-                li.levels = (int)h->ops.size();
-                if (info) *info = li;
-                return (int)WAE_OK;
-            }
-        } else if (mode == 3) {
-            // raw snapshots: the handle's basis is not touched
-        } else {
-            WAE_REQUIRE(R.Q == Q && R.l == l && R.cap == nbasis, "the basis in the handle belongs to another store / shape");
-            WAE_REQUIRE(mode != 0 || slot0 == R.S, "mode 0 appends: slot0 must equal the number of snapshots taken so far");
-            WAE_REQUIRE(mode != 2 || R.S > 0, "mode 2 needs a basis: run mode 0 (or 1) first");
-        }
-
-        // with a fixed basis (modes 1/2, no enrichment) the coefficients of the next chunk's guesses are computed on a helper
-        // thread while the device solves the current chunk
-        const bool fixed_basis = (mode == 1 || mode == 2) && enrich_its >= (1 << 30);
         std::future<std::vector<cplx>> next_Y;
         auto launch_coeffs = [&](int q0) {
             const int nq = std::min(spc, npts - q0);
-            return std::async(std::launch::async, [h, coeff_table, q0, nq, T]() { return rb_guess_coeffs(h, coeff_table + (size_t)q0 * 2 * T, nq); });
+            const double *ct = p.coeff_table + (size_t)q0 * 2 * T;
+            return std::async(std::launch::async, [h, ct, nq]() { return rb_guess_coeffs(h, ct, nq); });
         };
-        if (fixed_basis && npts > 0 && R.S > 0) next_Y = launch_coeffs(0);
-        // Mode 0 is progressive, so the first chunks should be small: a chunk never takes more points than the basis already
-        // holds, starting with 16 columns' worth (1, 1, 2, 4, 4, ... points for l = 16; 16, 16, 32 for l = 1).  Measured on
-        // the snapshot phase: C2 0.695 -> 0.668 s, C3 2.71 -> 2.56 s; one rank's share of C3 when the probe columns are split
-        // over 8 / 4 / 2 GPUs (1 / 2 / 4 columns x 64 points): 0.97 -> 0.63, 1.19 -> 0.97, 1.79 -> 1.69 s (dev/c3_rank_share.py).
-        // WAE_RB_DOUBLING=0 restores full chunks, WAE_RB_C0COLS sets the starting width (4, 8, 32 measured: slower).
-        static const int doubling = getenv("WAE_RB_DOUBLING") ? atoi(getenv("WAE_RB_DOUBLING")) : 1;
-        static const int c0cols = getenv("WAE_RB_C0COLS") ? std::max(1, atoi(getenv("WAE_RB_C0COLS"))) : 16;
-        const int c0 = doubling ? std::max(1, c0cols / l) : spc;
-        int ns_next = 0, rep_nb = -1;
-        for (int p0 = 0; p0 < npts; p0 += ns_next) {
-            const int ns = (mode == 0) ? std::min(std::min(spc, npts - p0), std::max(c0, R.S)) : std::min(spc, npts - p0);
-            ns_next = ns;
-            Batch bt;
-            bt.nb = ns * l; bt.cps = l; bt.nsys = ns; bt.op = WAE_OP_N;
-            std::vector<std::vector<zc>> pcs(ns);
-            std::vector<cplx> zw(2 * ns);
-            for (int s = 0; s < ns; ++s) {
-                plane_coeffs(h, coeff_table + (size_t)(p0 + s) * 2 * T, WAE_OP_N, pcs[s]);
-                zw[s] = cplx{w[2 * (p0 + s)], w[2 * (p0 + s) + 1]};
-                zw[ns + s] = cplx{z[2 * (p0 + s)], z[2 * (p0 + s) + 1]};
-            }
-            h->zw_dev.upload(zw.data(), zw.size(), st);
-            HIP_CHECK(hipStreamSynchronize(st));
-            if (bt.nb != rep_nb) { launch_replicate(h->io_a.p, d, l, h->Bs.p, bt.nb, st, h->perm()); rep_nb = bt.nb; }   // same right-hand sides for every chunk
-            const bool guess = mode != 3 && R.S > 0;   // mode 0 is progressive: later snapshot chunks start from the earlier ones
+        if (p.prefetch_coeffs && npts > 0 && R.S > 0) next_Y = launch_coeffs(0);
+        int rep_nb = -1;
+        for (int p0 = 0, ns; p0 < npts; p0 += ns) {
+            ns = std::min(spc, npts - p0);
+            if (p.progressive) ns = std::min(ns, std::max(c0, R.S));
+            const Batch bt{ns * lg, lg, ns, WAE_OP_N};
+            const auto pcs = beyn_chunk_prepare(h, p, p0, ns, cg, lg, rep_nb);
+            const bool guess = p.guess && R.S > 0;
             const double ta = now_s();
             if (guess) {
                 std::vector<cplx> Y;
@@ -1588,25 +1587,20 @@ int wae_beyn_moments_rb(wae_family *h, int32_t npts, const double *z, const doub
                     Y = next_Y.get();
                     if (p0 + spc < npts) next_Y = launch_coeffs(p0 + spc);
                 } else {
-                    Y = rb_guess_coeffs(h, coeff_table + (size_t)p0 * 2 * T, ns);
+                    Y = rb_guess_coeffs(h, p.coeff_table + (size_t)p0 * 2 * T, ns);
                 }
                 rb_apply_guess(h, Y, ns, h->Xs.p);
             }
             const double tb = now_s();
-            struct LightGuard { wae_family *h; ~LightGuard() { h->vc_light = false; } } light_guard{h};
-            h->vc_light = guess && (mode == 1 || mode == 2);       // (vcycle: the cheaper cycle for the solves of the projected phase)
-            const int its = solve_chunk(h, bt, pcs, h->Bs.p, h->Xs.p, tol, maxit, &li, nullptr, guess);
-            h->vc_light = false;
-            launch_beyn_accum(h->Xs.p, bt.nb, d, l, ns, h->zw_dev.p, h->zw_dev.p + ns, npow, Ad, st, l_total, col0, h->perm());
+            h->vc_light = guess && p.light_cycle;
+            const int its = solve_chunk(h, bt, pcs, h->Bs.p, h->Xs.p, p.tol, p.maxit, &ci.li, nullptr, guess);
+            launch_beyn_accum(h->Xs.p, bt.nb, d, lg, ns, h->zw_dev.p, h->zw_dev.p + ns, npow, Ad, st, p.l_total, p.col0 + cg, h->perm());
             if (rbdbg) HIP_CHECK(hipStreamSynchronize(st));
             const double tc = now_s();
-            // mode 0 keeps every solution; modes 1/2 enrich the basis where the guesses were poor (a region of the
-            // contour close to poles outside it), as long as the store has room
-            if (mode == 3) {                       // raw solutions into the caller's slots; no basis work (another rank builds it)
+            if (p.keep == BeynPass::raw_to_store) {
                 for (int s = 0; s < ns; ++s)
-                    launch_extract_cols(h->Xs.p, bt.nb, s * l, l, Q + (size_t)(slot0 + p0 + s) * vecl, d, st);
-            } else
-            if (mode == 0 || (its > enrich_its && R.S + ns <= R.cap)) {
+                    launch_extract_cols(h->Xs.p, bt.nb, s * l, l, Q + (size_t)(p.slot0 + p0 + s) * vecl, d, st);
+            } else if (p.keep == BeynPass::into_basis || (its > p.enrich_its && R.S + ns <= R.cap)) {
                 for (int s = 0; s < ns; ++s)
                     launch_extract_cols(h->Xs.p, bt.nb, s * l, l, Q + (size_t)(R.S + s) * vecl, d, st);
                 rb_append(h, ns);
@@ -1616,14 +1610,39 @@ int wae_beyn_moments_rb(wae_family *h, int32_t npts, const double *z, const doub
                 t_guess += tb - ta; t_solve += tc - tb; t_append += now_s() - tc;
             }
         }
-        if (rbdbg) fprintf(stderr, "[rb] mode=%d S=%d guess %.3f s  solve %.3f s  append %.3f s\n", mode, R.S, t_guess, t_solve, t_append);
-        if (A_out) HIP_CHECK(hipMemcpyAsync(A_out, Ad, acnt * sizeof(cplx), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        Aown.release();
-        li.seconds = now_s() - t0;
-        const int rc_ = info_code(li);
-        if (info) *info = li;
-        return rc_;
+    }
+    if (rbdbg && store) fprintf(stderr, "[rb] keep=%d S=%d guess %.3f s  solve %.3f s  append %.3f s\n", (int)p.keep, R.S, t_guess, t_solve, t_append);
+    if (p.A_out) HIP_CHECK(hipMemcpyAsync(p.A_out, Ad, acnt * sizeof(cplx), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return ci.finish(info);
+}
+
+int wae_beyn_moments(wae_family *h, int32_t npts, const double *z, const double *w, const double *coeff_table, const double *V, int32_t l, int32_t K,
+                     double tol, int32_t maxit, double *A_out, uint64_t out_dev, wae_solve_info *info) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && npts >= 0 && (npts == 0 || (z && w && coeff_table)) && V && l > 0 && K > 0, "bad argument");
+        WAE_REQUIRE(A_out || out_dev, "no output buffer");
+        BeynPass p;                  // every system from zero and nothing kept: no store, and the handle's basis is left alone
+        p.npts = npts; p.z = z; p.w = w; p.coeff_table = coeff_table; p.V = V; p.l = p.l_total = l; p.K = K; p.tol = tol; p.maxit = maxit;
+        p.A_out = A_out; p.out_dev = (cplx *)(uintptr_t)out_dev;
+        return beyn_pass_core(h, p, info);
+    });
+}
+
+int wae_beyn_moments_rb(wae_family *h, int32_t npts, const double *z, const double *w, const double *coeff_table, const double *V, int32_t l, int32_t K,
+                        double tol, int32_t maxit, int32_t mode, int32_t nbasis, int32_t slot0, uint64_t Q_dev, double *A_out, uint64_t out_dev,
+                        int32_t accumulate, int32_t l_total, int32_t col0, wae_solve_info *info) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && npts >= 0 && (npts == 0 || (z && w && coeff_table)) && l > 0 && K > 0, "bad argument");
+        WAE_REQUIRE(A_out || out_dev, "no output buffer");
+        BeynPass p = beyn_pass_for_mode(mode, V != nullptr, npts, nbasis, slot0);
+        WAE_REQUIRE(!accumulate || out_dev, "accumulate needs a device-resident moment buffer");
+        if (l_total <= 0) { l_total = l; col0 = 0; }
+        WAE_REQUIRE(col0 >= 0 && col0 + l <= l_total, "column slice out of range");
+        p.npts = npts; p.z = z; p.w = w; p.coeff_table = coeff_table; p.V = V; p.l = l; p.l_total = l_total; p.col0 = col0; p.K = K; p.tol = tol;
+        p.maxit = maxit; p.Q = (cplx *)(uintptr_t)Q_dev; p.nbasis = nbasis; p.slot0 = slot0;
+        p.A_out = A_out; p.out_dev = (cplx *)(uintptr_t)out_dev; p.accumulate = accumulate != 0;
+        return beyn_pass_core(h, p, info);
     });
 }
 
@@ -1704,9 +1723,8 @@ static int arnoldi_core(wae_family *h, int32_t nsys, const double *coeffsA, cons
     {
         HIP_CHECK(hipSetDevice(h->device));
         hipStream_t st = h->stream;
-        wae_solve_info li;
-        memset(&li, 0, sizeof(li));
-        const double t0 = now_s();
+        CallInfo ci;
+        wae_solve_info &li = ci.li;
         const int64_t d = h->d;
         const int T = h->T;
         const size_t vec = (size_t)d * nsys;
@@ -1873,10 +1891,7 @@ static int arnoldi_core(wae_family *h, int32_t nsys, const double *coeffsA, cons
             h->arn_cols = std::min(done, m) + 1;
         }
         for (int sy = 0; sy < nsys; ++sy) memcpy(H_out + (size_t)sy * (m + 1) * m * 2, H[sy].data(), H[sy].size() * sizeof(zc));
-        li.seconds = now_s() - t0;
-        const int rc_ = info_code(li);
-        if (info) *info = li;
-        return rc_;
+        return ci.finish(info);
     }
 }
 
@@ -2109,9 +2124,8 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
     const int norm_mode = norm_mode_in & 15;
     WAE_REQUIRE(norm_mode >= 0 && norm_mode <= 2 && (norm_mode != 2 || coeffsY), "bad norm_mode");
     hipStream_t st = h->stream;
-    wae_solve_info li;
-    memset(&li, 0, sizeof(li));
-    const double t0 = now_s();
+    CallInfo ci;
+    wae_solve_info &li = ci.li;
     const int64_t d = h->d;
     const int T = h->T, ns = nsys, npl = h->nplanes;
     const int nb = perturb_batch_width(h, ns);
@@ -2300,10 +2314,8 @@ static int perturb_batch_core(wae_family *h, int32_t nsys, const double *coeff_t
         for (int it : order_iters) fprintf(stderr, " %d", it);
         fprintf(stderr, "\n");
     }
-    li.seconds = now_s() - t0;
-    int rc_ = info_code(li);
+    int rc_ = ci.finish(info);
     for (int s = 0; s < ns; ++s) if (status[s] != WAE_OK && rc_ == WAE_OK) rc_ = WAE_WARN_MAXITER;
-    if (info) *info = li;
     return rc_;
 }
 

@@ -291,15 +291,26 @@ extern "C" int wae_beyn_moments_mgpu(wae_family *const *handles, int32_t ngpu, i
         };
         int code = 0;
         const size_t vecl_all = (size_t)d * l;
+        // every ngpu-th entry of the first n of `from`, starting at the g-th: device g's round-robin share
+        auto share = [&](const std::vector<int> &from, size_t n, int g) {
+            std::vector<int> mine;
+            for (size_t i = g; i < n; i += ngpu) mine.push_back(from[i]);
+            return mine;
+        };
+        // Device g runs the points `pts`, in that order, for the lc probe columns from column c0 on and adds their moments into
+        // Ad[g]: through wae_beyn_moments (mode = PLAIN), or through `mode` of wae_beyn_moments_rb on the store Q (nbasis slots, slot0).
+        const int PLAIN = -1;
+        auto run = [&](int g, const std::vector<int> &pts, int mode, cplx *Q, int nbasis, int slot0, int c0, int lc, wae_solve_info *li) {
+            const auto zz = take(z, pts, 2), ww = take(w, pts, 2), cc = take(coeff_table, pts, 2 * T);
+            const int32_t n = (int32_t)pts.size();
+            const uint64_t out = (uint64_t)(uintptr_t)Ad[g].p;
+            if (mode == PLAIN) return wae_beyn_moments(handles[g], n, zz.data(), ww.data(), cc.data(), V, l, K, tol, maxit, nullptr, out, li);
+            return wae_beyn_moments_rb(handles[g], n, zz.data(), ww.data(), cc.data(), V + (size_t)2 * d * c0, lc, K, tol, maxit, mode, nbasis, slot0,
+                                       (uint64_t)(uintptr_t)Q, nullptr, out, 1, l, c0, li);
+        };
         if (S == 0) {
             // no snapshot scheme: every device integrates its share of the points from zero guesses
-            code = std::max(code, on_all([&](int g, wae_solve_info *li) {
-                std::vector<int> mine;
-                for (size_t i = g; i < rest.size(); i += ngpu) mine.push_back(rest[i]);
-                const auto zz = take(z, mine, 2), ww = take(w, mine, 2), cc = take(coeff_table, mine, 2 * T);
-                return wae_beyn_moments(handles[g], (int32_t)mine.size(), zz.data(), ww.data(), cc.data(), V, l, K, tol, maxit, nullptr,
-                                        (uint64_t)(uintptr_t)Ad[g].p, li);
-            }));
+            code = std::max(code, on_all([&](int g, wae_solve_info *li) { return run(g, share(rest, rest.size(), g), PLAIN, nullptr, 0, 0, 0, l, li); }));
         } else if (l % ngpu == 0) {
             // The probe columns divide over the devices.  Snapshot phase, WAE_SNAPSHOT_SPLIT:
             //   "columns" (default): device g solves all S points for its columns progressively (mode 0) -- fewer, longer, narrower
@@ -326,13 +337,7 @@ extern "C" int wae_beyn_moments_mgpu(wae_family *const *handles, int32_t ngpu, i
                 const size_t rawn = (size_t)per * vecl_all;
                 std::vector<DevBuf<cplx>> raw(ngpu), allraw(ngpu);
                 for (int g = 0; g < ngpu; ++g) { HIP_CHECK(hipSetDevice(devs[g])); raw[g].alloc(rawn); allraw[g].alloc(rawn * ngpu); }
-                code = std::max(code, on_all([&](int g, wae_solve_info *li) {
-                    std::vector<int> mine;
-                    for (int i = g; i < S; i += ngpu) mine.push_back(snap[i]);
-                    const auto zz = take(z, mine, 2), ww = take(w, mine, 2), cc = take(coeff_table, mine, 2 * T);
-                    return wae_beyn_moments_rb(handles[g], per, zz.data(), ww.data(), cc.data(), V, l, K, tol, maxit, 3, per, 0,
-                                               (uint64_t)(uintptr_t)raw[g].p, nullptr, (uint64_t)(uintptr_t)Ad[g].p, 1, 0, 0, li);
-                }));
+                code = std::max(code, on_all([&](int g, wae_solve_info *li) { return run(g, share(snap, S, g), 3, raw[g].p, per, 0, 0, l, li); }));
                 {
                     std::vector<cplx *> src(ngpu), dst(ngpu);
                     for (int g = 0; g < ngpu; ++g) { src[g] = raw[g].p; dst[g] = allraw[g].p; }
@@ -346,19 +351,11 @@ extern "C" int wae_beyn_moments_mgpu(wae_family *const *handles, int32_t ngpu, i
                 ex.sync_all();
                 std::vector<int> order;                          // the snapshot point behind every slot: [source device][its points]
                 for (int g = 0; g < ngpu; ++g)
-                    for (int i = g; i < S; i += ngpu) order.push_back(snap[i]);
-                const auto zo = take(z, order, 2), wo = take(w, order, 2), co = take(coeff_table, order, 2 * T);
-                code = std::max(code, on_all([&](int g, wae_solve_info *li) {
-                    return wae_beyn_moments_rb(handles[g], S, zo.data(), wo.data(), co.data(), V + (size_t)2 * d * g * ls, ls, K, tol, maxit, 4, S, S,
-                                               (uint64_t)(uintptr_t)local[g].p, nullptr, (uint64_t)(uintptr_t)Ad[g].p, 1, l, g * ls, li);
-                }));
+                    for (int i : share(snap, S, g)) order.push_back(i);
+                code = std::max(code, on_all([&](int g, wae_solve_info *li) { return run(g, order, 4, local[g].p, S, S, g * ls, ls, li); }));
                 for (int g = 0; g < ngpu; ++g) { HIP_CHECK(hipSetDevice(devs[g])); raw[g].release(); allraw[g].release(); }
             } else {
-                const auto zs = take(z, snap, 2), ws = take(w, snap, 2), cs = take(coeff_table, snap, 2 * T);
-                code = std::max(code, on_all([&](int g, wae_solve_info *li) {
-                    return wae_beyn_moments_rb(handles[g], S, zs.data(), ws.data(), cs.data(), V + (size_t)2 * d * g * ls, ls, K, tol, maxit, 0, S, 0,
-                                               (uint64_t)(uintptr_t)local[g].p, nullptr, (uint64_t)(uintptr_t)Ad[g].p, 1, l, g * ls, li);
-                }));
+                code = std::max(code, on_all([&](int g, wae_solve_info *li) { return run(g, snap, 0, local[g].p, S, 0, g * ls, ls, li); }));
             }
             {
                 std::vector<cplx *> src(ngpu), dst(ngpu);
@@ -388,13 +385,7 @@ extern "C" int wae_beyn_moments_mgpu(wae_family *const *handles, int32_t ngpu, i
                 if (wae_rb_import(handles[g], S, l, (uint64_t)(uintptr_t)store[g].p, nk, kact.data(), Hk_all.data(), g_all.data()) != WAE_OK)
                     throw WaeError(WAE_ERR_INVALID, wae_last_error());
             }
-            code = std::max(code, on_all([&](int g, wae_solve_info *li) {
-                std::vector<int> mine;
-                for (size_t i = g; i < rest.size(); i += ngpu) mine.push_back(rest[i]);
-                const auto zz = take(z, mine, 2), ww = take(w, mine, 2), cc = take(coeff_table, mine, 2 * T);
-                return wae_beyn_moments_rb(handles[g], (int32_t)mine.size(), zz.data(), ww.data(), cc.data(), V, l, K, tol, maxit, 2, S, 0,
-                                           (uint64_t)(uintptr_t)store[g].p, nullptr, (uint64_t)(uintptr_t)Ad[g].p, 1, 0, 0, li);
-            }));
+            code = std::max(code, on_all([&](int g, wae_solve_info *li) { return run(g, share(rest, rest.size(), g), 2, store[g].p, S, 0, 0, l, li); }));
         } else {
             // l not divisible by the number of devices: the snapshot POINTS are split, the raw snapshots all-gathered, and every
             // device rebuilds the (same) basis from them (mode 1)
@@ -404,26 +395,14 @@ extern "C" int wae_beyn_moments_mgpu(wae_family *const *handles, int32_t ngpu, i
             for (int i = Su; i < S; ++i) rest.push_back(snap[i]);
             const size_t slab = (size_t)per * vecl_all;
             for (int g = 0; g < ngpu; ++g) { HIP_CHECK(hipSetDevice(devs[g])); local[g].alloc(slab); store[g].alloc(slab * ngpu); }
-            code = std::max(code, on_all([&](int g, wae_solve_info *li) {
-                std::vector<int> mine;
-                for (int i = g; i < Su; i += ngpu) mine.push_back(snap[i]);
-                const auto zz = take(z, mine, 2), ww = take(w, mine, 2), cc = take(coeff_table, mine, 2 * T);
-                return wae_beyn_moments_rb(handles[g], per, zz.data(), ww.data(), cc.data(), V, l, K, tol, maxit, 0, per, 0,
-                                           (uint64_t)(uintptr_t)local[g].p, nullptr, (uint64_t)(uintptr_t)Ad[g].p, 1, 0, 0, li);
-            }));
+            code = std::max(code, on_all([&](int g, wae_solve_info *li) { return run(g, share(snap, Su, g), 0, local[g].p, per, 0, 0, l, li); }));
             {
                 std::vector<cplx *> src(ngpu), dst(ngpu);
                 for (int g = 0; g < ngpu; ++g) { src[g] = local[g].p; dst[g] = store[g].p; }
                 ex.all_gather(src, dst, slab);
             }
             ex.sync_all();
-            code = std::max(code, on_all([&](int g, wae_solve_info *li) {
-                std::vector<int> mine;
-                for (size_t i = g; i < rest.size(); i += ngpu) mine.push_back(rest[i]);
-                const auto zz = take(z, mine, 2), ww = take(w, mine, 2), cc = take(coeff_table, mine, 2 * T);
-                return wae_beyn_moments_rb(handles[g], (int32_t)mine.size(), zz.data(), ww.data(), cc.data(), V, l, K, tol, maxit, 1, Su, Su,
-                                           (uint64_t)(uintptr_t)store[g].p, nullptr, (uint64_t)(uintptr_t)Ad[g].p, 1, 0, 0, li);
-            }));
+            code = std::max(code, on_all([&](int g, wae_solve_info *li) { return run(g, share(rest, rest.size(), g), 1, store[g].p, Su, Su, 0, l, li); }));
         }
         // sum of the partial moment tensors on device 0 (in place), then to the host
         {
