@@ -433,7 +433,7 @@ int wae_debug_spmv(wae_family *h, int32_t which, int32_t level, int32_t mode, co
  *          status_out: NULL or the status word of the dense inversion (DENSE only; 0 = every pivot non-zero).
  *   A size outside the ranges a launcher accepts, or an array shorter than the sizes need: WAE_ERR_INVALID, nothing is launched
  *   past the point of the refusal.
- * Contract of a masked chunk (cmask byte 0), as the consumers rely on it (kernels.hip gmres_step_kernel, gmres_pair_coef_kernel read
+ * Contract of a masked chunk (cmask byte 0), as the consumers rely on it (vec.hip gmres_step_kernel, gmres_pair_coef_kernel read
  * the reductions of every column, retired ones included, and take 0 for "column retired": 1/norm = 0 keeps it out of every later
  * coefficient): vector outputs of its columns keep what they held; every reduction output of its columns (dots, norms, 1/norm^2,
  * Gram entries) is WRITTEN as exact 0.  Columns never mix: a NaN in one column changes no output of another.

@@ -272,7 +272,7 @@ struct Gmres {
     int m = (int)std::min<size_t>(150, h->V.n / vec - 1) - off;
     // wide batches, single Gram-Schmidt pass: unnormalised basis (single_step; 4096: coefficients of one axpy launch)
     bool lazy = gmres_env().lazy && !reorth && ((size_t)m + off + 2) * nb <= 4096 && ((size_t)m + off + 2) * nb <= h->vsq.n;
-    // Pair steps in the two-pass recurrence (kernels.hip "Two Arnoldi steps per pass over the basis"): w1 = Op v_j, w2 = Op w1, both
+    // Pair steps in the two-pass recurrence (vec.hip "Two Arnoldi steps per pass over the basis"): w1 = Op v_j, w2 = Op w1, both
     // orthogonalised against V_0..j by two passes of classical Gram-Schmidt that read the basis ONCE each for the two vectors -- four
     // readings of the basis per two steps instead of eight; same Krylov space, Hessenberg columns recovered on the host (pair_step).
     // For batches whose basis vectors are large enough for the readings to be what an iteration costs (>= 4 MB per vector).
@@ -379,7 +379,7 @@ struct Gmres {
     }
 
     // The device recurrence: the same left-preconditioned, lock-step, unnormalised-basis GMRES(m) as the host's lazy form, with the
-    // per-column Hessenberg / Givens / convergence bookkeeping in kernels (kernels.hip gmres_*_kernel): an iteration is a chain of
+    // per-column Hessenberg / Givens / convergence bookkeeping in kernels (vec.hip gmres_*_kernel): an iteration is a chain of
     // launches with no device-to-host copy; the host looks at three status words every WAE_GMRES_SYNC iterations (default 4) and at
     // the per-column figures once per restart cycle.  Columns that converge between two looks are masked on the device at once
     // (their 8-column chunks are skipped by every kernel), so the overshoot costs launches, not traffic.
@@ -401,7 +401,7 @@ struct Gmres {
         S.R = h->gs_R.p; S.cs = h->gs_cs.p; S.sn = h->gs_sn.p; S.g = h->gs_g.p; S.sv = h->gs_sv.p; S.vsq = h->vsq.p;
         S.conv = h->gs_int.p; S.steps = S.conv + nb; S.iters = S.steps + nb; S.histlen = S.iters + nb; S.stalled = S.histlen + nb; S.status = S.stalled + nb;
         S.relres = h->gs_relres.p; S.bnorm = h->gs_bnorm.p; S.hist = h->gs_hist.p; S.rescale = h->gs_rescale.p; S.cmask = h->cmask.p;
-        // Pair steps (kernels.hip "Two Arnoldi steps per pass over the basis"): from iteration pair_min of a cycle on, while most columns
+        // Pair steps (vec.hip "Two Arnoldi steps per pass over the basis"): from iteration pair_min of a cycle on, while most columns
         // are still active, the operator is applied twice before the Gram-Schmidt pass.  Same Krylov space, same per-column stopping test
         // after each of the two steps; what it costs is one operator application when the batch ends on the first step of a pair.
         const int pair_min = env.pair_min;

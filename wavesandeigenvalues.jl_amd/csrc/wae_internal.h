@@ -238,7 +238,7 @@ struct Transfer {                   // P (n_fine x n_coarse) and R = P^T as sing
     OpDev devR() const;
 };
 
-// kernel launch wrappers (kernels.hip) -----------------------------------------------------------------
+// kernel launch wrappers: operator, transfer and dense level (kernels.hip) ------------------------------
 enum { MODE_AX = 0, MODE_RES = 1, MODE_JAC = 2, MODE_ADD = 3, MODE_AX_DS = 4, MODE_RES_DS = 5, MODE_AX_J0 = 6 };
 // Y = f(A X) over columns [0,nb) of interleaved multivectors (leading dimension nb).
 //   pc: [nsys][nplanes_total] plane coefficients; column b uses row b / cps.
@@ -262,7 +262,7 @@ void launch_dense_assemble(const cplx *planes, int nplanes, int n, const cplx *p
 void launch_dense_invert(cplx *Ainv, int n, int nsys, int *status, hipStream_t s);
 void launch_dense_apply(const cplx *Ainv, int n, int cps, const cplx *X, cplx *Y, int nb, hipStream_t s, const unsigned char *cmask = nullptr);
 
-// vector kernels on interleaved multivectors [n][nb]
+// vector kernels on interleaved multivectors [n][nb] (vec.hip; the V-cycle transfers among them are in kernels.hip) -----------
 void launch_fill_zero(cplx *X, size_t count, hipStream_t s);
 void launch_copy(const cplx *X, cplx *Y, size_t count, hipStream_t s);
 // partial dots: out[i][b] = sum_rows conj(V_i[row][b]) * W[row][b], i = 0..nv-1; V_i = V + i*stride
@@ -310,7 +310,8 @@ void launch_mask_cols(cplx *X, const cplx *keep, int64_t n, int nb, hipStream_t 
 // Beyn accumulation: A[(p*lA+c0+c)*d + row] += sum_s w[s] z[s]^p X[row][s*l+c], s < nsys, p < npow  (lA columns in A; 0 = l)
 void launch_beyn_accum(const cplx *Xi, int nb, int64_t d, int l, int nsys, const cplx *w, const cplx *z, int npow, cplx *A, hipStream_t s,
                        int lA = 0, int c0 = 0, const int *perm = nullptr);
-// perturbation recurrence (nb systems interleaved; kernels.hip "Batched adjoint perturbation")
+// perturbation recurrence (nb systems interleaved; vec.hip "Batched adjoint perturbation", launch_pt_spmv_batch with the operator
+// kernels in kernels.hip)
 // U[row][t][b] = sum_{i<k} G[i][t][b] V_i[row][b], V_i = V + i*stride (interleaved blocks), G: [k][T][nb]; every V_i is read once
 void launch_pt_gemm_batch(const cplx *V, size_t stride, int k, const cplx *G, cplx *U, int64_t d, int T, int nb, hipStream_t s);
 // Y[row][b] (+)= sum_q pc[q] plane_q U[:, plane_col[q], b]  (U: [row][nin][nb]; pc shared by the systems)
@@ -320,7 +321,7 @@ void launch_pt_spmv_batch(const OpDev &op, const cplx *pc, const int *plane_col,
 void launch_pt_axpby_cols(const cplx *coef, const cplx *x, const cplx *y, cplx *out, int64_t d, int nb, hipStream_t s);
 // vk += (-dots[0][b] - 1/2 sum_{1<=j<nd} dots[j][b]) v0, per column
 void launch_pt_project(cplx *vk, const cplx *v0, const cplx *dots, int nd, int64_t d, int nb, hipStream_t s);
-// device-resident state of the lock-step GMRES recurrence (one thread per column, kernels.hip gmres_*_kernel)
+// device-resident state of the lock-step GMRES recurrence (one thread per column, vec.hip gmres_*_kernel)
 struct GmresDev {
     int nb, m, histcap;
     cplx *R;                // [m][m+1][nb]: rotated Hessenberg columns
@@ -341,7 +342,7 @@ struct GmresDev {
 void launch_gmres_init(const GmresDev &S, const cplx *beta, const unsigned char *done, int use_mask, hipStream_t s);
 void launch_gmres_step(const GmresDev &S, const cplx *hd, int j, double tol, double lim, int use_mask, cplx *Vnew, int64_t n, hipStream_t s,
                        const cplx *rn = nullptr);     // rn (optional): the norm of the new vector, instead of hd[j+1]
-// pair steps (two Arnoldi steps per pass over the basis; kernels.hip)
+// pair steps (two Arnoldi steps per pass over the basis; vec.hip)
 void launch_dots2_scaled(const cplx *V, size_t stride, int nv, const cplx *W1, const cplx *W2, int64_t n, int nb, cplx *partial, cplx *out1,
                          cplx *out2, cplx *gram_out, const cplx *scale, hipStream_t s, const unsigned char *cmask = nullptr);
 void launch_axpy2_norm(const cplx *V, size_t stride, int nv, const cplx *c1, const cplx *c2m, const cplx *alpha, cplx *W1, cplx *W2, int64_t n, int nb,
