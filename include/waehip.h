@@ -389,6 +389,43 @@ int wae_p1_shape_sensitivity_flame(int32_t device, int64_t npoints, const double
                                    const double *n_ref, const double *v, const double *v_adj, double h, double *det_pm, double *ssum,
                                    double *g_pm, double *g0);
 
+/* -- tall matrices: Beyn's eigenpair extraction on the device ------------------------------------------------------
+ * The step that turns the moments into eigenpairs (beyn.jl:76-107; `moments2eigs`, beyn.jl:289-323): block Hankel matrices
+ * B0, B1 of size (d K) x (l K), the thin SVD  B0 = U S W^H,  the small matrix  U^H B1 W S^-1,  its eigenpairs (Omega, Y), and
+ * P = U[1:d, :] Y.  Everything tall stays in HBM and runs in the library; the (l K) x (l K) problems stay with the host's
+ * LAPACK (Julia LinearAlgebra / numpy), the split the Arnoldi entries use.  The host wrappers build the SVD from Gram matrices
+ * by deflation in stages (julia/WAEHip.jl `moments2eigs_device`, nlevp/beyn.py `moments2eigs_native`).
+ * A wae_tall is a column-major rows x ncols ComplexF64 matrix in HBM with leading dimension = rows, in the caller's row
+ * numbering, owned by the library and independent of any family; host arrays are column-major, interleaved (re,im).
+ * The dev_ptr of wae_tall_info is what the caller passes as out_dev of wae_beyn_moments / wae_beyn_moments_rb (moments of
+ * d x l x 2K = a d x (l 2K) tall matrix: they never visit the host) and as P_dev of wae_eig_residuals (d x n).
+ * Calls that name one handle -- in any argument, `const` ones included: wae_tall_gram keeps its reduction scratch in `a` -- must be
+ * serialised by the caller, like calls on a family; calls on different handles may run from different threads.
+ * Every entry returns when its result is complete.  WAE_ERR_INVALID (nothing launched): null pointers, ranges outside a
+ * matrix, widths above WAE_TALL_MAXCOLS or below 0, matrices that differ in rows or device, shapes that do not fit
+ * wae_tall_hankel.  A call with a zero width (na, nb, ns, nc, nrows or ncols = 0) is a no-op: WAE_OK.
+ *   create   zero-filled.  write / read: the block rows row0 .. row0+nrows-1, columns col0 .. col0+ncols-1 from / to
+ *            X (nrows x ncols, host).
+ *   gram     G (na x nb, host) = A[:, a_col0 .. +na)^H B[:, b_col0 .. +nb);  A and B on one device, same rows; a == b allowed.
+ *            Summed in two stages in a fixed order (no atomics): two identical calls return identical bits.
+ *   mul      dst[r, dst_col0+j] = beta dst[r, dst_col0+j] + alpha sum_i src[src_row0+r, src_col0+i] C[i,j]  for r < rows of
+ *            dst, j < nc;  C: ns x nc on the host; alpha, beta: one complex number each; needs src_row0 + rows of dst <= rows of
+ *            src.  dst and src may be one matrix if the two column ranges do not overlap (WAE_ERR_INVALID if they do).
+ *            beta = 0: dst is not read (NaNs there do not propagate).
+ *   hankel   from a moment tensor kept as a d x (l 2K) tall matrix (the layout wae_beyn_moments writes), dst (d K) x (l K):
+ *            dst[i d + r, j l + c] = moments[r, (i+j+shift) l + c],  shift = 0 (B0) or 1 (B1)   (beyn.jl:76-90) */
+typedef struct wae_tall wae_tall;
+#define WAE_TALL_MAXCOLS 64     /* widest block one gram / mul call takes; the wrappers loop over blocks */
+int wae_tall_create (wae_tall **out, int32_t device, int64_t rows, int32_t ncols);
+int wae_tall_destroy(wae_tall *m);
+int wae_tall_info   (const wae_tall *m, int64_t *rows, int32_t *ncols, uint64_t *dev_ptr);
+int wae_tall_write  (wae_tall *m, int64_t row0, int64_t nrows, int32_t col0, int32_t ncols, const double *X);
+int wae_tall_read   (const wae_tall *m, int64_t row0, int64_t nrows, int32_t col0, int32_t ncols, double *X);
+int wae_tall_gram(const wae_tall *a, int32_t a_col0, int32_t na, const wae_tall *b, int32_t b_col0, int32_t nb, double *G_out);
+int wae_tall_mul(wae_tall *dst, int32_t dst_col0, const wae_tall *src, int64_t src_row0, int32_t src_col0, int32_t ns,
+                 const double *C, int32_t nc, const double *alpha, const double *beta);
+int wae_tall_hankel(wae_tall *dst, const wae_tall *moments, int32_t l, int32_t K, int32_t shift);
+
 /* -- measurement helpers (bench.py) --------------------------------------------------------------------
  * Time `reps` launches of the fused multi-term SpMV on device-resident data with HIP events on the
  * library's own stream; r right-hand sides.  ms_out = average milliseconds per launch. */

@@ -60,6 +60,7 @@ mutable struct DeviceFamily
     solver_ready::Bool
     tol::Float64
     maxit::Int32
+    device::Int                      # HIP device ordinal the terms live on (tall matrices of `beyn(...; device_tail=true)` go there too)
     # symmetry_tol: opts[0] of wae_family_create_opts.  0 (default): `A'` is exactly `A'` -- a term is applied un-transposed for
     # A'*y / A'\\b only if it is bitwise symmetric.  Families from `discretize` (M, K, C symmetric by construction, assembled in floating
     # point) should pass 1e-14: their adjoint products then take the forward path (include/waehip.h).
@@ -82,7 +83,7 @@ mutable struct DeviceFamily
                             h, d, T, 4, 1, 0 #=WAE_CSC=#, ptrs, idxs, vals, device, opts, length(opts)))
             end
         end
-        fam = new(L, h[], false, tol, maxit)
+        fam = new(L, h[], false, tol, maxit, Int(device))
         finalizer(f -> (f.handle != C_NULL && ccall((:wae_family_destroy, libwaehip), Cint, (Ptr{Cvoid},), f.handle); f.handle = C_NULL), fam)
         return fam
     end
@@ -230,8 +231,9 @@ function _snapshot_split(n::Int, rb::Int)
 end
 
 "moments of beyn.jl:62-74 / compute_moment_matrices (beyn.jl:251-268) on the device; `rb` = number of snapshot points
-for projected initial guesses (wae_beyn_moments_rb; default 40 for contours of at least 64 points)"
-function compute_moment_matrices(fam::DeviceFamily, Γ, V::Matrix{ComplexF64}; K=1, N=16, rb=nothing)
+for projected initial guesses (wae_beyn_moments_rb; default 40 for contours of at least 64 points); `out_dev` = `tall_ptr` of a
+d x (l 2K) TallMatrix: the moments are left there instead of being copied to the host (returns `nothing`)"
+function compute_moment_matrices(fam::DeviceFamily, Γ, V::Matrix{ComplexF64}; K=1, N=16, rb=nothing, out_dev::UInt64=UInt64(0))
     ensure_solver!(fam)
     L = fam.L
     X, W = FastGaussQuadrature.gausslegendre(N)
@@ -246,37 +248,57 @@ function compute_moment_matrices(fam::DeviceFamily, Γ, V::Matrix{ComplexF64}; K
     for (j, z) in enumerate(zs); ct[:, j] = coefficients(L, z); end
     L.active, L.mode = saved
     d, l = size(V)
-    A = zeros(ComplexF64, d, l, 2K); info = Ref{SolveInfo}()
+    dev = out_dev != 0
+    A = dev ? C_NULL : zeros(ComplexF64, d, l, 2K); info = Ref{SolveInfo}()
     npts = length(zs)
     rb === nothing && (rb = (npts >= 64 && d >= 1000) ? min(40, div(npts, 2)) : 0)
     if rb == 0 || npts < 2rb
         check(ccall((:wae_beyn_moments, libwaehip), Cint,
                     (Ptr{Cvoid}, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Int32, Int32, Float64, Int32,
                      Ptr{ComplexF64}, UInt64, Ref{SolveInfo}),
-                    fam.handle, npts, zs, ws, ct, V, l, K, fam.tol, fam.maxit, A, 0, info))
+                    fam.handle, npts, zs, ws, ct, V, l, K, fam.tol, fam.maxit, A, out_dev, info))
         report(0, info[], "beyn moments"; fatal=true)
-        return A
+        return dev ? nothing : A
     end
     idx, rest = _snapshot_split(npts, rb)
-    A1 = zeros(ComplexF64, d, l, 2K)
+    A1 = dev ? C_NULL : zeros(ComplexF64, d, l, 2K)
     sig = (Ptr{Cvoid}, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Int32, Int32, Float64, Int32,
            Int32, Int32, Int32, UInt64, Ptr{ComplexF64}, UInt64, Int32, Int32, Int32, Ref{SolveInfo})
     # mode 0: the snapshot points (solutions kept in the handle's store); mode 2: all other points from the projection
     check(ccall((:wae_beyn_moments_rb, libwaehip), Cint, sig, fam.handle, length(idx), zs[idx], ws[idx], ct[:, idx], V, l, K,
-                fam.tol, fam.maxit, 0, length(idx), 0, 0, A, 0, 0, 0, 0, info))
+                fam.tol, fam.maxit, 0, length(idx), 0, 0, A, out_dev, 0, 0, 0, info))
     report(0, info[], "beyn moments (snapshot points)"; fatal=true)
     # V = C_NULL: the probe matrix uploaded by the mode-0 call is still on the device (include/waehip.h)
     check(ccall((:wae_beyn_moments_rb, libwaehip), Cint, sig, fam.handle, length(rest), zs[rest], ws[rest], ct[:, rest], C_NULL, l, K,
-                fam.tol, fam.maxit, 2, length(idx), 0, 0, A1, 0, 0, 0, 0, info))
+                fam.tol, fam.maxit, 2, length(idx), 0, 0, A1, out_dev, dev ? 1 : 0, 0, 0, info))     # (device: accumulate)
     report(0, info[], "beyn moments (projected points)"; fatal=true)
-    return A .+ A1                                                  # the moments are a plain sum over quadrature points
+    return dev ? nothing : A .+ A1                                  # the moments are a plain sum over quadrature points
 end
 
-"Ω, P = beyn(Ld, Γ; l, K, N, tol, pos_test) -- src/NLEVP/beyn.jl:34-110 with the quadrature loop on the GPU"
-function beyn(fam::DeviceFamily, Γ; l=5, K=1, N=16, tol=0.0, pos_test=true)
+"Ω, P = beyn(Ld, Γ; l, K, N, tol, pos_test) -- src/NLEVP/beyn.jl:34-110 with the quadrature loop on the GPU.
+`device_tail=true`: the moments stay in HBM (a TallMatrix on the family's device) and the eigenpairs are extracted there
+(`moments2eigs_device`, singular directions above `rel_tol` σ₁); only the eigenvectors that pass `pos_test` are copied back."
+function beyn(fam::DeviceFamily, Γ; l=5, K=1, N=16, tol=0.0, pos_test=true, device_tail::Bool=false, rel_tol::Float64=1e-6)
     d = size(fam.L.terms[1].coeff, 1)
     K = max(K, div(l, d) + Int(mod(l, d) != 0))
     V = zeros(ComplexF64, d, l); for i in 1:min(d, l); V[i, i] = 1; end
+    if device_tail
+        M = TallMatrix(d, l * 2K; device=fam.device)
+        try
+            compute_moment_matrices(fam, Γ, V; K=K, N=N, out_dev=tall_ptr(M))
+            Ω, Pd, _ = moments2eigs_device(M, d, l, K; rel_tol=rel_tol)
+            try
+                keep = pos_test ? findall(z -> inpoly(z, Γ), Ω) : collect(1:length(Ω))
+                P = Matrix{ComplexF64}(undef, d, length(keep))
+                for (j, c) in enumerate(keep); P[:, j] = tall_read(Pd; cols=c:c); end
+                return Ω[keep], P
+            finally
+                destroy!(Pd)
+            end
+        finally
+            destroy!(M)
+        end
+    end
     A = compute_moment_matrices(fam, Γ, V; K=K, N=N)
     B = Array{ComplexF64}(undef, d * K, l * K, 2)
     for i in 0:K-1, j in 0:K-1
@@ -1172,6 +1194,143 @@ function solve_batched(fam::DeviceFamily, Γ; Δl=1, N=16, tol=1e-8, eigvals=Dic
         (!found_new && sum(keep) < l) && break                         # rank gap reached and nothing new: done (solver.jl:172)
     end
     return eigvals
+end
+
+# -- tall matrices in HBM and Beyn's eigenpair extraction on them (include/waehip.h "tall matrices"; beyn.jl:76-107,289-323) --------
+# Column and row arguments are 1-based ranges here; the library's are 0-based offsets and counts.
+const TALL_MAXCOLS = 64
+
+"a column-major rows x ncols ComplexF64 matrix in HBM, owned by the library (wae_tall_create / wae_tall_destroy)"
+mutable struct TallMatrix
+    handle::Ptr{Cvoid}
+    rows::Int
+    ncols::Int
+    device::Int
+    function TallMatrix(rows::Integer, ncols::Integer; device::Integer=0)
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:wae_tall_create, libwaehip), Cint, (Ref{Ptr{Cvoid}}, Int32, Int64, Int32), h, device, rows, ncols))
+        m = new(h[], rows, ncols, device)
+        finalizer(x -> (x.handle != C_NULL && ccall((:wae_tall_destroy, libwaehip), Cint, (Ptr{Cvoid},), x.handle); x.handle = C_NULL), m)
+        return m
+    end
+end
+
+"free the HBM of a TallMatrix now (wae_tall_destroy): the garbage collector does not see device memory, so code that makes tall
+temporaries frees them itself; the finalizer is only the safety net.  Idempotent."
+function destroy!(m::TallMatrix)
+    if m.handle != C_NULL
+        ccall((:wae_tall_destroy, libwaehip), Cint, (Ptr{Cvoid},), m.handle); m.handle = C_NULL
+    end
+    return nothing
+end
+
+"raw device address of the matrix: `out_dev` of the moment integrals, `P_dev` of wae_eig_residuals"
+function tall_ptr(m::TallMatrix)
+    p = Ref{UInt64}(0)
+    check(ccall((:wae_tall_info, libwaehip), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ref{UInt64}), m.handle, C_NULL, C_NULL, p))
+    return p[]
+end
+
+function tall_write(m::TallMatrix, X::Matrix{ComplexF64}; row0::Integer=1, col0::Integer=1)
+    check(ccall((:wae_tall_write, libwaehip), Cint, (Ptr{Cvoid}, Int64, Int64, Int32, Int32, Ptr{ComplexF64}),
+                m.handle, row0 - 1, size(X, 1), col0 - 1, size(X, 2), X))
+    return m
+end
+
+function tall_read(m::TallMatrix; rows::UnitRange{Int}=1:m.rows, cols::UnitRange{Int}=1:m.ncols)
+    X = Matrix{ComplexF64}(undef, length(rows), length(cols))
+    check(ccall((:wae_tall_read, libwaehip), Cint, (Ptr{Cvoid}, Int64, Int64, Int32, Int32, Ptr{ComplexF64}),
+                m.handle, first(rows) - 1, length(rows), first(cols) - 1, length(cols), X))
+    return X
+end
+
+"A[:, acols]' * B[:, bcols] (host matrix), in blocks of TALL_MAXCOLS columns"
+function tall_gram(A::TallMatrix, B::TallMatrix; acols::UnitRange{Int}=1:A.ncols, bcols::UnitRange{Int}=1:B.ncols)
+    G = Matrix{ComplexF64}(undef, length(acols), length(bcols))
+    for i0 in 0:TALL_MAXCOLS:length(acols)-1, j0 in 0:TALL_MAXCOLS:length(bcols)-1
+        wi = min(TALL_MAXCOLS, length(acols) - i0); wj = min(TALL_MAXCOLS, length(bcols) - j0)
+        blk = Matrix{ComplexF64}(undef, wi, wj)
+        check(ccall((:wae_tall_gram, libwaehip), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int32, Int32, Ptr{ComplexF64}),
+                    A.handle, first(acols) - 1 + i0, wi, B.handle, first(bcols) - 1 + j0, wj, blk))
+        G[i0+1:i0+wi, j0+1:j0+wj] = blk
+    end
+    return G
+end
+
+"dst[:, dst_col0 .+ (0:nc-1)] = beta * dst[...] + alpha * src[src_row0 .+ (0:rows-1), src_col0 .+ (0:ns-1)] * C   (C: ns x nc, host)"
+function tall_mul!(dst::TallMatrix, src::TallMatrix, C::AbstractMatrix; dst_col0::Integer=1, src_col0::Integer=1, src_row0::Integer=1, alpha=1, beta=0)
+    Cm = Matrix{ComplexF64}(C); ns, nc = size(Cm)
+    for j0 in 0:TALL_MAXCOLS:nc-1
+        wj = min(TALL_MAXCOLS, nc - j0); be = ComplexF64(beta)
+        for i0 in 0:TALL_MAXCOLS:ns-1
+            wi = min(TALL_MAXCOLS, ns - i0); blk = Cm[i0+1:i0+wi, j0+1:j0+wj]
+            check(ccall((:wae_tall_mul, libwaehip), Cint,
+                        (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{ComplexF64}, Int32, Ref{ComplexF64}, Ref{ComplexF64}),
+                        dst.handle, dst_col0 - 1 + j0, src.handle, src_row0 - 1, src_col0 - 1 + i0, wi, blk, wj, Ref(ComplexF64(alpha)), Ref(be)))
+            be = ComplexF64(1)
+        end
+    end
+    return dst
+end
+
+"dst (d K) x (l K) = block Hankel matrix of the d x (l 2K) moments: shift 0 -> B0, 1 -> B1 (beyn.jl:76-90)"
+function tall_hankel!(dst::TallMatrix, moments::TallMatrix, l::Integer, K::Integer, shift::Integer)
+    check(ccall((:wae_tall_hankel, libwaehip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32), dst.handle, moments.handle, l, K, shift))
+    return dst
+end
+
+"Ω, P (TallMatrix d x kept), Σ = moments2eigs_device(M, d, l, K; rel_tol): `moments2eigs` (beyn.jl:289-323) on moments that stay in HBM.
+The thin SVD of B0 comes from Gram matrices by deflation in stages of six decades (each kept block made orthonormal by a second
+Cholesky-QR pass), then the exact SVD of U' B0 for the kept group; `eigen` / `svd` run on (l K) x (l K) matrices only.  Singular
+directions above rel_tol σ₁ are kept (0: all); Σ lists all l K singular values.  K = 1: B0, B1 are column ranges of M, nothing is copied."
+function moments2eigs_device(M::TallMatrix, d::Integer, l::Integer, K::Integer; rel_tol::Float64=1e-6)
+    n = l * K; R = d * K; dev = M.device
+    tmp = TallMatrix[]                                   # every tall temporary, freed on the way out (P is handed to the caller)
+    scratch(r, c) = (t = TallMatrix(r, c; device=dev); push!(tmp, t); t)
+    try
+        B0, c0, B1, c1 = M, 1, M, l + 1
+        if K > 1
+            B0 = tall_hankel!(scratch(R, n), M, l, K, 0); B1 = tall_hankel!(scratch(R, n), M, l, K, 1); c1 = 1
+        end
+        rest, rc, own = B0, c0, false
+        blocks = TallMatrix[]; s_top = 0.0; S = Float64[]
+        for _ in 1:8
+            G = tall_gram(rest, rest; acols=rc:rc+n-1, bcols=rc:rc+n-1)
+            F = eigen(Hermitian((G + G') / 2)); S = sqrt.(max.(reverse(F.values), 0.0)); W = F.vectors[:, end:-1:1]
+            isempty(blocks) && (s_top = S[1])
+            nkept = sum(Int[b.ncols for b in blocks])
+            (S[1] <= rel_tol * s_top || S[1] == 0.0 || nkept >= n) && break
+            k = min(count(x -> x > max(rel_tol * s_top, 1e-6 * S[1]), S), n - nkept)
+            U = tall_mul!(scratch(R, k), rest, W[:, 1:k] * Diagonal(1 ./ S[1:k]); src_col0=rc)
+            for Ub in blocks; tall_mul!(U, Ub, tall_gram(Ub, U); alpha=-1, beta=1); end      # rounding left along the earlier blocks
+            G2 = tall_gram(U, U); F2 = eigen(Hermitian((G2 + G2') / 2))
+            U2 = tall_mul!(scratch(R, k), U, F2.vectors * Diagonal(1 ./ sqrt.(F2.values)) * F2.vectors')
+            destroy!(U)
+            push!(blocks, U2)
+            Cm = tall_gram(U2, rest; bcols=rc:rc+n-1)
+            if !own                                                                          # B0 itself is needed again below
+                rest = tall_mul!(scratch(R, n), rest, Matrix{ComplexF64}(I, n, n); src_col0=rc); rc = 1; own = true
+            end
+            tall_mul!(rest, U2, Cm; alpha=-1, beta=1)
+        end
+        isempty(blocks) && error("moments2eigs_device: the moment matrix is zero")
+        own && destroy!(rest)
+        UhB0 = reduce(vcat, [tall_gram(Ub, B0; bcols=c0:c0+n-1) for Ub in blocks])
+        UhB1 = reduce(vcat, [tall_gram(Ub, B1; bcols=c1:c1+n-1) for Ub in blocks])
+        F = svd(UhB0); ktot = size(UhB0, 1)
+        Ω, Y = eigen(F.U' * UhB1 * F.V * Diagonal(1 ./ F.S))
+        P = TallMatrix(d, ktot; device=dev); r0 = 0
+        try
+            for (i, Ub) in enumerate(blocks)
+                tall_mul!(P, Ub, F.U[r0+1:r0+Ub.ncols, :] * Y; beta=(i == 1 ? 0 : 1)); r0 += Ub.ncols
+            end
+        catch
+            destroy!(P); rethrow()
+        end
+        return Ω, P, vcat(F.S, S[1:n-ktot])
+    finally
+        foreach(destroy!, tmp)
+    end
 end
 
 # ---------------------------------------------------------------------------------------------------------------

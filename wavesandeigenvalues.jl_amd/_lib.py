@@ -37,7 +37,9 @@ EXPORTS = [
     "wae_last_error", "wae_device_count", "wae_version", "wae_family_create", "wae_family_create_opts", "wae_family_destroy",
     "wae_family_info", "wae_family_spmv_bytes", "wae_spmv_sum", "wae_spmv_sum_cols", "wae_spmv_sum_multi", "wae_solver_setup",
     "wae_solve", "wae_solve_guess", "wae_beyn_moments", "wae_beyn_moments_mgpu", "wae_beyn_moments_rb", "wae_rb_export", "wae_rb_import", "wae_eig_residuals", "wae_arnoldi_shiftinvert", "wae_arnoldi_shiftinvert_batch", "wae_perturb", "wae_slot_write", "wae_slot_read", "wae_slot_axpby", "wae_slot_forms", "wae_arnoldi_shiftinvert_slots", "wae_arnoldi_ritz_to_slot", "wae_perturb_slots", "wae_perturb_batch", "wae_perturb_batch_slots", "wae_p1_assemble", "wae_p1_assemble_boundary", "wae_p1_assemble_flame", "wae_p1_info", "wae_p1_get", "wae_p1_free", "wae_p1_shape_sensitivity", "wae_p1_shape_sensitivity_flame", "wae_bench_spmv", "wae_bench_spmv_level", "wae_bench_triad", "wae_debug_spmv", "wae_debug_vec",
+    "wae_tall_create", "wae_tall_destroy", "wae_tall_info", "wae_tall_write", "wae_tall_read", "wae_tall_gram", "wae_tall_mul", "wae_tall_hankel",
 ]
+TALL_MAXCOLS = 64           # WAE_TALL_MAXCOLS
 
 # operation codes of wae_debug_vec (include/waehip.h WAE_VEC_*)
 (VEC_DOTS, VEC_NORMS, VEC_DOTS_MULTI, VEC_AXPY_NEG, VEC_LINCOMB, VEC_LINCOMB_ADD, VEC_AXPY_NEG_NORM, VEC_AXPY_NEG_MULTI, VEC_DOTS2, VEC_AXPY2,
@@ -125,6 +127,14 @@ def lib():
                                  C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.wae_debug_vec.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.c_int32,
                                 C.POINTER(C.c_uint8), ip, ip]
+    L.wae_tall_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32]
+    L.wae_tall_destroy.argtypes = [C.c_void_p]
+    L.wae_tall_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+    L.wae_tall_write.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, dp]
+    L.wae_tall_read.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, dp]
+    L.wae_tall_gram.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, dp]
+    L.wae_tall_mul.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, dp, C.c_int32, dp, dp]
+    L.wae_tall_hankel.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     _lib = L
     return L
 

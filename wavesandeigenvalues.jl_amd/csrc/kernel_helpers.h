@@ -1,5 +1,5 @@
-// One-line device helpers and launch arithmetic shared by kernels.hip (operator, transfer, dense level) and vec.hip (vector kernels).
-// Private to those two files; nothing else belongs here.
+// One-line device helpers and launch arithmetic shared by kernels.hip (operator, transfer, dense level), vec.hip (vector kernels) and
+// tall.hip (tall matrices).  Private to those files; nothing else belongs here.
 #pragma once
 #include <algorithm>
 #include <mutex>

@@ -3,7 +3,8 @@
 The quadrature loop -- ``length(Γ)·N`` times {assemble L(z), sparse LU, l solves} in the reference
 (beyn.jl:62-74,112-138) -- is ONE call into libwaehip (``wae_beyn_moments``): all quadrature points and probe
 columns are solved in lock-step batches by multigrid-GMRES and the moments are accumulated in HBM.  The small
-dense tail (block Hankel SVD + eigen, beyn.jl:76-107) stays on the host, as in the reference (LAPACK).
+dense tail (block Hankel SVD + eigen, beyn.jl:76-107) stays on the host, as in the reference (LAPACK) -- or, with
+`moments2eigs_native` / `beyn_native`, keeps its tall half in HBM too (wae_tall_*) and only the (lK x lK) problems on the host.
 """
 from __future__ import annotations
 
@@ -189,6 +190,63 @@ def beyn(L, G, l=5, K=1, N=16, tol=0.0, pos_test_=True, output=False, random=Fal
     if pos_test_:
         Om, P = pos_test(Om, P, G)
     return (Om, P, S) if return_sigma else (Om, P)
+
+
+def moments2eigs_native(M, shape, tol_sigma=0.0, rel_tol=0.0, info=None):
+    """`moments2eigs` (beyn.jl:289-323) with everything tall kept in HBM behind the C ABI (``wae_tall_*``): no torch, only the
+    (lK x lK) problems run on the host (numpy).  M: a TallMatrix holding the d x (l 2K) moments (what ``out_dev=M.ptr`` of
+    ``compute_moment_matrices`` leaves there), or a host array d x l x 2K that is uploaded.  shape = (d, l, 2K).
+    rel_tol > 0 keeps the singular directions above rel_tol sigma_1 (the reference's `tol`, beyn.jl:92-95, relative), rel_tol = 0
+    all of them; tol_sigma > 0 is the reference's absolute threshold on top.  For K = 1, B0 and B1 are column ranges of M itself:
+    nothing is copied.  Returns (Omega, P as TallMatrix d x kept, Sigma of all l K directions); see tall.staged_extract."""
+    from .tall import TallMatrix, staged_extract
+    d, l, K2 = (int(v) for v in shape)
+    K = K2 // 2
+    uploaded = not hasattr(M, "gram")
+    if uploaded:
+        M = TallMatrix.from_host(np.asarray(M, dtype=np.complex128).reshape(d, l * K2, order="F"))
+    if M.rows != d or M.ncols != l * K2:
+        raise ValueError(f"moments2eigs_native: M is {M.rows} x {M.ncols}, shape says {d} x {l * K2}")
+    n = l * K
+    try:
+        if K == 1:
+            return staged_extract(M, 0, M, l, d, n, rel_tol=rel_tol, tol_sigma=tol_sigma, info=info)
+        B0 = M.new(d * K, n).hankel(M, l, K, 0)
+        B1 = M.new(d * K, n).hankel(M, l, K, 1)
+        try:
+            return staged_extract(B0, 0, B1, 0, d, n, rel_tol=rel_tol, tol_sigma=tol_sigma, info=info)
+        finally:
+            B0.release()
+            B1.release()
+    finally:
+        if uploaded:
+            M.destroy()
+
+
+def beyn_native(L, G, l=5, K=1, N=16, rel_tol=1e-6, pos_test_=True):
+    """`beyn` (beyn.jl:34-110) without a host copy of anything tall: the moments are written into a TallMatrix, the eigenpairs are
+    extracted there (`moments2eigs_native`), the residual test of the pairs inside the contour reads P in HBM, and only those n
+    eigenvectors come back.  Returns (Omega, P (d x n, numpy), Sigma, residuals of wae_eig_residuals)."""
+    from .tall import TallMatrix
+    d = L.size()
+    K = max(K, l // d + int(l % d != 0))
+    M = TallMatrix.create(d, l * 2 * K, device=L.device_id)
+    try:
+        compute_moment_matrices(L, G, initialize_V(d, l), K=K, N=N, out_dev=M.ptr)
+        Om, P, S = moments2eigs_native(M, (d, l, 2 * K), rel_tol=rel_tol)
+    finally:
+        M.destroy()
+    keep = np.array([inpoly(z, G) for z in Om], dtype=bool) if pos_test_ else np.ones(len(Om), dtype=bool)
+    Om = Om[keep]
+    if len(Om) == 0:
+        P.release()
+        return Om, np.zeros((d, 0), dtype=np.complex128), S, np.zeros(0)
+    Pk = P.new(d, len(Om)).mul(P, np.eye(P.ncols)[:, keep])         # the kept columns, contiguous: the layout P_dev wants
+    P.release()
+    res = L.ensure_solver().eig_residuals(coefficient_table(L, Om), P_dev=Pk.ptr)
+    Ph = Pk.to_host()
+    Pk.release()
+    return Om, Ph, S, res
 
 
 # ------------------------------------------------------------------------------------------------------
