@@ -362,6 +362,38 @@ int wae_p1_assemble_flame(int32_t device, int64_t npoints, const double *points,
 int wae_p1_info(const void *handle, int64_t *npoints, int64_t *nnz);
 int wae_p1_get(const void *handle, int32_t *rowptr, int32_t *col, double *mass, double *stiff);
 int wae_p1_free(void *handle);
+/* -- P2 (second-order) assembly on the device: `discretize(...; order=:quad)` ----------------------------------------
+ * Edge numbering (replaces aggregate_elements, src/FEM/FEM.jl:84-116, with collect_lines!, Meshutils.jl:831-840): one DoF per
+ * unique mesh edge, DoF of edge e = npoints + e, the edges sorted by (smaller point, larger point) -- the reference's order for
+ * meshes whose simplices list their points in ascending order.  Edge keys, radix sort, unique pass and the binary searches run on
+ * the device.  Local node order, as in the reference: tetrahedron = its 4 points, then the edges (1,2), (1,3), (1,4), (2,3), (2,4),
+ * (3,4); triangle = its 3 points, then the edges (1,2), (1,3), (2,3).  tets: 4 point indices (0-based) per tetrahedron, tris: 3 per
+ * boundary triangle (ntris may be 0, tris NULL).  wae_p2_connectivity returns a handle, wae_p2_connectivity_info the sizes,
+ * wae_p2_connectivity_get copies out edges[2*nedges], tets10[10*ntets], tris6[6*ntris] (0-based; any pointer may be NULL),
+ * wae_p2_connectivity_free releases it.  WAE_ERR_INVALID: an index outside 0..npoints-1, a triangle edge that is no tetrahedron's
+ * edge, or a mesh with 100*ntets or 36*ntris beyond a 32-bit count (the limit of the assembly below; nothing is truncated). */
+int wae_p2_connectivity(int32_t device, int64_t npoints, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris, void **out);
+int wae_p2_connectivity_info(const void *handle, int64_t *nedges, int64_t *ntets, int64_t *ntris);
+int wae_p2_connectivity_get(const void *handle, int32_t *edges, int32_t *tets10, int32_t *tris6);
+int wae_p2_connectivity_free(void *handle);
+/* The three operators on the P2 space, basis phi_i = l_i (2 l_i - 1) on the points and phi_ij = 4 l_i l_j on the edges (l:
+ * barycentric coordinates), node order and numbering as above.  Each entry takes the plain mesh, numbers the edges itself and
+ * returns the handle type of the P1 entries (wae_p1_info / wae_p1_get / wae_p1_free) with npoints + nedges rows; same pipeline:
+ * triplets sorted and summed on the device, deterministic, no atomics.
+ *  - interior (src/Helmholtz.jl:120-149,405-441 with the element matrices s43v2u2 / s43nv2nu2, FEM.jl:726-738,1768-):
+ *        M_ab += |det J| int phi_a phi_b,      K_ab += -c_tet^2 |det J| int grad(phi_a).grad(phi_b)     (c_tet NULL = 1)
+ *  - admittance boundary (Helmholtz.jl:151-170,443-463 with s33v2u2, FEM.jl:442-450): b_ab = c_tri |(x0-x2) x (x1-x2)| int phi_a phi_b
+ *    on the 6-node triangle; the operator term is C = -i b.  The tetrahedra are needed for the edge numbers.
+ *  - flame (Helmholtz.jl:292-344,464-487 with s43v2 / s43nv2rx, FEM.jl:2433-2435,2450-2484): Q = sum over the flame tetrahedra of
+ *    S (x) g,  S_a = |det J| int phi_a (-|det J|/120 on points, |det J|/30 on edges),  g_b = -nlocal grad(phi_b)(x_ref).n_ref on the 10
+ *    nodes of the reference tetrahedron, nlocal = nglobal_scaled / V_flame.  Unlike P1 the gradients depend on where x_ref (3
+ *    doubles) lies inside ref_tet.  The flame volume is returned in volume_out if not NULL. */
+int wae_p2_assemble(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_tet, void **out);
+int wae_p2_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                             const int32_t *tris, const double *c_tri, void **out);
+int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t nflame,
+                          const int32_t *flame_tets, int32_t ref_tet, const double *x_ref, const double *n_ref, double nglobal_scaled, void **out,
+                          double *volume_out);
 /* Discrete-adjoint shape sensitivity (src/shape_sensitivity.jl:16-141) of an eigenvalue w.r.t. the coordinates of surface
  * points, for the interior (M, K) and the admittance-boundary (w*Y*C) parts of the P1 Helmholtz operator.  As in the
  * reference the operator derivative is a central difference (step h) of two local re-discretisations of the simplices

@@ -1408,6 +1408,74 @@ function assemble_p1_flame(points::Matrix{Float64}, tets::AbstractMatrix{<:Integ
     return _take_p1(h[], false), vol[]
 end
 
+# P2 (second-order) elements, `discretize(...; order=:quad)`: edge DoFs numbered on the device (aggregate_elements, FEM.jl:84-116) and the
+# three operators on the 10-node tetrahedra / 6-node triangles.  Arguments as for the P1 wrappers (1-based indices in, 1-based out).
+"edges (2 x nedges), tets10 (10 x ntet), tris6 (6 x ntri) = p2_connectivity(npoints, tets[, tris]; device): DoF of edge e = npoints + e, the
+edges sorted by (smaller point, larger point); local order: the points, then the edges (1,2), (1,3), (1,4), (2,3), (2,4), (3,4) resp. (1,2), (1,3), (2,3)"
+function p2_connectivity(npoints::Integer, tets::AbstractMatrix{<:Integer}, tris::Union{Nothing,AbstractMatrix{<:Integer}}=nothing; device::Integer=0)
+    t0 = _zero_based(tets); s0 = tris === nothing ? zeros(Int32, 3, 0) : _zero_based(tris); h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:wae_p2_connectivity, libwaehip), Cint, (Int32, Int64, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ref{Ptr{Cvoid}}),
+                device, npoints, size(t0, 2), t0, size(s0, 2), size(s0, 2) == 0 ? C_NULL : s0, h))
+    try
+        ne = Ref{Int64}(0); nt = Ref{Int64}(0); ns = Ref{Int64}(0)
+        check(ccall((:wae_p2_connectivity_info, libwaehip), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], ne, nt, ns))
+        edges = zeros(Int32, 2, ne[]); t10 = zeros(Int32, 10, nt[]); t6 = zeros(Int32, 6, ns[])
+        check(ccall((:wae_p2_connectivity_get, libwaehip), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), h[], edges, t10, t6))
+        return edges .+ Int32(1), t10 .+ Int32(1), t6 .+ Int32(1)
+    finally
+        ccall((:wae_p2_connectivity_free, libwaehip), Cint, (Ptr{Cvoid},), h[])
+    end
+end
+
+"M, K = assemble_p2(points, tets; c_tet, device): P2 mass and stiffness (Helmholtz.jl:120-149,405-441 with order=:quad), size npoints + nedges"
+function assemble_p2(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; c_tet=nothing, device::Integer=0)
+    t0 = _zero_based(tets); h = Ref{Ptr{Cvoid}}(C_NULL)
+    cc = c_tet === nothing ? C_NULL : Vector{Float64}(c_tet)
+    check(ccall((:wae_p2_assemble, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                device, size(points, 2), points, size(t0, 2), t0, cc, h))
+    return _take_p1(h[], true)
+end
+
+"C = assemble_p2_boundary(points, tets, tris; c_tri, device): P2 admittance-boundary operator -i c |e1×e2| ∫φ_aφ_b (Helmholtz.jl:151-170,443-463)"
+function assemble_p2_boundary(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, tris::AbstractMatrix{<:Integer}; c_tri=nothing, device::Integer=0)
+    t0 = _zero_based(tets); s0 = _zero_based(tris); h = Ref{Ptr{Cvoid}}(C_NULL)
+    cc = c_tri === nothing ? C_NULL : Vector{Float64}(c_tri)
+    check(ccall((:wae_p2_assemble_boundary, libwaehip), Cint,
+                (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                device, size(points, 2), points, size(t0, 2), t0, size(s0, 2), s0, cc, h))
+    return -1im .* _take_p1(h[], false)
+end
+
+"Q, V_flame = assemble_p2_flame(points, tets, flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled; device): P2 flame operator Q = Σ_flame S ⊗ g
+(Helmholtz.jl:292-344,464-487); as assemble_p1_flame, and x_ref, the reference point inside ref_tet where the gradients are taken"
+function assemble_p2_flame(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, flame_tets::AbstractVector{<:Integer}, ref_tet::Integer,
+                           x_ref::Vector{Float64}, n_ref::Vector{Float64}, nglobal_scaled::Real; device::Integer=0)
+    t0 = _zero_based(tets); fl = Vector{Int32}(flame_tets) .- Int32(1); h = Ref{Ptr{Cvoid}}(C_NULL); vol = Ref{Float64}(0.0)
+    check(ccall((:wae_p2_assemble_flame, libwaehip), Cint,
+                (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Ref{Ptr{Cvoid}}, Ref{Float64}),
+                device, size(points, 2), points, size(t0, 2), t0, length(fl), fl, ref_tet - 1, x_ref, n_ref, Float64(nglobal_scaled), h, vol))
+    return _take_p1(h[], false), vol[]
+end
+
+"M, K, C, Q, V_flame = discretize_device(points, tets; order, c_tet, bnd_tris, bnd_c, flame): the term matrices of `discretize` assembled on the
+device, order = :lin or :quad (Helmholtz.jl:36-54).  bnd_tris / bnd_c: admittance-boundary triangles and the speed of sound behind each;
+flame = (flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled).  Terms that were not asked for come back as `nothing`."
+function discretize_device(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; order::Symbol=:lin, c_tet=nothing, bnd_tris=nothing,
+                           bnd_c=nothing, flame=nothing, device::Integer=0)
+    order in (:lin, :quad) || error("discretize_device: order must be :lin or :quad")
+    quad = order == :quad
+    M, K = quad ? assemble_p2(points, tets; c_tet=c_tet, device=device) : assemble_p1(points, tets; c_tet=c_tet, device=device)
+    C = bnd_tris === nothing ? nothing :
+        quad ? assemble_p2_boundary(points, tets, bnd_tris; c_tri=bnd_c, device=device) : assemble_p1_boundary(points, bnd_tris; c_tri=bnd_c, device=device)
+    Q = nothing; V = nothing
+    if flame !== nothing
+        flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled = flame
+        Q, V = quad ? assemble_p2_flame(points, tets, flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled; device=device) :
+                      assemble_p1_flame(points, tets, flame_tets, ref_tet, n_ref, nglobal_scaled; device=device)
+    end
+    return M, K, C, Q, V
+end
+
 "sens (3 x length(surface_points)) = discrete_adjoint_shape_sensitivity_p1(points, tets, c_tet, surface_points, ω, v, v_adj; ...):
 -v_adjᴴ (dL/dx) v of shape_sensitivity.jl:16-141 for the interior operators and, if bnd_tris is given, the admittance boundary ω·Y·C;
 v, v_adj normalised as there (vᴴv = 1, v_adjᴴ L'(ω) v = 1).  One device thread per (point, adjacent simplex, coordinate); the pairs of a

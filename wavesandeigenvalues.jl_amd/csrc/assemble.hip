@@ -185,20 +185,11 @@ __global__ __launch_bounds__(256) void split_keys_kernel(const unsigned long lon
     }
 }
 
-struct P1Handle {
-    int64_t np = 0, nnz = 0;
-    std::vector<int> rowptr, col;
-    std::vector<double> m, k;
-};
-
-template <class T> struct Dev {
-    T *p = nullptr;
-    explicit Dev(size_t n) { HIP_CHECK(hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T))); }
-    ~Dev() { if (p) (void)hipFree(p); }
-};
+}  // namespace
 
 // keyed triplets (key = row * np + col; up to two value streams) -> CSR: stable radix sort (duplicates adjacent, in
-// element order: the sums are deterministic, no atomics), reduce-by-key, row pointer from the unique keys
+// element order: the sums are deterministic, no atomics), reduce-by-key, row pointer from the unique keys  (declared in
+// wae_internal.h: assemble_p2.hip feeds it too)
 P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k0, Dev<double> &mv, Dev<double> *kv) {
     Dev<double> ms(ne), ks(kv ? ne : 1), mu(ne), ku(kv ? ne : 1);
     Dev<int> dcol(ne), drow((size_t)npoints + 1), dnum(1);
@@ -236,6 +227,8 @@ P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k
         if (H->rowptr[r] < 0) H->rowptr[r] = H->rowptr[r + 1];
     return H.release();
 }
+
+namespace {
 
 // boundary mass of one triangle: b_ab = c |(x0-x2) x (x1-x2)| (1+delta_ab)/24  (FEM.jl:9-20,435-441; Helmholtz.jl:151-156); C = -i b
 __global__ __launch_bounds__(256) void p1_boundary_kernel(const double *__restrict__ pts, const int *__restrict__ tris, const double *__restrict__ c_tri,

@@ -1,0 +1,486 @@
+// P2 (second-order) tetrahedral assembly of the Helmholtz operators on the device: `discretize(...; order=:quad)` of the reference
+// (src/Helmholtz.jl:36-54) for the interior, admittance-boundary and flame domains.
+//
+//   1. Edge numbering (aggregate_elements, src/FEM/FEM.jl:84-116; collect_lines!, Meshutils.jl:831-840): one kernel writes the six
+//      keys min(v_i,v_j)*npoints + max(v_i,v_j) of every tetrahedron, a radix sort and a unique pass (hipCUB) leave the edge list
+//      in lexicographic order, a second kernel finds every local edge of every tetrahedron and boundary triangle in it by binary
+//      search.  DoF of edge e = npoints + e.
+//   2. Element kernels, one thread per (simplex, local row): 10 (tetrahedron) or 6 (triangle) triplets of that row.  A thread keeps
+//      no array that it indexes by its row number: what depends on the row is read from the basis tables in constant memory.
+//   3. triplets_to_csr (assemble.hip): stable sort, reduce-by-key, row pointer -- deterministic, no atomics.
+//
+// Basis (barycentric coordinates l_1..l_n, n = 4 or 3): vertex functions l_i (2 l_i - 1), edge functions 4 l_i l_j, local order
+// vertices first, then the edges (1,2), (1,3), (1,4), (2,3), (2,4), (3,4) resp. (1,2), (1,3), (2,3).  With sum l = 1 every function is
+// a homogeneous quadratic form  phi_a = 1/2 sum_kl q2[a][k][l] l_k l_l  with integer q2, and the monomial formula
+//     int l^alpha = |det J| prod(alpha_i!) / (|alpha| + n - 1)!
+// gives every local matrix exactly: the tables below are made from it at compile time, none is copied from anywhere.
+#include <hipcub/hipcub.hpp>
+
+#include <climits>
+#include <memory>
+
+#include "wae_internal.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+template <class F> int wae_guarded(F &&f) {
+    try {
+        return f();
+    } catch (const WaeError &e) {
+        wae_set_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        wae_set_error(e.what());
+        return WAE_ERR_INVALID;
+    }
+}
+
+template <int NV> struct P2Basis {
+    static constexpr int NN = NV + NV * (NV - 1) / 2;
+    double mass[NN][NN];      // int phi_a phi_b / |det J|
+    double src[NN];           // int phi_a / |det J|
+    double d[NN][NV][NV];     // d phi_a / d l_i = sum_k d[a][i][k] l_k
+};
+
+constexpr long long p2_factorial(int n) { return n <= 1 ? 1 : n * p2_factorial(n - 1); }
+
+template <int NV> constexpr P2Basis<NV> make_p2_basis() {
+    constexpr int NN = P2Basis<NV>::NN;
+    int q2[NN][NV][NV] = {};
+    for (int a = 0; a < NV; ++a)                  // l_a (2 l_a - sum_k l_k) = l_a^2 - sum_{k != a} l_a l_k
+        for (int k = 0; k < NV; ++k) {
+            if (k == a) q2[a][a][a] = 2;
+            else q2[a][a][k] = q2[a][k][a] = -1;
+        }
+    int a = NV;
+    for (int i = 0; i < NV; ++i)
+        for (int j = i + 1; j < NV; ++j, ++a) q2[a][i][j] = q2[a][j][i] = 4;      // 4 l_i l_j
+    P2Basis<NV> B = {};
+    for (int r = 0; r < NN; ++r) {
+        long long s = 0;
+        for (int k = 0; k < NV; ++k)
+            for (int l = 0; l < NV; ++l) s += q2[r][k][l] * (k == l ? 2 : 1);
+        B.src[r] = (double)s / (double)(2 * p2_factorial(NV + 1));
+        for (int c = 0; c < NN; ++c) {
+            long long num = 0;
+            for (int k = 0; k < NV; ++k)
+                for (int l = 0; l < NV; ++l)
+                    for (int m = 0; m < NV; ++m)
+                        for (int n = 0; n < NV; ++n) {
+                            if (q2[r][k][l] == 0 || q2[c][m][n] == 0) continue;
+                            int cnt[NV] = {};
+                            ++cnt[k]; ++cnt[l]; ++cnt[m]; ++cnt[n];
+                            long long mono = 1;
+                            for (int v = 0; v < NV; ++v) mono *= p2_factorial(cnt[v]);
+                            num += (long long)q2[r][k][l] * q2[c][m][n] * mono;
+                        }
+            B.mass[r][c] = (double)num / (double)(4 * p2_factorial(NV + 3));
+        }
+        for (int i = 0; i < NV; ++i)
+            for (int k = 0; k < NV; ++k) B.d[r][i][k] = (double)q2[r][i][k];
+    }
+    return B;
+}
+
+constexpr P2Basis<4> kTet = make_p2_basis<4>();
+constexpr P2Basis<3> kTri = make_p2_basis<3>();
+__constant__ P2Basis<4> dTet = kTet;
+__constant__ P2Basis<3> dTri = kTri;
+
+// G[a] = grad l_a of the tetrahedron with corners X (l_4 = 1 - l_1 - l_2 - l_3, corner 4 is the origin: CooTrafo, FEM.jl:9-20); returns det J
+__host__ __device__ inline double p2_tet_gradients(const double X[4][3], double G[4][3]) {
+    double J[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int a = 0; a < 3; ++a) J[r][a] = X[a][r] - X[3][r];
+    const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+    const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+    const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+    const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
+    const double id = 1.0 / det;
+    G[0][0] = c00 * id; G[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id; G[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
+    G[1][0] = c01 * id; G[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id; G[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
+    G[2][0] = c02 * id; G[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id; G[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+    for (int k = 0; k < 3; ++k) G[3][k] = -(G[0][k] + G[1][k] + G[2][k]);
+    return det;
+}
+
+// grad phi = sum_k l_k w[k] with w[k] = sum_i d[i][k] grad l_i; s = sum_k w[k].  One fixed order of operations, so that the row's and
+// the column's function get the same bits and K_ab == K_ba.
+__host__ __device__ inline void p2_grad_coeffs(const double d[4][4], const double G[4][3], double w[4][3], double s[3]) {
+    for (int c = 0; c < 3; ++c) s[c] = 0.0;
+    for (int k = 0; k < 4; ++k)
+        for (int c = 0; c < 3; ++c) {
+            double x = d[0][k] * G[0][c];
+            for (int i = 1; i < 4; ++i) x = fma(d[i][k], G[i][c], x);
+            w[k][c] = x;
+            s[c] += x;
+        }
+}
+
+// ---- edge numbering ------------------------------------------------------------------------------------------------------------
+__device__ inline u64 p2_edge_key(int u, int v, u64 np) { return (u64)min(u, v) * np + (u64)max(u, v); }
+
+__global__ __launch_bounds__(256) void p2_edge_keys_kernel(const int *__restrict__ tets, int64_t nt, u64 np, u64 *__restrict__ keys) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    const int v0 = tets[t * 4], v1 = tets[t * 4 + 1], v2 = tets[t * 4 + 2], v3 = tets[t * 4 + 3];
+    u64 *k = keys + t * 6;
+    k[0] = p2_edge_key(v0, v1, np); k[1] = p2_edge_key(v0, v2, np); k[2] = p2_edge_key(v0, v3, np);
+    k[3] = p2_edge_key(v1, v2, np); k[4] = p2_edge_key(v1, v3, np); k[5] = p2_edge_key(v2, v3, np);
+}
+
+// position of the edge (u, v) in the sorted list, or -1
+__device__ inline int p2_find_edge(const u64 *__restrict__ ek, int64_t ne, u64 np, int u, int v) {
+    const u64 key = p2_edge_key(u, v, np);
+    int64_t lo = 0, hi = ne;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ek[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return (lo < ne && ek[lo] == key) ? (int)lo : -1;
+}
+
+// threads 0..nt-1: 10-node connectivity of a tetrahedron; nt..nt+ns-1: 6-node connectivity of a boundary triangle.
+// bad[0] / bad[1]: a tetrahedron / a triangle with an edge that is not in the list (its node is written as -1)
+__global__ __launch_bounds__(256) void p2_connect_kernel(const int *__restrict__ tets, int64_t nt, const int *__restrict__ tris, int64_t ns,
+                                                         const u64 *__restrict__ ek, int64_t ne, u64 np, int *__restrict__ t10,
+                                                         int *__restrict__ s6, int *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < nt) {
+        const int v0 = tets[i * 4], v1 = tets[i * 4 + 1], v2 = tets[i * 4 + 2], v3 = tets[i * 4 + 3];
+        const int e0 = p2_find_edge(ek, ne, np, v0, v1), e1 = p2_find_edge(ek, ne, np, v0, v2), e2 = p2_find_edge(ek, ne, np, v0, v3);
+        const int e3 = p2_find_edge(ek, ne, np, v1, v2), e4 = p2_find_edge(ek, ne, np, v1, v3), e5 = p2_find_edge(ek, ne, np, v2, v3);
+        int *o = t10 + i * 10;
+        const int off = (int)np;
+        o[0] = v0; o[1] = v1; o[2] = v2; o[3] = v3;
+        o[4] = e0 < 0 ? -1 : off + e0; o[5] = e1 < 0 ? -1 : off + e1; o[6] = e2 < 0 ? -1 : off + e2;
+        o[7] = e3 < 0 ? -1 : off + e3; o[8] = e4 < 0 ? -1 : off + e4; o[9] = e5 < 0 ? -1 : off + e5;
+        if ((e0 | e1 | e2 | e3 | e4 | e5) < 0) bad[0] = 1;
+    } else if (i < nt + ns) {
+        const int64_t s = i - nt;
+        const int v0 = tris[s * 3], v1 = tris[s * 3 + 1], v2 = tris[s * 3 + 2];
+        const int e0 = p2_find_edge(ek, ne, np, v0, v1), e1 = p2_find_edge(ek, ne, np, v0, v2), e2 = p2_find_edge(ek, ne, np, v1, v2);
+        int *o = s6 + s * 6;
+        const int off = (int)np;
+        o[0] = v0; o[1] = v1; o[2] = v2;
+        o[3] = e0 < 0 ? -1 : off + e0; o[4] = e1 < 0 ? -1 : off + e1; o[5] = e2 < 0 ? -1 : off + e2;
+        if ((e0 | e1 | e2) < 0) bad[1] = 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void p2_edge_pairs_kernel(const u64 *__restrict__ ek, int64_t ne, u64 np, int *__restrict__ edges) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= ne) return;
+    const u64 k = ek[e], lo = k / np;
+    edges[e * 2] = (int)lo;
+    edges[e * 2 + 1] = (int)(k - lo * np);
+}
+
+// ---- element kernels -------------------------------------------------------------------------------------------------------------
+// row a of the local matrices of tetrahedron t:  M_ab = |det J| int phi_a phi_b,   K_ab = -c^2 |det J| int grad phi_a . grad phi_b  with
+// int l_k l_l = (1 + delta_kl)/120:   K_ab = -c^2 |det J|/120 (s_a . s_b + sum_k w_a[k] . w_b[k])
+__global__ __launch_bounds__(256) void p2_local_kernel(const double *__restrict__ pts, const int *__restrict__ t10, const double *__restrict__ c_tet,
+                                                       int64_t nt, u64 dim, u64 *__restrict__ keys, double *__restrict__ mv, double *__restrict__ kv) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= nt * 10) return;
+    const int64_t t = e / 10;
+    const int a = (int)(e - t * 10);
+    int nd[10];
+#pragma unroll
+    for (int b = 0; b < 10; ++b) nd[b] = t10[t * 10 + b];
+    double X[4][3], G[4][3];
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+        for (int k = 0; k < 3; ++k) X[v][k] = pts[(size_t)nd[v] * 3 + k];
+    const double adet = fabs(p2_tet_gradients(X, G));
+    const double c = c_tet ? c_tet[t] : 1.0;
+    const double ks = -(c * c) * adet / 120.0;
+    double wa[4][3], sa[3];
+    p2_grad_coeffs(dTet.d[a], G, wa, sa);
+    const u64 row = (u64)t10[t * 10 + a] * dim;
+#pragma unroll
+    for (int b = 0; b < 10; ++b) {
+        double wb[4][3], sb[3];
+        p2_grad_coeffs(dTet.d[b], G, wb, sb);
+        double acc = sa[0] * sb[0];
+        acc = fma(sa[1], sb[1], acc);
+        acc = fma(sa[2], sb[2], acc);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            for (int x = 0; x < 3; ++x) acc = fma(wa[k][x], wb[k][x], acc);
+        const size_t o = (size_t)e * 10 + b;
+        keys[o] = row + (u64)nd[b];
+        mv[o] = adet * dTet.mass[a][b];
+        kv[o] = ks * acc;
+    }
+}
+
+// row a of the boundary mass of triangle t: b_ab = c |(x0-x2) x (x1-x2)| int phi_a phi_b on the 6-node triangle
+__global__ __launch_bounds__(256) void p2_boundary_kernel(const double *__restrict__ pts, const int *__restrict__ s6, const double *__restrict__ c_tri,
+                                                          int64_t ns, u64 dim, u64 *__restrict__ keys, double *__restrict__ bv) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= ns * 6) return;
+    const int64_t t = e / 6;
+    const int a = (int)(e - t * 6);
+    int nd[6];
+#pragma unroll
+    for (int b = 0; b < 6; ++b) nd[b] = s6[t * 6 + b];
+    double X[3][3];
+#pragma unroll
+    for (int v = 0; v < 3; ++v)
+        for (int k = 0; k < 3; ++k) X[v][k] = pts[(size_t)nd[v] * 3 + k];
+    const double u0 = X[0][0] - X[2][0], u1 = X[0][1] - X[2][1], u2 = X[0][2] - X[2][2];
+    const double w0 = X[1][0] - X[2][0], w1 = X[1][1] - X[2][1], w2 = X[1][2] - X[2][2];
+    const double n0 = u1 * w2 - u2 * w1, n1 = u2 * w0 - u0 * w2, n2 = u0 * w1 - u1 * w0;
+    const double cd = (c_tri ? c_tri[t] : 1.0) * sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+    const u64 row = (u64)s6[t * 6 + a] * dim;
+#pragma unroll
+    for (int b = 0; b < 6; ++b) {
+        const size_t o = (size_t)e * 6 + b;
+        keys[o] = row + (u64)nd[b];
+        bv[o] = cd * dTri.mass[a][b];
+    }
+}
+
+// |det J| of the listed tetrahedra (flame volume = sum |det J| / 6)
+__global__ __launch_bounds__(256) void p2_det_kernel(const double *__restrict__ pts, const int *__restrict__ t10, const int *__restrict__ list, int64_t n,
+                                                     double *__restrict__ adet) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t t = list[i];
+    double X[4][3], G[4][3];
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+        for (int k = 0; k < 3; ++k) X[v][k] = pts[(size_t)t10[t * 10 + v] * 3 + k];
+    adet[i] = fabs(p2_tet_gradients(X, G));
+}
+
+// Q triplets: (node a of flame tetrahedron i, node b of the reference tetrahedron) -> |det J_i| int phi_a * g_b
+__global__ __launch_bounds__(256) void p2_flame_kernel(const int *__restrict__ t10, const int *__restrict__ list, int64_t n, const double *__restrict__ adet,
+                                                       int ref_tet, const double *__restrict__ g, u64 dim, u64 *__restrict__ keys, double *__restrict__ qv) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n * 10) return;
+    const int64_t i = e / 10;
+    const int a = (int)(e - i * 10);
+    const int64_t t = list[i];
+    const double s = adet[i] * dTet.src[a];
+    const u64 row = (u64)t10[t * 10 + a] * dim;
+#pragma unroll
+    for (int b = 0; b < 10; ++b) {
+        const size_t o = (size_t)e * 10 + b;
+        keys[o] = row + (u64)t10[(int64_t)ref_tet * 10 + b];
+        qv[o] = s * g[b];
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+struct P2Conn {
+    int64_t npoints = 0, nedges = 0, ntets = 0, ntris = 0;
+    std::vector<int> edges, tets10, tris6;
+};
+
+void p2_check_mesh(int64_t npoints, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris) {
+    if (!(npoints > 0 && ntets > 0 && tets && ntris >= 0 && (ntris == 0 || tris))) throw WaeError(WAE_ERR_INVALID, "bad argument");
+    if (npoints > INT_MAX || ntets > INT_MAX / 100 || ntris > INT_MAX / 36)
+        throw WaeError(WAE_ERR_INVALID, "mesh too large: 100*ntets and 36*ntris triplets must fit a 32-bit count");
+    for (int64_t i = 0; i < ntets * 4; ++i)
+        if (tets[i] < 0 || tets[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "tetrahedron refers to a point outside 0..npoints-1");
+    for (int64_t i = 0; i < ntris * 3; ++i)
+        if (tris[i] < 0 || tris[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "triangle refers to a point outside 0..npoints-1");
+}
+
+// Edge list and connectivities of a mesh whose 4-node tetrahedra (and 3-node triangles, ns may be 0) are on the device.
+// ek: room for 6*nt keys, on return the nedges sorted unique keys; t10: 10*nt; s6: 6*ns.  Returns nedges.
+int64_t p2_connect(int64_t npoints, int64_t nt, const int *dtets, int64_t ns, const int *dtris, Dev<u64> &ek, Dev<int> &t10, Dev<int> &s6) {
+    const int nk = (int)(nt * 6);
+    Dev<u64> k0((size_t)nk), k1((size_t)nk);
+    Dev<int> dnum(1), bad(2);
+    hipLaunchKernelGGL(p2_edge_keys_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, 0, dtets, nt, (u64)npoints, k0.p);
+    HIP_CHECK(hipGetLastError());
+    int bits = 1;
+    while (bits < 64 && ((u64)npoints * (u64)npoints) >> bits) ++bits;
+    size_t tb = 0, tb2 = 0;
+    HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, k0.p, k1.p, nk, 0, bits));
+    HIP_CHECK(hipcub::DeviceSelect::Unique(nullptr, tb2, k1.p, ek.p, dnum.p, nk));
+    Dev<char> tmp(std::max(tb, tb2));
+    HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(tmp.p, tb, k0.p, k1.p, nk, 0, bits));
+    HIP_CHECK(hipcub::DeviceSelect::Unique(tmp.p, tb2, k1.p, ek.p, dnum.p, nk));
+    int ne = 0;
+    HIP_CHECK(hipMemcpy(&ne, dnum.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (ne <= 0 || ne > nk) throw WaeError(WAE_ERR_HIP, "edge list: unique pass returned an impossible count");
+    if (npoints + (int64_t)ne > INT_MAX) throw WaeError(WAE_ERR_INVALID, "npoints + nedges does not fit a 32-bit index");
+    HIP_CHECK(hipMemset(bad.p, 0, 2 * sizeof(int)));
+    hipLaunchKernelGGL(p2_connect_kernel, dim3((unsigned)((nt + ns + 255) / 256)), dim3(256), 0, 0, dtets, nt, dtris, ns, ek.p, (int64_t)ne, (u64)npoints,
+                       t10.p, s6.p, bad.p);
+    HIP_CHECK(hipGetLastError());
+    int hbad[2] = {0, 0};
+    HIP_CHECK(hipMemcpy(hbad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    if (hbad[0]) throw WaeError(WAE_ERR_HIP, "edge list: an edge of a tetrahedron was not found");
+    if (hbad[1]) throw WaeError(WAE_ERR_INVALID, "a boundary triangle has an edge that is no tetrahedron's edge");
+    return ne;
+}
+
+// the mesh on the device with its P2 connectivity
+struct P2Mesh {
+    Dev<double> pts;
+    Dev<int> tets, tris, t10, s6;
+    Dev<u64> ek;
+    int64_t nedges = 0, dim = 0;
+    P2Mesh(int64_t npoints, const double *points, int64_t nt, const int32_t *htets, int64_t ns, const int32_t *htris)
+        : pts(points ? (size_t)npoints * 3 : 1), tets((size_t)nt * 4), tris((size_t)ns * 3), t10((size_t)nt * 10), s6((size_t)ns * 6), ek((size_t)nt * 6) {
+        if (points) HIP_CHECK(hipMemcpy(pts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(tets.p, htets, (size_t)nt * 4 * sizeof(int), hipMemcpyHostToDevice));
+        if (ns) HIP_CHECK(hipMemcpy(tris.p, htris, (size_t)ns * 3 * sizeof(int), hipMemcpyHostToDevice));
+        nedges = p2_connect(npoints, nt, tets.p, ns, tris.p, ek, t10, s6);
+        dim = npoints + nedges;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int wae_p2_connectivity(int32_t device, int64_t npoints, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris, void **out) {
+    return wae_guarded([&]() {
+        if (!out) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        p2_check_mesh(npoints, ntets, tets, ntris, tris);
+        HIP_CHECK(hipSetDevice(device));
+        P2Mesh m(npoints, nullptr, ntets, tets, ntris, tris);
+        std::unique_ptr<P2Conn> H(new P2Conn);
+        H->npoints = npoints; H->nedges = m.nedges; H->ntets = ntets; H->ntris = ntris;
+        H->edges.resize((size_t)m.nedges * 2); H->tets10.resize((size_t)ntets * 10); H->tris6.resize((size_t)ntris * 6);
+        Dev<int> de((size_t)m.nedges * 2);
+        hipLaunchKernelGGL(p2_edge_pairs_kernel, dim3((unsigned)((m.nedges + 255) / 256)), dim3(256), 0, 0, m.ek.p, m.nedges, (u64)npoints, de.p);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(H->edges.data(), de.p, H->edges.size() * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(H->tets10.data(), m.t10.p, H->tets10.size() * sizeof(int), hipMemcpyDeviceToHost));
+        if (ntris) HIP_CHECK(hipMemcpy(H->tris6.data(), m.s6.p, H->tris6.size() * sizeof(int), hipMemcpyDeviceToHost));
+        *out = H.release();
+        return WAE_OK;
+    });
+}
+
+int wae_p2_connectivity_info(const void *handle, int64_t *nedges, int64_t *ntets, int64_t *ntris) {
+    return wae_guarded([&]() {
+        if (!handle) throw WaeError(WAE_ERR_INVALID, "null handle");
+        const P2Conn *H = (const P2Conn *)handle;
+        if (nedges) *nedges = H->nedges;
+        if (ntets) *ntets = H->ntets;
+        if (ntris) *ntris = H->ntris;
+        return WAE_OK;
+    });
+}
+
+int wae_p2_connectivity_get(const void *handle, int32_t *edges, int32_t *tets10, int32_t *tris6) {
+    return wae_guarded([&]() {
+        if (!handle) throw WaeError(WAE_ERR_INVALID, "null handle");
+        const P2Conn *H = (const P2Conn *)handle;
+        if (edges) memcpy(edges, H->edges.data(), H->edges.size() * sizeof(int));
+        if (tets10) memcpy(tets10, H->tets10.data(), H->tets10.size() * sizeof(int));
+        if (tris6) memcpy(tris6, H->tris6.data(), H->tris6.size() * sizeof(int));
+        return WAE_OK;
+    });
+}
+
+int wae_p2_connectivity_free(void *handle) {
+    delete (P2Conn *)handle;
+    return WAE_OK;
+}
+
+int wae_p2_assemble(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_tet, void **out) {
+    return wae_guarded([&]() {
+        if (!(points && out)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        p2_check_mesh(npoints, ntets, tets, 0, nullptr);
+        HIP_CHECK(hipSetDevice(device));
+        P2Mesh m(npoints, points, ntets, tets, 0, nullptr);
+        const size_t ne = (size_t)ntets * 100;
+        Dev<double> dc(c_tet ? (size_t)ntets : 1), mv(ne), kv(ne);
+        Dev<u64> k0(ne);
+        if (c_tet) HIP_CHECK(hipMemcpy(dc.p, c_tet, (size_t)ntets * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(p2_local_kernel, dim3((unsigned)((ntets * 10 + 255) / 256)), dim3(256), 0, 0, m.pts.p, m.t10.p, c_tet ? dc.p : nullptr, ntets,
+                           (u64)m.dim, k0.p, mv.p, kv.p);
+        HIP_CHECK(hipGetLastError());
+        *out = triplets_to_csr(m.dim, ne, k0, mv, &kv);
+        return WAE_OK;
+    });
+}
+
+int wae_p2_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                             const int32_t *tris, const double *c_tri, void **out) {
+    return wae_guarded([&]() {
+        if (!(points && out && ntris > 0)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        p2_check_mesh(npoints, ntets, tets, ntris, tris);
+        HIP_CHECK(hipSetDevice(device));
+        P2Mesh m(npoints, points, ntets, tets, ntris, tris);
+        const size_t ne = (size_t)ntris * 36;
+        Dev<double> dc(c_tri ? (size_t)ntris : 1), bv(ne);
+        Dev<u64> k0(ne);
+        if (c_tri) HIP_CHECK(hipMemcpy(dc.p, c_tri, (size_t)ntris * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(p2_boundary_kernel, dim3((unsigned)((ntris * 6 + 255) / 256)), dim3(256), 0, 0, m.pts.p, m.s6.p, c_tri ? dc.p : nullptr, ntris,
+                           (u64)m.dim, k0.p, bv.p);
+        HIP_CHECK(hipGetLastError());
+        *out = triplets_to_csr(m.dim, ne, k0, bv, nullptr);
+        return WAE_OK;
+    });
+}
+
+int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t nflame,
+                          const int32_t *flame_tets, int32_t ref_tet, const double *x_ref, const double *n_ref, double nglobal_scaled, void **out,
+                          double *volume_out) {
+    return wae_guarded([&]() {
+        if (!(points && out && nflame > 0 && flame_tets && x_ref && n_ref)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        p2_check_mesh(npoints, ntets, tets, 0, nullptr);
+        if (nflame > INT_MAX / 100) throw WaeError(WAE_ERR_INVALID, "too many flame tetrahedra: 100*nflame triplets must fit a 32-bit count");
+        if (ref_tet < 0 || ref_tet >= ntets) throw WaeError(WAE_ERR_INVALID, "reference tetrahedron out of range");
+        for (int64_t i = 0; i < nflame; ++i)
+            if (flame_tets[i] < 0 || flame_tets[i] >= ntets) throw WaeError(WAE_ERR_INVALID, "flame tetrahedron out of range");
+        HIP_CHECK(hipSetDevice(device));
+        P2Mesh m(npoints, points, ntets, tets, 0, nullptr);
+        const size_t ne = (size_t)nflame * 100;
+        Dev<double> adet((size_t)nflame), vol(1), qv(ne), dg(10);
+        Dev<int> dl((size_t)nflame);
+        Dev<u64> k0(ne);
+        HIP_CHECK(hipMemcpy(dl.p, flame_tets, (size_t)nflame * sizeof(int), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(p2_det_kernel, dim3((unsigned)((nflame + 255) / 256)), dim3(256), 0, 0, m.pts.p, m.t10.p, dl.p, nflame, adet.p);
+        HIP_CHECK(hipGetLastError());
+        // flame volume = sum |det J| / 6 (Meshutils.jl:757-767), summed in a fixed tree order on the device
+        size_t tb = 0;
+        HIP_CHECK(hipcub::DeviceReduce::Sum(nullptr, tb, adet.p, vol.p, (int)nflame));
+        Dev<char> tmp(tb);
+        HIP_CHECK(hipcub::DeviceReduce::Sum(tmp.p, tb, adet.p, vol.p, (int)nflame));
+        double det_sum = 0.0;
+        HIP_CHECK(hipMemcpy(&det_sum, vol.p, sizeof(double), hipMemcpyDeviceToHost));
+        const double volume = det_sum / 6.0;
+        if (!(volume > 0.0)) throw WaeError(WAE_ERR_INVALID, "flame domain has no volume");
+        if (volume_out) *volume_out = volume;
+        const double nlocal = nglobal_scaled / volume;                                 // Helmholtz.jl:325
+        // g_b = -nlocal grad(phi_b)(x_ref) . n_ref on the 10 nodes of the reference tetrahedron (Helmholtz.jl:477-482): 10 numbers, on the host
+        double X[4][3], G[4][3];
+        for (int a = 0; a < 4; ++a)
+            for (int k = 0; k < 3; ++k) X[a][k] = points[(size_t)tets[(size_t)ref_tet * 4 + a] * 3 + k];
+        if (p2_tet_gradients(X, G) == 0.0) throw WaeError(WAE_ERR_INVALID, "degenerate reference tetrahedron");
+        double lam[4];
+        lam[3] = 1.0;
+        for (int a = 0; a < 3; ++a) {
+            lam[a] = G[a][0] * (x_ref[0] - X[3][0]) + G[a][1] * (x_ref[1] - X[3][1]) + G[a][2] * (x_ref[2] - X[3][2]);
+            lam[3] -= lam[a];
+        }
+        double g[10];
+        for (int b = 0; b < 10; ++b) {
+            double w[4][3], s[3], acc = 0.0;
+            p2_grad_coeffs(kTet.d[b], G, w, s);
+            for (int k = 0; k < 4; ++k) acc += lam[k] * (w[k][0] * n_ref[0] + w[k][1] * n_ref[1] + w[k][2] * n_ref[2]);
+            g[b] = -nlocal * acc;
+        }
+        HIP_CHECK(hipMemcpy(dg.p, g, sizeof(g), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(p2_flame_kernel, dim3((unsigned)((nflame * 10 + 255) / 256)), dim3(256), 0, 0, m.t10.p, dl.p, nflame, adet.p, ref_tet, dg.p,
+                           (u64)m.dim, k0.p, qv.p);
+        HIP_CHECK(hipGetLastError());
+        *out = triplets_to_csr(m.dim, ne, k0, qv, nullptr);
+        return WAE_OK;
+    });
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of libwaehip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <complex>
 #include <cstdint>
 #include <cstdio>
@@ -237,6 +238,22 @@ struct Transfer {                   // P (n_fine x n_coarse) and R = P^T as sing
     OpDev devP() const;
     OpDev devR() const;
 };
+
+// device assembly (assemble.hip: P1, assemble_p2.hip: P2) ------------------------------------------------------------
+struct P1Handle {                   // an assembled CSR pattern with up to two real value streams, on the host (wae_p1_info / _get / _free)
+    int64_t np = 0, nnz = 0;        // np: rows = columns (P1: points; P2: points + edges)
+    std::vector<int> rowptr, col;
+    std::vector<double> m, k;
+};
+template <class T> struct Dev {     // function-local device array of the assembly entries
+    T *p = nullptr;
+    explicit Dev(size_t n) { HIP_CHECK(hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T))); }
+    Dev(const Dev &) = delete;
+    Dev &operator=(const Dev &) = delete;
+    ~Dev() { if (p) (void)hipFree(p); }
+};
+// keyed triplets (key = row * npoints + col, ne of them with ne <= INT_MAX; one or two value streams) -> CSR of npoints rows
+P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k0, Dev<double> &mv, Dev<double> *kv);
 
 // kernel launch wrappers: operator, transfer and dense level (kernels.hip) ------------------------------
 enum { MODE_AX = 0, MODE_RES = 1, MODE_JAC = 2, MODE_ADD = 3, MODE_AX_DS = 4, MODE_RES_DS = 5, MODE_AX_J0 = 6 };

@@ -21,6 +21,12 @@ def assemble_p1(points, tets, c_tet=None, device=0, dtype=np.complex128):
     dp = C.POINTER(C.c_double)
     _lib.check(L.wae_p1_assemble(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
                                  None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
+    return _take_pair(L, h, dtype)
+
+
+def _take_pair(L, h, dtype):
+    """copy an assembly handle with two value streams out as (M, K), scipy CSR matrices sharing one pattern, and free it"""
+    dp = C.POINTER(C.c_double)
     try:
         n, nnz = C.c_int64(0), C.c_int64(0)
         _lib.check(L.wae_p1_info(h, C.byref(n), C.byref(nnz)))
@@ -79,6 +85,83 @@ def assemble_p1_flame(points, tets, flame_tets, ref_tet, n_ref, nglobal_scaled, 
     ip = C.POINTER(C.c_int32)
     _lib.check(L.wae_p1_assemble_flame(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), len(fl), fl.ctypes.data_as(ip),
                                        int(ref_tet), nr.ctypes.data_as(dp), float(nglobal_scaled), C.byref(h), C.byref(vol)))
+    return _take_csr(L, h, np.complex128), vol.value
+
+
+# ---- P2 (second-order) elements: `discretize(...; order=:quad)` ---------------------------------------------------------------
+def _mesh_args(points, tets, tris=None):
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    tt = np.ascontiguousarray(tets, dtype=np.int32).reshape(-1, 4)
+    tr = None if tris is None else np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    return pts, tt, tr
+
+
+def p2_connectivity(points, tets, tris=None, device=0):
+    """Edge DoFs of the P2 space numbered on the device (wae_p2_connectivity; aggregate_elements, src/FEM/FEM.jl:84-116): the unique
+    mesh edges sorted by (smaller point, larger point), DoF of edge e = npoints + e.  ``points``: the (npoints, 3) array or just
+    npoints.  Returns (edges (nedges, 2), tets10 (ntets, 10), tris6 (ntris, 6)), 0-based, local node order = the points, then the
+    edges (1,2), (1,3), (1,4), (2,3), (2,4), (3,4) resp. (1,2), (1,3), (2,3)."""
+    npoints = int(points) if np.ndim(points) == 0 else np.asarray(points).reshape(-1, 3).shape[0]
+    _, tt, tr = _mesh_args(np.zeros((0, 3)), tets, tris)
+    L = _lib.lib()
+    ip = C.POINTER(C.c_int32)
+    h = C.c_void_p()
+    _lib.check(L.wae_p2_connectivity(int(device), npoints, tt.shape[0], tt.ctypes.data_as(ip), 0 if tr is None else tr.shape[0],
+                                     None if tr is None or not len(tr) else tr.ctypes.data_as(ip), C.byref(h)))
+    try:
+        ne, nt, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(L.wae_p2_connectivity_info(h, C.byref(ne), C.byref(nt), C.byref(ns)))
+        edges = np.zeros((ne.value, 2), dtype=np.int32)
+        t10 = np.zeros((nt.value, 10), dtype=np.int32)
+        t6 = np.zeros((ns.value, 6), dtype=np.int32)
+        _lib.check(L.wae_p2_connectivity_get(h, edges.ctypes.data_as(ip), t10.ctypes.data_as(ip), t6.ctypes.data_as(ip)))
+    finally:
+        L.wae_p2_connectivity_free(h)
+    return edges, t10, t6
+
+
+def assemble_p2(points, tets, c_tet=None, device=0, dtype=np.complex128):
+    """P2 mass and stiffness matrices on the device (wae_p2_assemble; src/Helmholtz.jl:120-149,405-441 with order=:quad), arguments as
+    ``assemble_p1``.  Returns (M, K) as scipy CSR matrices of size npoints + nedges sharing one pattern."""
+    pts, tt, _ = _mesh_args(points, tets)
+    cc = None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
+    assert cc is None or cc.shape == (tt.shape[0],)
+    L = _lib.lib()
+    h = C.c_void_p()
+    dp = C.POINTER(C.c_double)
+    _lib.check(L.wae_p2_assemble(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
+    return _take_pair(L, h, dtype)
+
+
+def assemble_p2_boundary(points, tets, tris, c_tri=None, device=0):
+    """P2 boundary mass term of an admittance boundary on the device (wae_p2_assemble_boundary; src/Helmholtz.jl:151-170,443-463):
+    C = -i·c·|e1×e2|·∫φ_aφ_b on the 6-node triangles; ``tets`` gives the edge numbers.  Returns C (complex CSR, npoints + nedges)."""
+    pts, tt, tr = _mesh_args(points, tets, tris)
+    cc = None if c_tri is None else np.ascontiguousarray(c_tri, dtype=np.float64)
+    assert cc is None or cc.shape == (tr.shape[0],)
+    L = _lib.lib()
+    h = C.c_void_p()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _lib.check(L.wae_p2_assemble_boundary(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), tr.shape[0],
+                                          tr.ctypes.data_as(ip), None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
+    return -1j * _take_csr(L, h, np.complex128)
+
+
+def assemble_p2_flame(points, tets, flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled, device=0):
+    """P2 flame operator Q = Σ_flame S ⊗ g on the device (wae_p2_assemble_flame; src/Helmholtz.jl:292-344,464-487): as
+    ``assemble_p1_flame``, and ``x_ref``, the reference point inside ``ref_tet`` at which the gradients are taken.  Returns (Q, V_flame)."""
+    pts, tt, _ = _mesh_args(points, tets)
+    fl = np.ascontiguousarray(flame_tets, dtype=np.int32)
+    xr = np.ascontiguousarray(x_ref, dtype=np.float64)
+    nr = np.ascontiguousarray(n_ref, dtype=np.float64)
+    assert xr.shape == (3,) and nr.shape == (3,)
+    L = _lib.lib()
+    h = C.c_void_p()
+    vol = C.c_double(0.0)
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _lib.check(L.wae_p2_assemble_flame(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), len(fl), fl.ctypes.data_as(ip),
+                                       int(ref_tet), xr.ctypes.data_as(dp), nr.ctypes.data_as(dp), float(nglobal_scaled), C.byref(h), C.byref(vol)))
     return _take_csr(L, h, np.complex128), vol.value
 
 
