@@ -394,6 +394,29 @@ int wae_p2_assemble_boundary(int32_t device, int64_t npoints, const double *poin
 int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t nflame,
                           const int32_t *flame_tets, int32_t ref_tet, const double *x_ref, const double *n_ref, double nglobal_scaled, void **out,
                           double *volume_out);
+/* -- nodal speed of sound: K and C of the P1 and P2 spaces from one value per mesh point -----------------------------
+ * The second form of `C` in `discretize(mesh, dscrp, C; order)` (src/Helmholtz.jl:43,59-74): length(C) == size(mesh.points, 2), the
+ * speed of sound interpolated linearly between the vertices, generate_field(mesh, f; order=:lin).  On every simplex
+ *     c(x) = sum_p c_p l_p        (l: barycentric coordinates, c_p = c_point[corner p]; P2 uses the 4 resp. 3 corner points only)
+ * and the element matrices are those of `stiff` / `bound` (Helmholtz.jl:120-171: s43nv1nu1cc1, s43nv2nu2cc1, s33v1u1c1, s33v2u2c1),
+ * here from the monomial formula  int l^alpha = |det J| alpha! / (|alpha| + n - 1)!  -- exact polynomials, no quadrature:
+ *  - interior:  K_ab += -|det J| int c(x)^2 grad(phi_a).grad(phi_b);  M does not depend on c and is that of wae_p1_assemble / wae_p2_assemble.
+ *        P1: K_ab = -|det J| (grad l_a . grad l_b) ((sum_p c_p)^2 + sum_p c_p^2) / 120
+ *        P2: grad phi_a = sum_k l_k w_a[k]:  K_ab = -|det J| sum_km (w_a[k].w_b[m]) W_km,  W_km = sum_pq c_p c_q int l_k l_m l_p l_q  (/7!)
+ *  - admittance boundary:  b_ab = |(x0-x2) x (x1-x2)| int c(x) phi_a phi_b on the triangle, the operator term is C = -i b.
+ *        P1: b_aa = |..| (2 c_a + S)/60,  b_ab = |..| (c_a + c_b + S)/120,  S = c_1 + c_2 + c_3  (b_11 = |..| (c_1/20 + c_2/60 + c_3/60))
+ *        P2: degree-5 monomials on the 6-node triangle  (/7!)
+ * The local K_ab and K_ba, b_ab and b_ba get the same bits.  Arguments, index checks, pipeline (sorted triplets, no atomics, the same bits
+ * on every call) and handle type (wae_p1_info / wae_p1_get / wae_p1_free) are those of the per-simplex entry of the same name.
+ * c_point: npoints doubles, required: NULL or a value that is not finite returns WAE_ERR_INVALID and nothing is launched.
+ * Not covered: the shape sensitivity (wae_p1_shape_sensitivity* re-discretise with c_tet / c_tri), the speaker source vector (:m,
+ * source=true) and Hermite elements. */
+int wae_p1_assemble_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_point, void **out);
+int wae_p1_assemble_boundary_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_point,
+                                    void **out);
+int wae_p2_assemble_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_point, void **out);
+int wae_p2_assemble_boundary_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                                    const int32_t *tris, const double *c_point, void **out);
 /* Discrete-adjoint shape sensitivity (src/shape_sensitivity.jl:16-141) of an eigenvalue w.r.t. the coordinates of surface
  * points, for the interior (M, K) and the admittance-boundary (w*Y*C) parts of the P1 Helmholtz operator.  As in the
  * reference the operator derivative is a central difference (step h) of two local re-discretisations of the simplices

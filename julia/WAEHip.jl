@@ -1379,18 +1379,48 @@ function _take_p1(h::Ptr{Cvoid}, both::Bool)
     end
 end
 
-"M, K = assemble_p1(points, tets; c_tet, device): mass and stiffness (K = -c² ∫∇φ_a·∇φ_b, Helmholtz.jl:120-124,405-441) on the device"
-function assemble_p1(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; c_tet=nothing, device::Integer=0)
+"\"tet\" or \"point\": how `discretize` reads its speed-of-sound array (Helmholtz.jl:59-74) -- one value per tetrahedron, tested first (it wins
+when the two counts coincide), or one per mesh point, interpolated linearly between the vertices"
+function speed_of_sound_kind(c::AbstractVector, npoints::Integer, ntets::Integer)
+    length(c) == ntets && return "tet"
+    length(c) == npoints && return "point"
+    throw(ArgumentError("speed of sound: $(length(c)) values fit neither the $ntets tetrahedra nor the $npoints points"))
+end
+
+# the checked nodal field of the c_point keyword (one value per mesh point), or nothing if the per-simplex form is used
+function _nodal(c_point, c_simplex, npoints::Integer)
+    c_point === nothing && return nothing
+    c_simplex === nothing || throw(ArgumentError("give the speed of sound per point (c_point) or per simplex, not both"))
+    length(c_point) == npoints || throw(ArgumentError("c_point has $(length(c_point)) values, the mesh has $npoints points"))
+    return Vector{Float64}(c_point)
+end
+
+"M, K = assemble_p1(points, tets; c_tet, c_point, device): mass and stiffness (K = -∫c² ∇φ_a·∇φ_b, Helmholtz.jl:120-124,405-441) on the device;
+c_tet: speed of sound per tetrahedron, or c_point: per mesh point, linear on every tetrahedron (Helmholtz.jl:59-74)"
+function assemble_p1(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; c_tet=nothing, c_point=nothing, device::Integer=0)
     t0 = _zero_based(tets); h = Ref{Ptr{Cvoid}}(C_NULL)
+    cp = _nodal(c_point, c_tet, size(points, 2))
+    if cp !== nothing
+        check(ccall((:wae_p1_assemble_cpoint, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                    device, size(points, 2), points, size(t0, 2), t0, cp, h))
+        return _take_p1(h[], true)
+    end
     cc = c_tet === nothing ? C_NULL : Vector{Float64}(c_tet)
     check(ccall((:wae_p1_assemble, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
                 device, size(points, 2), points, size(t0, 2), t0, cc, h))
     return _take_p1(h[], true)
 end
 
-"C = assemble_p1_boundary(points, tris; c_tri, device): admittance-boundary operator -i c |e1×e2| (1+δ_ab)/24 (Helmholtz.jl:443-463)"
-function assemble_p1_boundary(points::Matrix{Float64}, tris::AbstractMatrix{<:Integer}; c_tri=nothing, device::Integer=0)
+"C = assemble_p1_boundary(points, tris; c_tri, c_point, device): admittance-boundary operator -i c |e1×e2| (1+δ_ab)/24 (Helmholtz.jl:443-463); with
+c_point (per mesh point) instead of c_tri: -i |e1×e2| ∫c φ_aφ_b, c linear on every triangle"
+function assemble_p1_boundary(points::Matrix{Float64}, tris::AbstractMatrix{<:Integer}; c_tri=nothing, c_point=nothing, device::Integer=0)
     t0 = _zero_based(tris); h = Ref{Ptr{Cvoid}}(C_NULL)
+    cp = _nodal(c_point, c_tri, size(points, 2))
+    if cp !== nothing
+        check(ccall((:wae_p1_assemble_boundary_cpoint, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                    device, size(points, 2), points, size(t0, 2), t0, cp, h))
+        return -1im .* _take_p1(h[], false)
+    end
     cc = c_tri === nothing ? C_NULL : Vector{Float64}(c_tri)
     check(ccall((:wae_p1_assemble_boundary, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
                 device, size(points, 2), points, size(t0, 2), t0, cc, h))
@@ -1427,18 +1457,34 @@ function p2_connectivity(npoints::Integer, tets::AbstractMatrix{<:Integer}, tris
     end
 end
 
-"M, K = assemble_p2(points, tets; c_tet, device): P2 mass and stiffness (Helmholtz.jl:120-149,405-441 with order=:quad), size npoints + nedges"
-function assemble_p2(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; c_tet=nothing, device::Integer=0)
+"M, K = assemble_p2(points, tets; c_tet, c_point, device): P2 mass and stiffness (Helmholtz.jl:120-149,405-441 with order=:quad), size
+npoints + nedges; c_tet or c_point as for assemble_p1"
+function assemble_p2(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; c_tet=nothing, c_point=nothing, device::Integer=0)
     t0 = _zero_based(tets); h = Ref{Ptr{Cvoid}}(C_NULL)
+    cp = _nodal(c_point, c_tet, size(points, 2))
+    if cp !== nothing
+        check(ccall((:wae_p2_assemble_cpoint, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                    device, size(points, 2), points, size(t0, 2), t0, cp, h))
+        return _take_p1(h[], true)
+    end
     cc = c_tet === nothing ? C_NULL : Vector{Float64}(c_tet)
     check(ccall((:wae_p2_assemble, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
                 device, size(points, 2), points, size(t0, 2), t0, cc, h))
     return _take_p1(h[], true)
 end
 
-"C = assemble_p2_boundary(points, tets, tris; c_tri, device): P2 admittance-boundary operator -i c |e1×e2| ∫φ_aφ_b (Helmholtz.jl:151-170,443-463)"
-function assemble_p2_boundary(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, tris::AbstractMatrix{<:Integer}; c_tri=nothing, device::Integer=0)
+"C = assemble_p2_boundary(points, tets, tris; c_tri, c_point, device): P2 admittance-boundary operator -i c |e1×e2| ∫φ_aφ_b (Helmholtz.jl:151-170,443-463);
+c_tri or c_point as for assemble_p1_boundary"
+function assemble_p2_boundary(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, tris::AbstractMatrix{<:Integer}; c_tri=nothing, c_point=nothing,
+                              device::Integer=0)
     t0 = _zero_based(tets); s0 = _zero_based(tris); h = Ref{Ptr{Cvoid}}(C_NULL)
+    cp = _nodal(c_point, c_tri, size(points, 2))
+    if cp !== nothing
+        check(ccall((:wae_p2_assemble_boundary_cpoint, libwaehip), Cint,
+                    (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                    device, size(points, 2), points, size(t0, 2), t0, size(s0, 2), s0, cp, h))
+        return -1im .* _take_p1(h[], false)
+    end
     cc = c_tri === nothing ? C_NULL : Vector{Float64}(c_tri)
     check(ccall((:wae_p2_assemble_boundary, libwaehip), Cint,
                 (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
@@ -1457,16 +1503,30 @@ function assemble_p2_flame(points::Matrix{Float64}, tets::AbstractMatrix{<:Integ
     return _take_p1(h[], false), vol[]
 end
 
-"M, K, C, Q, V_flame = discretize_device(points, tets; order, c_tet, bnd_tris, bnd_c, flame): the term matrices of `discretize` assembled on the
-device, order = :lin or :quad (Helmholtz.jl:36-54).  bnd_tris / bnd_c: admittance-boundary triangles and the speed of sound behind each;
-flame = (flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled).  Terms that were not asked for come back as `nothing`."
-function discretize_device(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; order::Symbol=:lin, c_tet=nothing, bnd_tris=nothing,
+"M, K, C, Q, V_flame = discretize_device(points, tets; order, c, c_tet, bnd_tris, bnd_c, flame): the term matrices of `discretize` assembled on the
+device, order = :lin or :quad (Helmholtz.jl:36-54).  c: the speed of sound as `discretize` takes it (Helmholtz.jl:59-74) -- one value per
+tetrahedron, or one per mesh point (then linear on every simplex, in K and in C; bnd_c is not used); c_tet = the first form alone.
+bnd_tris / bnd_c: admittance-boundary triangles and the speed of sound behind each; flame = (flame_tets, ref_tet, x_ref, n_ref,
+nglobal_scaled).  Terms that were not asked for come back as `nothing`."
+function discretize_device(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; order::Symbol=:lin, c=nothing, c_tet=nothing, bnd_tris=nothing,
                            bnd_c=nothing, flame=nothing, device::Integer=0)
     order in (:lin, :quad) || error("discretize_device: order must be :lin or :quad")
     quad = order == :quad
-    M, K = quad ? assemble_p2(points, tets; c_tet=c_tet, device=device) : assemble_p1(points, tets; c_tet=c_tet, device=device)
+    c_point = nothing
+    if c !== nothing
+        c_tet === nothing || throw(ArgumentError("discretize_device: give c or c_tet, not both"))
+        if speed_of_sound_kind(c, size(points, 2), size(tets, 2)) == "tet"
+            c_tet = c
+        else
+            c_point = c
+            bnd_c === nothing || throw(ArgumentError("discretize_device: with a nodal c the boundary term takes c from the mesh points, not bnd_c"))
+        end
+    end
+    M, K = quad ? assemble_p2(points, tets; c_tet=c_tet, c_point=c_point, device=device) :
+                  assemble_p1(points, tets; c_tet=c_tet, c_point=c_point, device=device)
     C = bnd_tris === nothing ? nothing :
-        quad ? assemble_p2_boundary(points, tets, bnd_tris; c_tri=bnd_c, device=device) : assemble_p1_boundary(points, bnd_tris; c_tri=bnd_c, device=device)
+        quad ? assemble_p2_boundary(points, tets, bnd_tris; c_tri=bnd_c, c_point=c_point, device=device) :
+               assemble_p1_boundary(points, bnd_tris; c_tri=bnd_c, c_point=c_point, device=device)
     Q = nothing; V = nothing
     if flame !== nothing
         flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled = flame

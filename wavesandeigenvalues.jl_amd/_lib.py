@@ -40,6 +40,7 @@ EXPORTS = [
     "wae_tall_create", "wae_tall_destroy", "wae_tall_info", "wae_tall_write", "wae_tall_read", "wae_tall_gram", "wae_tall_mul", "wae_tall_hankel",
     "wae_p2_connectivity", "wae_p2_connectivity_info", "wae_p2_connectivity_get", "wae_p2_connectivity_free", "wae_p2_assemble",
     "wae_p2_assemble_boundary", "wae_p2_assemble_flame",
+    "wae_p1_assemble_cpoint", "wae_p1_assemble_boundary_cpoint", "wae_p2_assemble_cpoint", "wae_p2_assemble_boundary_cpoint",
 ]
 TALL_MAXCOLS = 64           # WAE_TALL_MAXCOLS
 
@@ -127,6 +128,8 @@ def lib():
     L.wae_p2_assemble_boundary.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, dp, C.POINTER(C.c_void_p)]
     L.wae_p2_assemble_flame.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, C.c_int32, dp, dp, C.c_double,
                                         C.POINTER(C.c_void_p), dp]
+    for name in ("wae_p1_assemble", "wae_p1_assemble_boundary", "wae_p2_assemble", "wae_p2_assemble_boundary"):       # c_point in the place of c_tet / c_tri
+        getattr(L, name + "_cpoint").argtypes = getattr(L, name).argtypes
     L.wae_p1_shape_sensitivity.argtypes = [C.c_int32, C.c_int64, dp, i32p, dp, C.c_int64, i32p, i32p, i32p, dp, C.c_int64, i32p, i32p,
                                            C.c_int64, C.c_int64, dp, dp, dp, dp, C.c_double, dp, dp]
     L.wae_p1_shape_sensitivity_flame.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, i32p, C.c_int32, C.c_int64, i32p, dp, dp, dp,

@@ -56,6 +56,19 @@ __device__ inline void p1_local(const double X[4][3], double c, double M[16], do
         }
 }
 
+// the same with the speed of sound interpolated linearly between the corner values c[0..3] (generate_field(...; order=:lin) and
+// s43nv1nu1cc1 of the reference, Helmholtz.jl:59-74,120-124).  The gradients are constant on the tetrahedron, so c enters through
+//     int c^2 = |det J| sum_pq c_p c_q (1 + delta_pq)/120 = |det J| ((sum_p c_p)^2 + sum_p c_p^2)/120 :
+// K_ab = (-|det J|/6 grad_a.grad_b) ((sum c)^2 + sum c^2)/20, the first factor being what p1_local returns for c = 1.
+__device__ inline void p1_local_cpoint(const double X[4][3], const double c[4], double M[16], double K[16]) {
+    p1_local(X, 1.0, M, K);
+    const double s = (c[0] + c[1]) + (c[2] + c[3]);
+    double q = c[0] * c[0];
+    for (int p = 1; p < 4; ++p) q = fma(c[p], c[p], q);
+    const double w = fma(s, s, q) / 20.0;
+    for (int i = 0; i < 16; ++i) K[i] *= w;
+}
+
 // Discrete-adjoint shape sensitivity (src/shape_sensitivity.jl:16-141), interior part: for the pair (surface point p,
 // adjacent tetrahedron t) and coordinate x:  out = -v_adj_loc^H [ w^2 (M+ - M-) + (K+ - K-) ] v_loc / (2h), M+-/K+- the local
 // matrices with x_p moved by +-h (central difference of two local re-discretisations, as the reference does).
@@ -167,6 +180,30 @@ __global__ __launch_bounds__(256) void p1_local_kernel(const double *__restrict_
         }
 }
 
+// p1_local_kernel with the speed of sound given at the mesh points
+__global__ __launch_bounds__(256) void p1_local_cpoint_kernel(const double *__restrict__ pts, const int *__restrict__ tets,
+                                                              const double *__restrict__ c_point, int64_t nt, int64_t np,
+                                                              unsigned long long *__restrict__ keys, double *__restrict__ mv, double *__restrict__ kv) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    int v[4];
+    double X[4][3], c[4];
+    for (int a = 0; a < 4; ++a) {
+        v[a] = tets[t * 4 + a];
+        for (int k = 0; k < 3; ++k) X[a][k] = pts[(size_t)v[a] * 3 + k];
+        c[a] = c_point[v[a]];
+    }
+    double Ml[16], Kl[16];
+    p1_local_cpoint(X, c, Ml, Kl);
+    for (int a = 0; a < 4; ++a)
+        for (int b = 0; b < 4; ++b) {
+            const size_t o = (size_t)t * 16 + a * 4 + b;
+            keys[o] = (unsigned long long)v[a] * (unsigned long long)np + (unsigned long long)v[b];
+            mv[o] = Ml[a * 4 + b];
+            kv[o] = Kl[a * 4 + b];
+        }
+}
+
 __global__ __launch_bounds__(256) void gather_d_kernel(const double *__restrict__ src, const unsigned int *__restrict__ idx, double *__restrict__ dst, size_t n) {
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) dst[e] = src[idx[e]];
 }
@@ -251,6 +288,34 @@ __global__ __launch_bounds__(256) void p1_boundary_kernel(const double *__restri
             const size_t o = (size_t)t * 9 + a * 3 + b;
             keys[o] = (unsigned long long)v[a] * (unsigned long long)np + (unsigned long long)v[b];
             bv[o] = c * ((a == b ? 2.0 : 1.0) / 24.0) * det;
+        }
+}
+
+// the same with c interpolated linearly between the corner values (s33v1u1c1 of the reference, Helmholtz.jl:151-156): with
+// int l^alpha = alpha!/(|alpha| + 2)! on the triangle,  b_ab = |..| sum_p c_p int l_a l_b l_p:
+//     b_aa = |..| (2 c_a + S)/60,     b_ab = |..| (c_a + c_b + S)/120  (a != b),     S = c_1 + c_2 + c_3
+__global__ __launch_bounds__(256) void p1_boundary_cpoint_kernel(const double *__restrict__ pts, const int *__restrict__ tris,
+                                                                 const double *__restrict__ c_point, int64_t nt, int64_t np,
+                                                                 unsigned long long *__restrict__ keys, double *__restrict__ bv) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    int v[3];
+    double X[3][3], c[3];
+    for (int a = 0; a < 3; ++a) {
+        v[a] = tris[t * 3 + a];
+        for (int k = 0; k < 3; ++k) X[a][k] = pts[(size_t)v[a] * 3 + k];
+        c[a] = c_point[v[a]];
+    }
+    const double u0 = X[0][0] - X[2][0], u1 = X[0][1] - X[2][1], u2 = X[0][2] - X[2][2];
+    const double w0 = X[1][0] - X[2][0], w1 = X[1][1] - X[2][1], w2 = X[1][2] - X[2][2];
+    const double n0 = u1 * w2 - u2 * w1, n1 = u2 * w0 - u0 * w2, n2 = u0 * w1 - u1 * w0;
+    const double det = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+    const double S = c[0] + c[1] + c[2];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            const size_t o = (size_t)t * 9 + a * 3 + b;
+            keys[o] = (unsigned long long)v[a] * (unsigned long long)np + (unsigned long long)v[b];
+            bv[o] = (a == b ? (2.0 * c[a] + S) / 60.0 : ((c[a] + c[b]) + S) / 120.0) * det;          // (c_a + c_b) first: b_ab == b_ba
         }
 }
 
@@ -368,25 +433,38 @@ __global__ void shape_ref_kernel(const double *__restrict__ pts, const int *__re
 
 extern "C" {
 
-int wae_p1_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_tri, void **out) {
+// c: per triangle (NULL = 1), or per mesh point (nodal; required)
+static int p1_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c, bool nodal,
+                                void **out) {
     return wae_guarded([&]() {
         if (!(npoints > 0 && ntris > 0 && points && tris && out)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        if (nodal) check_c_point(npoints, c);
         for (int64_t i = 0; i < ntris * 3; ++i)
             if (tris[i] < 0 || tris[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "triangle refers to a point outside 0..npoints-1");
         HIP_CHECK(hipSetDevice(device));
-        const size_t ne = (size_t)ntris * 9;
-        Dev<double> dpts((size_t)npoints * 3), dc(c_tri ? (size_t)ntris : 1), bv(ne);
+        const size_t ne = (size_t)ntris * 9, nc = (size_t)(nodal ? npoints : ntris);
+        Dev<double> dpts((size_t)npoints * 3), dc(c ? nc : 1), bv(ne);
         Dev<int> dt((size_t)ntris * 3);
         Dev<unsigned long long> k0(ne);
         HIP_CHECK(hipMemcpy(dpts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dt.p, tris, (size_t)ntris * 3 * sizeof(int), hipMemcpyHostToDevice));
-        if (c_tri) HIP_CHECK(hipMemcpy(dc.p, c_tri, (size_t)ntris * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(p1_boundary_kernel, dim3((unsigned)((ntris + 255) / 256)), dim3(256), 0, 0, dpts.p, dt.p, c_tri ? dc.p : nullptr, ntris, npoints,
-                           k0.p, bv.p);
+        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
+        const dim3 grid((unsigned)((ntris + 255) / 256));
+        if (nodal) hipLaunchKernelGGL(p1_boundary_cpoint_kernel, grid, dim3(256), 0, 0, dpts.p, dt.p, dc.p, ntris, npoints, k0.p, bv.p);
+        else hipLaunchKernelGGL(p1_boundary_kernel, grid, dim3(256), 0, 0, dpts.p, dt.p, c ? dc.p : nullptr, ntris, npoints, k0.p, bv.p);
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(npoints, ne, k0, bv, nullptr);
         return WAE_OK;
     });
+}
+
+int wae_p1_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_tri, void **out) {
+    return p1_assemble_boundary(device, npoints, points, ntris, tris, c_tri, false, out);
+}
+
+int wae_p1_assemble_boundary_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_point,
+                                    void **out) {
+    return p1_assemble_boundary(device, npoints, points, ntris, tris, c_point, true, out);
 }
 
 int wae_p1_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t nflame,
@@ -449,26 +527,37 @@ int wae_p1_assemble_flame(int32_t device, int64_t npoints, const double *points,
     });
 }
 
-int wae_p1_assemble(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_tet, void **out) {
+static int p1_assemble_interior(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c, bool nodal,
+                                void **out) {
     return wae_guarded([&]() {
         if (!(npoints > 0 && ntets > 0 && points && tets && out)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        if (nodal) check_c_point(npoints, c);
         if ((size_t)ntets * 16 >= 0xffffffffull) throw WaeError(WAE_ERR_INVALID, "too many tetrahedra for 32-bit triplet indices");
         for (int64_t i = 0; i < ntets * 4; ++i)
             if (tets[i] < 0 || tets[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "tetrahedron refers to a point outside 0..npoints-1");
         HIP_CHECK(hipSetDevice(device));
-        const size_t ne = (size_t)ntets * 16;
-        Dev<double> dpts((size_t)npoints * 3), dc(c_tet ? (size_t)ntets : 1), mv(ne), kv(ne);
+        const size_t ne = (size_t)ntets * 16, nc = (size_t)(nodal ? npoints : ntets);
+        Dev<double> dpts((size_t)npoints * 3), dc(c ? nc : 1), mv(ne), kv(ne);
         Dev<int> dt((size_t)ntets * 4);
         Dev<unsigned long long> k0(ne);
         HIP_CHECK(hipMemcpy(dpts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dt.p, tets, (size_t)ntets * 4 * sizeof(int), hipMemcpyHostToDevice));
-        if (c_tet) HIP_CHECK(hipMemcpy(dc.p, c_tet, (size_t)ntets * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(p1_local_kernel, dim3((unsigned)((ntets + 255) / 256)), dim3(256), 0, 0, dpts.p, dt.p, c_tet ? dc.p : nullptr, ntets, npoints,
-                           k0.p, mv.p, kv.p);
+        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
+        const dim3 grid((unsigned)((ntets + 255) / 256));
+        if (nodal) hipLaunchKernelGGL(p1_local_cpoint_kernel, grid, dim3(256), 0, 0, dpts.p, dt.p, dc.p, ntets, npoints, k0.p, mv.p, kv.p);
+        else hipLaunchKernelGGL(p1_local_kernel, grid, dim3(256), 0, 0, dpts.p, dt.p, c ? dc.p : nullptr, ntets, npoints, k0.p, mv.p, kv.p);
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(npoints, ne, k0, mv, &kv);
         return WAE_OK;
     });
+}
+
+int wae_p1_assemble(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_tet, void **out) {
+    return p1_assemble_interior(device, npoints, points, ntets, tets, c_tet, false, out);
+}
+
+int wae_p1_assemble_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_point, void **out) {
+    return p1_assemble_interior(device, npoints, points, ntets, tets, c_point, true, out);
 }
 
 int wae_p1_shape_sensitivity(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_tet, int64_t npair_t,

@@ -46,9 +46,8 @@ template <int NV> struct P2Basis {
 
 constexpr long long p2_factorial(int n) { return n <= 1 ? 1 : n * p2_factorial(n - 1); }
 
-template <int NV> constexpr P2Basis<NV> make_p2_basis() {
-    constexpr int NN = P2Basis<NV>::NN;
-    int q2[NN][NV][NV] = {};
+// phi_a = 1/2 sum_kl q2[a][k][l] l_k l_l
+template <int NV> constexpr void p2_quadratic_forms(int (&q2)[NV + NV * (NV - 1) / 2][NV][NV]) {
     for (int a = 0; a < NV; ++a)                  // l_a (2 l_a - sum_k l_k) = l_a^2 - sum_{k != a} l_a l_k
         for (int k = 0; k < NV; ++k) {
             if (k == a) q2[a][a][a] = 2;
@@ -57,6 +56,12 @@ template <int NV> constexpr P2Basis<NV> make_p2_basis() {
     int a = NV;
     for (int i = 0; i < NV; ++i)
         for (int j = i + 1; j < NV; ++j, ++a) q2[a][i][j] = q2[a][j][i] = 4;      // 4 l_i l_j
+}
+
+template <int NV> constexpr P2Basis<NV> make_p2_basis() {
+    constexpr int NN = P2Basis<NV>::NN;
+    int q2[NN][NV][NV] = {};
+    p2_quadratic_forms<NV>(q2);
     P2Basis<NV> B = {};
     for (int r = 0; r < NN; ++r) {
         long long s = 0;
@@ -88,6 +93,55 @@ constexpr P2Basis<4> kTet = make_p2_basis<4>();
 constexpr P2Basis<3> kTri = make_p2_basis<3>();
 __constant__ P2Basis<4> dTet = kTet;
 __constant__ P2Basis<3> dTri = kTri;
+
+// Tables of the nodal speed of sound, c(x) = sum_p c_p l_p on every simplex (the *_cpoint entries), from the same monomial formula.
+//   quart[km][pq] = (2 - delta_pq) int l_k l_m l_p l_q / |det J|  on the tetrahedron (denominator 7!), the unordered pairs k <= m and
+//                   p <= q numbered (0,0), (0,1), (0,2), (0,3), (1,1), (1,2), (1,3), (2,2), (2,3), (3,3):
+//                   W_km = int c^2 l_k l_m / |det J| = sum_{p<=q} c_p c_q quart[km][pq]
+//   tri[p][a][b]  = int l_p phi_a phi_b / |(x0-x2) x (x1-x2)|  on the 6-node triangle (degree 5, denominator 7!)
+struct P2NodalC {
+    double quart[10][10];
+    double tri[3][6][6];
+};
+
+constexpr P2NodalC make_p2_nodal_c() {
+    P2NodalC T = {};
+    int km = 0;
+    for (int k = 0; k < 4; ++k)
+        for (int m = k; m < 4; ++m, ++km) {
+            int pq = 0;
+            for (int p = 0; p < 4; ++p)
+                for (int q = p; q < 4; ++q, ++pq) {
+                    int cnt[4] = {};
+                    ++cnt[k]; ++cnt[m]; ++cnt[p]; ++cnt[q];
+                    long long mono = p == q ? 1 : 2;
+                    for (int v = 0; v < 4; ++v) mono *= p2_factorial(cnt[v]);
+                    T.quart[km][pq] = (double)mono / (double)p2_factorial(7);
+                }
+        }
+    int q2[6][3][3] = {};
+    p2_quadratic_forms<3>(q2);
+    for (int p = 0; p < 3; ++p)
+        for (int r = 0; r < 6; ++r)
+            for (int c = 0; c < 6; ++c) {
+                long long num = 0;
+                for (int k = 0; k < 3; ++k)
+                    for (int l = 0; l < 3; ++l)
+                        for (int m = 0; m < 3; ++m)
+                            for (int n = 0; n < 3; ++n) {
+                                int cnt[3] = {};
+                                ++cnt[p]; ++cnt[k]; ++cnt[l]; ++cnt[m]; ++cnt[n];
+                                long long mono = 1;
+                                for (int v = 0; v < 3; ++v) mono *= p2_factorial(cnt[v]);
+                                num += (long long)q2[r][k][l] * q2[c][m][n] * mono;
+                            }
+                T.tri[p][r][c] = (double)num / (double)(4 * p2_factorial(7));
+            }
+    return T;
+}
+
+constexpr P2NodalC kNodalC = make_p2_nodal_c();
+__constant__ P2NodalC dNodalC = kNodalC;
 
 // G[a] = grad l_a of the tetrahedron with corners X (l_4 = 1 - l_1 - l_2 - l_3, corner 4 is the origin: CooTrafo, FEM.jl:9-20); returns det J
 __host__ __device__ inline double p2_tet_gradients(const double X[4][3], double G[4][3]) {
@@ -244,6 +298,116 @@ __global__ __launch_bounds__(256) void p2_boundary_kernel(const double *__restri
     }
 }
 
+// ---- element kernels, speed of sound given at the mesh points ---------------------------------------------------------------------------
+// c(x) = sum_p c_p l_p with the 4 (3) corner values of the simplex (generate_field(...; order=:lin); s43nv2nu2cc1 and s33v2u2c1 of the
+// reference, Helmholtz.jl:59-74,120-171).  Every integral is a polynomial in l and exact: no quadrature.
+//
+// row a of tetrahedron t, M as in p2_local_kernel and, with grad phi_a = sum_k l_k w_a[k] and the symmetric W_km = int c^2 l_k l_m / |det J|,
+//     K_ab = -|det J| sum_{k<=m} d_km W_km,   d_kk = w_a[k].w_b[k],   d_km = w_a[k].w_b[m] + w_a[m].w_b[k]  (k < m).
+// Every dot product runs in one fixed order and d_km adds the two of a pair first, so K_ab and K_ba get the same bits -- as long as the
+// compiler rounds where the source does.  Two contractions would break that, and both are shut out:
+//  - of one dot product of a pair into the other's fma chain (fadd (fma x, y, (fmul u, v)), z -> fma x, y, (fma u, v, z)), which of the
+//    two depending on the side: contract(off) in this kernel;
+//  - of grad l_i = cofactor / det J into the sums of p2_grad_coeffs: for the column's function b is a constant, the compiler knows the
+//    table entries (0, -1, 2, 4), turns fma(-1, G, x) into x - G and fuses the product that made G into it, while the row's function,
+//    picked at run time, keeps the rounded G.  The gradients therefore pass through p2_opaque before they are used.
+__device__ inline double p2_opaque(double x) {
+    asm volatile("" : "+v"(x));          // no instruction: only hides where x came from
+    return x;
+}
+__device__ inline double p2_dot3(const double x[3], const double y[3]) {
+#pragma clang fp contract(off)
+    return fma(x[2], y[2], fma(x[1], y[1], x[0] * y[0]));
+}
+
+__global__ __launch_bounds__(256) void p2_local_cpoint_kernel(const double *__restrict__ pts, const int *__restrict__ t10,
+                                                              const double *__restrict__ c_point, int64_t nt, u64 dim, u64 *__restrict__ keys,
+                                                              double *__restrict__ mv, double *__restrict__ kv) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= nt * 10) return;
+    const int64_t t = e / 10;
+    const int a = (int)(e - t * 10);
+    int nd[10];
+#pragma unroll
+    for (int b = 0; b < 10; ++b) nd[b] = t10[t * 10 + b];
+    double X[4][3], G[4][3], cc[10], W[10];
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+        for (int k = 0; k < 3; ++k) X[v][k] = pts[(size_t)nd[v] * 3 + k];
+    {
+        double c[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) c[v] = c_point[nd[v]];
+        int pq = 0;
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int q = p; q < 4; ++q, ++pq) cc[pq] = c[p] * c[q];
+    }
+#pragma unroll
+    for (int km = 0; km < 10; ++km) {
+        double x = cc[0] * dNodalC.quart[km][0];
+#pragma unroll
+        for (int pq = 1; pq < 10; ++pq) x = fma(cc[pq], dNodalC.quart[km][pq], x);
+        W[km] = x;
+    }
+    const double nadet = -fabs(p2_tet_gradients(X, G));
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+        for (int k = 0; k < 3; ++k) G[v][k] = p2_opaque(G[v][k]);
+    double wa[4][3], sa[3];
+    p2_grad_coeffs(dTet.d[a], G, wa, sa);
+    const u64 row = (u64)t10[t * 10 + a] * dim;
+#pragma unroll
+    for (int b = 0; b < 10; ++b) {
+        double wb[4][3], sb[3];
+        p2_grad_coeffs(dTet.d[b], G, wb, sb);
+        double acc = 0.0;
+        int km = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int m = k; m < 4; ++m, ++km) {
+                const double d = k == m ? p2_dot3(wa[k], wb[k]) : p2_dot3(wa[k], wb[m]) + p2_dot3(wa[m], wb[k]);
+                acc = km == 0 ? d * W[0] : fma(d, W[km], acc);
+            }
+        const size_t o = (size_t)e * 10 + b;
+        keys[o] = row + (u64)nd[b];
+        mv[o] = -nadet * dTet.mass[a][b];
+        kv[o] = nadet * acc;
+    }
+}
+
+// row a of triangle t: b_ab = |(x0-x2) x (x1-x2)| sum_p c_p int l_p phi_a phi_b; the table is symmetric in (a, b) and p runs in one order
+__global__ __launch_bounds__(256) void p2_boundary_cpoint_kernel(const double *__restrict__ pts, const int *__restrict__ s6,
+                                                                 const double *__restrict__ c_point, int64_t ns, u64 dim, u64 *__restrict__ keys,
+                                                                 double *__restrict__ bv) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= ns * 6) return;
+    const int64_t t = e / 6;
+    const int a = (int)(e - t * 6);
+    int nd[6];
+#pragma unroll
+    for (int b = 0; b < 6; ++b) nd[b] = s6[t * 6 + b];
+    double X[3][3];
+#pragma unroll
+    for (int v = 0; v < 3; ++v)
+        for (int k = 0; k < 3; ++k) X[v][k] = pts[(size_t)nd[v] * 3 + k];
+    const double c0 = c_point[nd[0]], c1 = c_point[nd[1]], c2 = c_point[nd[2]];
+    const double u0 = X[0][0] - X[2][0], u1 = X[0][1] - X[2][1], u2 = X[0][2] - X[2][2];
+    const double w0 = X[1][0] - X[2][0], w1 = X[1][1] - X[2][1], w2 = X[1][2] - X[2][2];
+    const double n0 = u1 * w2 - u2 * w1, n1 = u2 * w0 - u0 * w2, n2 = u0 * w1 - u1 * w0;
+    const double det = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+    const u64 row = (u64)s6[t * 6 + a] * dim;
+#pragma unroll
+    for (int b = 0; b < 6; ++b) {
+        const size_t o = (size_t)e * 6 + b;
+        keys[o] = row + (u64)nd[b];
+        bv[o] = det * fma(c2, dNodalC.tri[2][a][b], fma(c1, dNodalC.tri[1][a][b], c0 * dNodalC.tri[0][a][b]));
+    }
+}
+
 // |det J| of the listed tetrahedra (flame volume = sum |det J| / 6)
 __global__ __launch_bounds__(256) void p2_det_kernel(const double *__restrict__ pts, const int *__restrict__ t10, const int *__restrict__ list, int64_t n,
                                                      double *__restrict__ adet) {
@@ -389,41 +553,65 @@ int wae_p2_connectivity_free(void *handle) {
     return WAE_OK;
 }
 
-int wae_p2_assemble(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_tet, void **out) {
+// c: per tetrahedron (NULL = 1), or per mesh point (nodal; required)
+static int p2_assemble_interior(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c, bool nodal,
+                                void **out) {
     return wae_guarded([&]() {
         if (!(points && out)) throw WaeError(WAE_ERR_INVALID, "bad argument");
         p2_check_mesh(npoints, ntets, tets, 0, nullptr);
+        if (nodal) check_c_point(npoints, c);
         HIP_CHECK(hipSetDevice(device));
         P2Mesh m(npoints, points, ntets, tets, 0, nullptr);
-        const size_t ne = (size_t)ntets * 100;
-        Dev<double> dc(c_tet ? (size_t)ntets : 1), mv(ne), kv(ne);
+        const size_t ne = (size_t)ntets * 100, nc = (size_t)(nodal ? npoints : ntets);
+        Dev<double> dc(c ? nc : 1), mv(ne), kv(ne);
         Dev<u64> k0(ne);
-        if (c_tet) HIP_CHECK(hipMemcpy(dc.p, c_tet, (size_t)ntets * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(p2_local_kernel, dim3((unsigned)((ntets * 10 + 255) / 256)), dim3(256), 0, 0, m.pts.p, m.t10.p, c_tet ? dc.p : nullptr, ntets,
-                           (u64)m.dim, k0.p, mv.p, kv.p);
+        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
+        const dim3 grid((unsigned)((ntets * 10 + 255) / 256));
+        if (nodal) hipLaunchKernelGGL(p2_local_cpoint_kernel, grid, dim3(256), 0, 0, m.pts.p, m.t10.p, dc.p, ntets, (u64)m.dim, k0.p, mv.p, kv.p);
+        else hipLaunchKernelGGL(p2_local_kernel, grid, dim3(256), 0, 0, m.pts.p, m.t10.p, c ? dc.p : nullptr, ntets, (u64)m.dim, k0.p, mv.p, kv.p);
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(m.dim, ne, k0, mv, &kv);
         return WAE_OK;
     });
 }
 
-int wae_p2_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
-                             const int32_t *tris, const double *c_tri, void **out) {
+static int p2_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                                const int32_t *tris, const double *c, bool nodal, void **out) {
     return wae_guarded([&]() {
         if (!(points && out && ntris > 0)) throw WaeError(WAE_ERR_INVALID, "bad argument");
         p2_check_mesh(npoints, ntets, tets, ntris, tris);
+        if (nodal) check_c_point(npoints, c);
         HIP_CHECK(hipSetDevice(device));
         P2Mesh m(npoints, points, ntets, tets, ntris, tris);
-        const size_t ne = (size_t)ntris * 36;
-        Dev<double> dc(c_tri ? (size_t)ntris : 1), bv(ne);
+        const size_t ne = (size_t)ntris * 36, nc = (size_t)(nodal ? npoints : ntris);
+        Dev<double> dc(c ? nc : 1), bv(ne);
         Dev<u64> k0(ne);
-        if (c_tri) HIP_CHECK(hipMemcpy(dc.p, c_tri, (size_t)ntris * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(p2_boundary_kernel, dim3((unsigned)((ntris * 6 + 255) / 256)), dim3(256), 0, 0, m.pts.p, m.s6.p, c_tri ? dc.p : nullptr, ntris,
-                           (u64)m.dim, k0.p, bv.p);
+        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
+        const dim3 grid((unsigned)((ntris * 6 + 255) / 256));
+        if (nodal) hipLaunchKernelGGL(p2_boundary_cpoint_kernel, grid, dim3(256), 0, 0, m.pts.p, m.s6.p, dc.p, ntris, (u64)m.dim, k0.p, bv.p);
+        else hipLaunchKernelGGL(p2_boundary_kernel, grid, dim3(256), 0, 0, m.pts.p, m.s6.p, c ? dc.p : nullptr, ntris, (u64)m.dim, k0.p, bv.p);
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(m.dim, ne, k0, bv, nullptr);
         return WAE_OK;
     });
+}
+
+int wae_p2_assemble(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_tet, void **out) {
+    return p2_assemble_interior(device, npoints, points, ntets, tets, c_tet, false, out);
+}
+
+int wae_p2_assemble_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_point, void **out) {
+    return p2_assemble_interior(device, npoints, points, ntets, tets, c_point, true, out);
+}
+
+int wae_p2_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                             const int32_t *tris, const double *c_tri, void **out) {
+    return p2_assemble_boundary(device, npoints, points, ntets, tets, ntris, tris, c_tri, false, out);
+}
+
+int wae_p2_assemble_boundary_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                                    const int32_t *tris, const double *c_point, void **out) {
+    return p2_assemble_boundary(device, npoints, points, ntets, tets, ntris, tris, c_point, true, out);
 }
 
 int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t nflame,

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <complex>
 #include <cstdint>
 #include <cstdio>
@@ -254,6 +255,12 @@ template <class T> struct Dev {     // function-local device array of the assemb
 };
 // keyed triplets (key = row * npoints + col, ne of them with ne <= INT_MAX; one or two value streams) -> CSR of npoints rows
 P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k0, Dev<double> &mv, Dev<double> *kv);
+// the nodal speed of sound of the *_cpoint entries: required, one finite value per mesh point (checked before anything is launched)
+inline void check_c_point(int64_t npoints, const double *c_point) {
+    if (!c_point) throw WaeError(WAE_ERR_INVALID, "c_point is required: one speed of sound per mesh point");
+    for (int64_t i = 0; i < npoints; ++i)
+        if (!std::isfinite(c_point[i])) throw WaeError(WAE_ERR_INVALID, "c_point holds a value that is not finite");
+}
 
 // kernel launch wrappers: operator, transfer and dense level (kernels.hip) ------------------------------
 enum { MODE_AX = 0, MODE_RES = 1, MODE_JAC = 2, MODE_ADD = 3, MODE_AX_DS = 4, MODE_RES_DS = 5, MODE_AX_J0 = 6 };

@@ -10,17 +10,43 @@ import scipy.sparse as sp
 from .. import _lib
 
 
-def assemble_p1(points, tets, c_tet=None, device=0, dtype=np.complex128):
-    """points (npoints, 3), tets (ntets, 4) 0-based, c_tet (ntets,) speed of sound per tetrahedron (None = 1).
-    Returns (M, K) as scipy CSR matrices sharing one pattern; K = -c² ∫ ∇φ_a·∇φ_b as in the reference (Helmholtz.jl:120-124)."""
+def speed_of_sound_kind(C, npoints, ntets):
+    """"tet" or "point": how ``discretize`` reads its speed-of-sound array (Helmholtz.jl:59-74) -- one value per tetrahedron, tested first
+    (it wins when the two counts coincide), or one per mesh point, interpolated linearly.  Any other length is a ValueError."""
+    n = len(C)
+    if n == ntets:
+        return "tet"
+    if n == npoints:
+        return "point"
+    raise ValueError(f"speed of sound: {n} values fit neither the {ntets} tetrahedra nor the {npoints} points")
+
+
+def _nodal(c_point, c_simplex, npoints, what):
+    """the checked nodal field of the c_point= keyword (one value per mesh point), or None if the per-simplex form is used"""
+    if c_point is None:
+        return None
+    if c_simplex is not None:
+        raise ValueError(f"give the speed of sound per point (c_point) or per simplex ({what}), not both")
+    cp = np.ascontiguousarray(c_point, dtype=np.float64)
+    if cp.shape != (npoints,):
+        raise ValueError(f"c_point has shape {cp.shape}, the mesh has {npoints} points")
+    return cp
+
+
+def assemble_p1(points, tets, c_tet=None, device=0, dtype=np.complex128, c_point=None):
+    """points (npoints, 3), tets (ntets, 4) 0-based, c_tet (ntets,) speed of sound per tetrahedron (None = 1) or c_point (npoints,)
+    speed of sound per mesh point, linear on every tetrahedron (wae_p1_assemble_cpoint; Helmholtz.jl:59-74).
+    Returns (M, K) as scipy CSR matrices sharing one pattern; K = -∫ c² ∇φ_a·∇φ_b as in the reference (Helmholtz.jl:120-124)."""
     pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
     tt = np.ascontiguousarray(tets, dtype=np.int32).reshape(-1, 4)
-    cc = None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
+    cp = _nodal(c_point, c_tet, pts.shape[0], "c_tet")
+    cc = cp if cp is not None else None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
     L = _lib.lib()
     h = C.c_void_p()
     dp = C.POINTER(C.c_double)
-    _lib.check(L.wae_p1_assemble(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
-                                 None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
+    entry = L.wae_p1_assemble if cp is None else L.wae_p1_assemble_cpoint
+    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
+                     None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
     return _take_pair(L, h, dtype)
 
 
@@ -57,17 +83,20 @@ def _take_csr(L, h, dtype):
     return sp.csr_matrix((v.astype(dtype), col, rowptr), shape=(n.value, n.value))
 
 
-def assemble_p1_boundary(points, tris, c_tri=None, device=0):
+def assemble_p1_boundary(points, tris, c_tri=None, device=0, c_point=None):
     """Boundary mass term of an admittance boundary on the device (wae_p1_assemble_boundary):
-    C = -i·c·|e1×e2|·(1+δ_ab)/24 per boundary triangle (src/Helmholtz.jl:443-463, src/FEM/FEM.jl:435-441).  Returns C (complex CSR)."""
+    C = -i·c·|e1×e2|·(1+δ_ab)/24 per boundary triangle (src/Helmholtz.jl:443-463, src/FEM/FEM.jl:435-441); with c_point (npoints,)
+    instead of c_tri, C = -i·|e1×e2|·∫c φ_aφ_b with c linear on every triangle (wae_p1_assemble_boundary_cpoint).  Returns C (complex CSR)."""
     pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
     tt = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
-    cc = None if c_tri is None else np.ascontiguousarray(c_tri, dtype=np.float64)
+    cp = _nodal(c_point, c_tri, pts.shape[0], "c_tri")
+    cc = cp if cp is not None else None if c_tri is None else np.ascontiguousarray(c_tri, dtype=np.float64)
     L = _lib.lib()
     h = C.c_void_p()
     dp = C.POINTER(C.c_double)
-    _lib.check(L.wae_p1_assemble_boundary(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
-                                          None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
+    entry = L.wae_p1_assemble_boundary if cp is None else L.wae_p1_assemble_boundary_cpoint
+    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
+                     None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
     return -1j * _take_csr(L, h, np.complex128)
 
 
@@ -120,31 +149,36 @@ def p2_connectivity(points, tets, tris=None, device=0):
     return edges, t10, t6
 
 
-def assemble_p2(points, tets, c_tet=None, device=0, dtype=np.complex128):
-    """P2 mass and stiffness matrices on the device (wae_p2_assemble; src/Helmholtz.jl:120-149,405-441 with order=:quad), arguments as
-    ``assemble_p1``.  Returns (M, K) as scipy CSR matrices of size npoints + nedges sharing one pattern."""
+def assemble_p2(points, tets, c_tet=None, device=0, dtype=np.complex128, c_point=None):
+    """P2 mass and stiffness matrices on the device (wae_p2_assemble, wae_p2_assemble_cpoint; src/Helmholtz.jl:120-149,405-441 with
+    order=:quad), arguments as ``assemble_p1``.  Returns (M, K) as scipy CSR matrices of size npoints + nedges sharing one pattern."""
     pts, tt, _ = _mesh_args(points, tets)
-    cc = None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
-    assert cc is None or cc.shape == (tt.shape[0],)
+    cp = _nodal(c_point, c_tet, pts.shape[0], "c_tet")
+    cc = cp if cp is not None else None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
+    assert cp is not None or cc is None or cc.shape == (tt.shape[0],)
     L = _lib.lib()
     h = C.c_void_p()
     dp = C.POINTER(C.c_double)
-    _lib.check(L.wae_p2_assemble(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
-                                 None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
+    entry = L.wae_p2_assemble if cp is None else L.wae_p2_assemble_cpoint
+    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
+                     None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
     return _take_pair(L, h, dtype)
 
 
-def assemble_p2_boundary(points, tets, tris, c_tri=None, device=0):
+def assemble_p2_boundary(points, tets, tris, c_tri=None, device=0, c_point=None):
     """P2 boundary mass term of an admittance boundary on the device (wae_p2_assemble_boundary; src/Helmholtz.jl:151-170,443-463):
-    C = -i·c·|e1×e2|·∫φ_aφ_b on the 6-node triangles; ``tets`` gives the edge numbers.  Returns C (complex CSR, npoints + nedges)."""
+    C = -i·c·|e1×e2|·∫φ_aφ_b on the 6-node triangles; ``tets`` gives the edge numbers; with c_point (npoints,) instead of c_tri, c is
+    linear on every triangle and under the integral (wae_p2_assemble_boundary_cpoint).  Returns C (complex CSR, npoints + nedges)."""
     pts, tt, tr = _mesh_args(points, tets, tris)
-    cc = None if c_tri is None else np.ascontiguousarray(c_tri, dtype=np.float64)
-    assert cc is None or cc.shape == (tr.shape[0],)
+    cp = _nodal(c_point, c_tri, pts.shape[0], "c_tri")
+    cc = cp if cp is not None else None if c_tri is None else np.ascontiguousarray(c_tri, dtype=np.float64)
+    assert cp is not None or cc is None or cc.shape == (tr.shape[0],)
     L = _lib.lib()
     h = C.c_void_p()
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    _lib.check(L.wae_p2_assemble_boundary(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), tr.shape[0],
-                                          tr.ctypes.data_as(ip), None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
+    entry = L.wae_p2_assemble_boundary if cp is None else L.wae_p2_assemble_boundary_cpoint
+    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), tr.shape[0],
+                     tr.ctypes.data_as(ip), None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
     return -1j * _take_csr(L, h, np.complex128)
 
 
