@@ -557,6 +557,36 @@ enum {
 int wae_debug_vec(int32_t device, int32_t op, const int64_t *sz, int32_t nsz, double *const *bufs, const int64_t *lens, int32_t nbuf,
                   const uint8_t *cmask, const int32_t *perm, int32_t *status_out);
 
+/* The small-matrix half of the lock-step GMRES (vec.hip gmres_init / step / rescale / clear_rescale / pair_coef / solve_y kernels):
+ * a SCRIPT of events against one recurrence state, each event the launcher calls the solver issues for it, so that tests/ can
+ * compare the Hessenberg columns, rotations, residual estimates, masks and pair coefficients with references of their own.  Needs no
+ * family and no solver set-up: the state is allocated for (nb, m, histcap) as the solver lays it out (integer block zeroed, bnorm[nb]
+ * from the caller, Hraw and sub present), the caller's arrays are uploaded to `device`, the events run on a stream of their own,
+ * everything is copied back and the stream synchronised.
+ *   ev[4 e ..]   kind (WAE_GMRES_* below), j (SOLVE_Y: ju), use_mask, offset of the event's arrays in `pool`;  evd[2 e ..]  tol, lim
+ *   pool         plen complex128 entries, in and out; an event's arrays lie back to back from its offset ([rows][nb], entry (i, b) at
+ *                i*nb + b; vectors [n][nb] alike):
+ *     INIT     beta[nb] done[nb] (real part non-zero = done)                        launch_gmres_init
+ *     STEP     hd[j+2][nb] Vnew[n][nb]                                              launch_gmres_step (step, rescale, clear_rescale);
+ *              row j+1 of vsq is set to 1/hd[j+1]^2 first, as the fused update writes it in the solver
+ *     PAIR     c1[j+1][nb] c2[j+1][nb] gram[3][nb] norms[2][nb] W1[n][nb] W2[n][nb] alpha[nb] c2m[j+1][nb] hd2[j+2][nb]
+ *              launch_gmres_pair_coef (writes alpha, c2m, hd2), rows j+1, j+2 of vsq set to 1/norms^2, then the two steps of the
+ *              solver's pair branch: (c1, j, lim 1e300, norm norms[0]) on W1 and (hd2, j+1, lim, norm norms[1]) on W2
+ *     SOLVE_Y  out[m][nb]: launch_gmres_solve_y(ju) writes rows below max(ju, steps[b]) of column b
+ *   cstate       complex128, in and out: R[m][m+1][nb] sn[m][nb] g[m+1][nb] vsq[m+2][nb] Hraw[m][m+1][nb] back to back
+ *   dstate       double, in and out: cs[m][nb] sv[m+2][nb] sub[m][nb] hist[histcap][nb]  (what the kernels do not write keeps the
+ *                caller's values)
+ *   after EVERY event e:  snap_relres[e][nb];  snap_int[e][5 nb + 4] = conv steps iters histlen stalled [nb each], status[0..2] (active
+ *                columns, NaN seen, renormalisation pending) and one unused word;  snap_cmask[e][(nb+7)/8];  snap_rescale[e][nb]
+ *                (complex128);  snap_sv[e][2][nb] and snap_vsq[e][2][nb] (complex128): the rows the event wrote (INIT: row 0; STEP: row
+ *                j+1; PAIR: rows j+1, j+2; unused rows 0).
+ *   nb outside 1..256, m < 1, a j outside the cycle (STEP: 0 <= j < m; PAIR: j + 2 <= m; SOLVE_Y: 1 <= ju <= m), an unknown event or
+ *   arrays that do not fit the pool: WAE_ERR_INVALID before anything is uploaded or launched. */
+enum { WAE_GMRES_INIT = 0, WAE_GMRES_STEP, WAE_GMRES_PAIR, WAE_GMRES_SOLVE_Y };
+int wae_debug_gmres(int32_t device, int32_t nb, int32_t m, int32_t histcap, int64_t n, const double *bnorm, const int64_t *ev,
+                    const double *evd, int32_t nev, double *pool, int64_t plen, double *cstate, double *dstate, double *snap_relres,
+                    int32_t *snap_int, uint8_t *snap_cmask, double *snap_rescale, double *snap_sv, double *snap_vsq);
+
 #ifdef __cplusplus
 }
 #endif

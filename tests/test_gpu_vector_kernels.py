@@ -1,7 +1,9 @@
 """Every streaming and reduction kernel under the lock-step GMRES, the snapshot basis, the Beyn accumulation, the batched
 perturbation and the dense coarse level, ONE launch at a time (wae_debug_vec) against the extended-precision references of
 tests/_vecref.py.  GMRES corrects itself: a dropped row, a skipped basis vector or a wrong pivot only costs iterations in the whole
-solves the rest of the suite runs, so these are the tests that pin each kernel to its defining formula.
+solves the rest of the suite runs, so these are the tests that pin each kernel to its defining formula.  The recurrence kernels
+between them (gmres_init, gmres_step, gmres_rescale, gmres_pair_coef, gmres_solve_y: Hessenberg columns, rotations, residual
+estimates, chunk masks) are pinned the same way by tests/test_gpu_gmres_recurrence.py (wae_debug_gmres, tests/_gmresref.py).
 
 Tolerances are rounding bounds of float64 arithmetic, not measured numbers:
   reductions   |gpu - ref| <= 2 (n + 4) eps sum_rows |v||w|                       per output entry

@@ -36,7 +36,7 @@ _lib = None
 EXPORTS = [
     "wae_last_error", "wae_device_count", "wae_version", "wae_family_create", "wae_family_create_opts", "wae_family_destroy",
     "wae_family_info", "wae_family_spmv_bytes", "wae_spmv_sum", "wae_spmv_sum_cols", "wae_spmv_sum_multi", "wae_solver_setup",
-    "wae_solve", "wae_solve_guess", "wae_beyn_moments", "wae_beyn_moments_mgpu", "wae_beyn_moments_rb", "wae_rb_export", "wae_rb_import", "wae_eig_residuals", "wae_arnoldi_shiftinvert", "wae_arnoldi_shiftinvert_batch", "wae_perturb", "wae_slot_write", "wae_slot_read", "wae_slot_axpby", "wae_slot_forms", "wae_arnoldi_shiftinvert_slots", "wae_arnoldi_ritz_to_slot", "wae_perturb_slots", "wae_perturb_batch", "wae_perturb_batch_slots", "wae_p1_assemble", "wae_p1_assemble_boundary", "wae_p1_assemble_flame", "wae_p1_info", "wae_p1_get", "wae_p1_free", "wae_p1_shape_sensitivity", "wae_p1_shape_sensitivity_flame", "wae_bench_spmv", "wae_bench_spmv_level", "wae_bench_triad", "wae_debug_spmv", "wae_debug_vec",
+    "wae_solve", "wae_solve_guess", "wae_beyn_moments", "wae_beyn_moments_mgpu", "wae_beyn_moments_rb", "wae_rb_export", "wae_rb_import", "wae_eig_residuals", "wae_arnoldi_shiftinvert", "wae_arnoldi_shiftinvert_batch", "wae_perturb", "wae_slot_write", "wae_slot_read", "wae_slot_axpby", "wae_slot_forms", "wae_arnoldi_shiftinvert_slots", "wae_arnoldi_ritz_to_slot", "wae_perturb_slots", "wae_perturb_batch", "wae_perturb_batch_slots", "wae_p1_assemble", "wae_p1_assemble_boundary", "wae_p1_assemble_flame", "wae_p1_info", "wae_p1_get", "wae_p1_free", "wae_p1_shape_sensitivity", "wae_p1_shape_sensitivity_flame", "wae_bench_spmv", "wae_bench_spmv_level", "wae_bench_triad", "wae_debug_spmv", "wae_debug_vec", "wae_debug_gmres",
     "wae_tall_create", "wae_tall_destroy", "wae_tall_info", "wae_tall_write", "wae_tall_read", "wae_tall_gram", "wae_tall_mul", "wae_tall_hankel",
     "wae_p2_connectivity", "wae_p2_connectivity_info", "wae_p2_connectivity_get", "wae_p2_connectivity_free", "wae_p2_assemble",
     "wae_p2_assemble_boundary", "wae_p2_assemble_flame",
@@ -48,6 +48,8 @@ TALL_MAXCOLS = 64           # WAE_TALL_MAXCOLS
 (VEC_DOTS, VEC_NORMS, VEC_DOTS_MULTI, VEC_AXPY_NEG, VEC_LINCOMB, VEC_LINCOMB_ADD, VEC_AXPY_NEG_NORM, VEC_AXPY_NEG_MULTI, VEC_DOTS2, VEC_AXPY2,
  VEC_LINCOMB_REP, VEC_SCALE_INV, VEC_MASK_COLS, VEC_EXTRACT_COLS, VEC_BEYN_ACCUM, VEC_PT_GEMM_BATCH, VEC_PT_AXPBY_COLS,
  VEC_PT_PROJECT, VEC_DENSE) = range(19)
+# event kinds of wae_debug_gmres (include/waehip.h WAE_GMRES_*)
+GMRES_INIT, GMRES_STEP, GMRES_PAIR, GMRES_SOLVE_Y = range(4)
 
 
 def lib():
@@ -141,6 +143,8 @@ def lib():
                                  C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.wae_debug_vec.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.c_int32,
                                 C.POINTER(C.c_uint8), ip, ip]
+    L.wae_debug_gmres.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, dp, C.POINTER(C.c_int64), dp, C.c_int32, dp, C.c_int64,
+                                  dp, dp, dp, ip, C.POINTER(C.c_uint8), dp, dp, dp]
     L.wae_tall_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32]
     L.wae_tall_destroy.argtypes = [C.c_void_p]
     L.wae_tall_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
@@ -191,3 +195,91 @@ def debug_vec(op, sizes, bufs, cmask=None, perm=None, device=0, raise_on_error=T
     if raise_on_error:
         check(code)
     return code, status.value
+
+
+class GmresScript:
+    """wae_debug_gmres (test hook): a script of INIT / STEP / PAIR / SOLVE_Y events for the recurrence kernels of the lock-step GMRES,
+    run against one device state.  Build it with the four methods below (each returns the event's index), then run()."""
+
+    def __init__(self, nb, m, n, histcap=None):
+        self.nb, self.m, self.n = int(nb), int(m), int(n)
+        self.histcap = int(histcap) if histcap is not None else self.m + 8
+        self.ev, self.evd, self.parts, self.layout, self.plen = [], [], [], [], 0
+
+    def _event(self, kind, j, use_mask, tol, lim, arrays):
+        views, off = {}, self.plen
+        for name, a in arrays:
+            a = np.ascontiguousarray(a, dtype=np.complex128)
+            views[name] = (self.plen, a.shape)
+            self.parts.append(a.ravel())
+            self.plen += a.size
+        self.ev.append([kind, int(j), int(bool(use_mask)), off])
+        self.evd.append([float(tol), float(lim)])
+        self.layout.append(views)
+        return len(self.ev) - 1
+
+    def init(self, beta, done, use_mask):
+        return self._event(GMRES_INIT, 0, use_mask, 0.0, 0.0, [("beta", beta), ("done", np.asarray(done, dtype=np.float64))])
+
+    def step(self, j, hd, tol, lim, Vnew, use_mask):
+        return self._event(GMRES_STEP, j, use_mask, tol, lim, [("hd", hd), ("Vnew", Vnew)])
+
+    def pair(self, j, c1, c2, gram, norms, tol, lim, W1, W2, use_mask, sentinel=3 + 7j):
+        nb = self.nb
+        out = [("alpha", np.full(nb, sentinel)), ("c2m", np.full((j + 1, nb), sentinel)), ("hd2", np.full((j + 2, nb), sentinel))]
+        return self._event(GMRES_PAIR, j, use_mask, tol, lim,
+                           [("c1", c1), ("c2", c2), ("gram", gram), ("norms", norms), ("W1", W1), ("W2", W2)] + out)
+
+    def solve_y(self, ju, sentinel=3 + 7j):
+        return self._event(GMRES_SOLVE_Y, ju, 0, 0.0, 0.0, [("out", np.full((self.m, self.nb), sentinel))])
+
+    def run(self, bnorm, device=0, raise_on_error=True, sentinel=3 + 7j, short=0):
+        """Returns (code, result): result.events[e] holds the event's arrays as the device left them and its snapshot (relres, conv,
+        steps, iters, histlen, stalled, status, cmask, rescale, sv, vsq); result.R, cs, sn, g, sv, vsq, Hraw, sub, hist the final state
+        (entries no kernel wrote hold `sentinel`, its real part in the double arrays).  short: entries by which the pool's length is understated."""
+        nb, m, n, hc = self.nb, self.m, self.n, self.histcap
+        nev, nch, nint = len(self.ev), (nb + 7) // 8, 5 * nb + 4
+        mm, mp = max(m, 0), max(m, 0) + 1
+        pool = np.concatenate(self.parts) if self.parts else np.zeros(1, dtype=np.complex128)
+        ev = np.ascontiguousarray(self.ev, dtype=np.int64).reshape(-1)
+        evd = np.ascontiguousarray(self.evd, dtype=np.float64).reshape(-1)
+        bn = np.ascontiguousarray(bnorm, dtype=np.float64)
+        nR, nrow = mm * mp * max(nb, 0), mm * max(nb, 0)
+        cstate = np.full(2 * nR + 3 * nrow + 3 * max(nb, 0), sentinel, dtype=np.complex128)
+        dstate = np.full(3 * nrow + 2 * max(nb, 0) + max(hc, 0) * max(nb, 0), np.real(sentinel), dtype=np.float64)
+        s_rel = np.zeros((nev, max(nb, 0)))
+        s_int = np.zeros((nev, max(nint, 4)), dtype=np.int32)
+        s_cm = np.zeros((nev, max(nch, 1)), dtype=np.uint8)
+        s_resc = np.zeros((nev, max(nb, 0)), dtype=np.complex128)
+        s_sv = np.zeros((nev, 2, max(nb, 0)))
+        s_vsq = np.zeros((nev, 2, max(nb, 0)), dtype=np.complex128)
+        dp = C.POINTER(C.c_double)
+        code = lib().wae_debug_gmres(device, nb, m, hc, n, bn.ctypes.data_as(dp), ev.ctypes.data_as(C.POINTER(C.c_int64)), evd.ctypes.data_as(dp),
+                                     nev, zptr(pool), pool.size - short, zptr(cstate), dstate.ctypes.data_as(dp), s_rel.ctypes.data_as(dp),
+                                     s_int.ctypes.data_as(C.POINTER(C.c_int32)), s_cm.ctypes.data_as(C.POINTER(C.c_uint8)), zptr(s_resc),
+                                     s_sv.ctypes.data_as(dp), zptr(s_vsq))
+        if raise_on_error:
+            check(code)
+        if code < 0:
+            return code, None
+
+        class Result:
+            pass
+        res = Result()
+        o = 0
+        for name, cnt, shape in (("R", nR, (m, m + 1, nb)), ("sn", nrow, (m, nb)), ("g", nrow + nb, (m + 1, nb)), ("vsq", nrow + 2 * nb, (m + 2, nb)),
+                                 ("Hraw", nR, (m, m + 1, nb))):
+            setattr(res, name, cstate[o:o + cnt].reshape(shape))
+            o += cnt
+        o = 0
+        for name, cnt, shape in (("cs", nrow, (m, nb)), ("sv", nrow + 2 * nb, (m + 2, nb)), ("sub", nrow, (m, nb)), ("hist", hc * nb, (hc, nb))):
+            setattr(res, name, dstate[o:o + cnt].reshape(shape))
+            o += cnt
+        res.events = []
+        for e, views in enumerate(self.layout):
+            d = {k: pool[off:off + int(np.prod(shape))].reshape(shape) for k, (off, shape) in views.items()}
+            ints = s_int[e, :5 * nb].reshape(5, nb)
+            d.update(relres=s_rel[e], conv=ints[0], steps=ints[1], iters=ints[2], histlen=ints[3], stalled=ints[4],
+                     status=s_int[e, 5 * nb:5 * nb + 3], cmask=s_cm[e, :nch], rescale=s_resc[e], sv=s_sv[e], vsq=s_vsq[e])
+            res.events.append(d)
+        return code, res

@@ -1,6 +1,8 @@
 // libwaehip.so -- wae_debug_vec (include/waehip.h, "test hook"): ONE launch_* call of wae_internal.h on the caller's host arrays, so
 // that tests/ can pin every streaming and reduction kernel to a reference of its own.  No family, no solver set-up.
+// wae_debug_gmres: a script of launch_gmres_* calls against one GmresDev, for the recurrence kernels of the lock-step GMRES.
 #include <algorithm>
+#include <vector>
 
 #include "family.h"
 
@@ -171,6 +173,145 @@ extern "C" int wae_debug_vec(int32_t device, int32_t op, const int64_t *sz, int3
         }
         for (int i = 0; i < nbuf; ++i)
             if (bufs[i] && lens[i]) HIP_CHECK(hipMemcpyAsync(bufs[i], d[i].p, (size_t)lens[i] * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return WAE_OK;
+    });
+}
+
+extern "C" int wae_debug_gmres(int32_t device, int32_t nb, int32_t m, int32_t histcap, int64_t n, const double *bnorm, const int64_t *ev,
+                               const double *evd, int32_t nev, double *pool, int64_t plen, double *cstate, double *dstate, double *snap_relres,
+                               int32_t *snap_int, uint8_t *snap_cmask, double *snap_rescale, double *snap_sv, double *snap_vsq) {
+    return guarded([&]() {
+        WAE_REQUIRE(bnorm && ev && evd && pool && cstate && dstate && snap_relres && snap_int && snap_cmask && snap_rescale && snap_sv && snap_vsq,
+                    "bad argument");
+        WAE_REQUIRE(nb >= 1 && nb <= 256, "1 <= nb <= 256");
+        WAE_REQUIRE(m >= 1 && m <= 256 && histcap >= 1 && histcap <= 65536 && n >= 1 && n <= 65536 && nev >= 1 && nev <= 4096,
+                    "m in 1..256, histcap, n in 1..65536, 1..4096 events");
+        WAE_REQUIRE(plen >= 1 && plen <= ((int64_t)1 << 28), "the pool is empty or too large");
+        int ndev = 0;
+        HIP_CHECK(hipGetDeviceCount(&ndev));
+        WAE_REQUIRE(device >= 0 && device < ndev, "no such device");
+        // every event is checked before anything is uploaded or launched
+        const int64_t N = nb, blk = n * N;
+        const cplx *hpool = (const cplx *)pool;
+        int ninit = 0;
+        for (int e = 0; e < nev; ++e) {
+            const int64_t kind = ev[4 * e], j = ev[4 * e + 1], off = ev[4 * e + 3];
+            int64_t need = 0;
+            switch (kind) {
+            case WAE_GMRES_INIT: need = 2 * N; ++ninit; break;
+            case WAE_GMRES_STEP:
+                WAE_REQUIRE(j >= 0 && j < m, "a step outside the cycle (0 <= j < m)");
+                need = (j + 2) * N + blk;
+                break;
+            case WAE_GMRES_PAIR:
+                WAE_REQUIRE(j >= 0 && j + 2 <= m, "a pair step outside the cycle (0 <= j, j + 2 <= m)");
+                need = (3 * (j + 1) + (j + 2) + 6) * N + 2 * blk;
+                break;
+            case WAE_GMRES_SOLVE_Y:
+                WAE_REQUIRE(j >= 1 && j <= m, "solve_y: 1 <= ju <= m");
+                need = (int64_t)m * N;
+                break;
+            default: throw WaeError(WAE_ERR_INVALID, "wae_debug_gmres: unknown event");
+            }
+            WAE_REQUIRE(off >= 0 && off <= plen && need <= plen - off, "an event's arrays do not fit the pool");
+        }
+        // host-side staging: the `done` bytes of every INIT and the 1/norm^2 rows the vector kernels write in the solver
+        const int nch = (nb + 7) / 8, nint = 5 * nb + 4;
+        std::vector<unsigned char> hdone((size_t)std::max(ninit, 1) * nb);
+        std::vector<cplx> hinv((size_t)nev * 2 * nb, cplx{0.0, 0.0});
+        auto inv2 = [](double r) { return cplx{r > 0.0 ? 1.0 / (r * r) : 0.0, 0.0}; };
+        for (int e = 0, ii = 0; e < nev; ++e) {
+            const int64_t kind = ev[4 * e], j = ev[4 * e + 1], off = ev[4 * e + 3];
+            if (kind == WAE_GMRES_INIT) {
+                for (int b = 0; b < nb; ++b) hdone[(size_t)ii * nb + b] = hpool[off + N + b].x != 0.0 ? 1 : 0;
+                ++ii;
+            } else if (kind == WAE_GMRES_STEP) {
+                for (int b = 0; b < nb; ++b) hinv[(size_t)e * 2 * nb + b] = inv2(hpool[off + (j + 1) * N + b].x);
+            } else if (kind == WAE_GMRES_PAIR) {
+                const int64_t onorm = off + (2 * (j + 1) + 3) * N;
+                for (int b = 0; b < 2 * nb; ++b) hinv[(size_t)e * 2 * nb + b] = inv2(hpool[onorm + b].x);
+            }
+        }
+        HIP_CHECK(hipSetDevice(device));
+        StreamGuard sg;
+        HIP_CHECK(hipStreamCreate(&sg.s));
+        hipStream_t st = sg.s;
+        // the state, laid out as lib.hip run_device lays it out (one integer block: conv, steps, iters, histlen, stalled, status)
+        const size_t nR = (size_t)m * (m + 1) * nb, nrow = (size_t)m * nb;
+        DevBuf<cplx> dpool, R, sn, g, vsq, Hraw, rescale, dinv, s_rescale, s_vsq;
+        DevBuf<double> cs, sv, sub, hist, relres, bn, s_relres, s_sv;
+        DevBuf<int> ints, s_int;
+        DevBuf<unsigned char> cmask, ddone, s_cmask;
+        const cplx *hc = (const cplx *)cstate;
+        dpool.upload(hpool, (size_t)plen, st);
+        R.upload(hc, nR, st); sn.upload(hc + nR, nrow, st); g.upload(hc + nR + nrow, nrow + nb, st);
+        vsq.upload(hc + nR + 2 * nrow + nb, nrow + 2 * nb, st); Hraw.upload(hc + nR + 3 * nrow + 3 * nb, nR, st);
+        cs.upload(dstate, nrow, st); sv.upload(dstate + nrow, nrow + 2 * nb, st); sub.upload(dstate + 2 * nrow + 2 * nb, nrow, st);
+        hist.upload(dstate + 3 * nrow + 2 * nb, (size_t)histcap * nb, st);
+        bn.upload(bnorm, (size_t)nb, st);
+        ddone.upload(hdone.data(), hdone.size(), st);
+        dinv.upload(hinv.data(), hinv.size(), st);
+        relres.alloc(nb); rescale.alloc(nb); ints.alloc(nint); cmask.alloc(nch);
+        HIP_CHECK(hipMemsetAsync(ints.p, 0, (size_t)nint * sizeof(int), st));
+        HIP_CHECK(hipMemsetAsync(relres.p, 0, (size_t)nb * sizeof(double), st));
+        HIP_CHECK(hipMemsetAsync(rescale.p, 0, (size_t)nb * sizeof(cplx), st));
+        HIP_CHECK(hipMemsetAsync(cmask.p, 0, (size_t)nch, st));
+        s_relres.alloc((size_t)nev * nb); s_int.alloc((size_t)nev * nint); s_cmask.alloc((size_t)nev * nch); s_rescale.alloc((size_t)nev * nb);
+        s_sv.alloc((size_t)nev * 2 * nb); s_vsq.alloc((size_t)nev * 2 * nb);
+        HIP_CHECK(hipMemsetAsync(s_sv.p, 0, (size_t)nev * 2 * nb * sizeof(double), st));
+        HIP_CHECK(hipMemsetAsync(s_vsq.p, 0, (size_t)nev * 2 * nb * sizeof(cplx), st));
+        GmresDev S;
+        S.nb = nb; S.m = m; S.histcap = histcap;
+        S.R = R.p; S.cs = cs.p; S.sn = sn.p; S.g = g.p; S.sv = sv.p; S.vsq = vsq.p;
+        S.conv = ints.p; S.steps = S.conv + nb; S.iters = S.steps + nb; S.histlen = S.iters + nb; S.stalled = S.histlen + nb; S.status = S.stalled + nb;
+        S.relres = relres.p; S.bnorm = bn.p; S.hist = hist.p; S.rescale = rescale.p; S.cmask = cmask.p;
+        S.Hraw = Hraw.p; S.sub = sub.p;
+        auto d2d = [&](void *dst, const void *src, size_t bytes) { HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st)); };
+        for (int e = 0, ii = 0; e < nev; ++e) {
+            const int64_t kind = ev[4 * e], j = ev[4 * e + 1], off = ev[4 * e + 3];
+            const int use_mask = ev[4 * e + 2] ? 1 : 0;
+            const double tol = evd[2 * e], lim = evd[2 * e + 1];
+            cplx *a = dpool.p + off;
+            int row0 = -1, rows = 0;                    // the sv / vsq rows this event writes
+            if (kind == WAE_GMRES_INIT) {               // pool: beta[nb] done[nb]
+                launch_gmres_init(S, a, ddone.p + (size_t)ii * nb, use_mask, st);
+                ++ii;
+                row0 = 0; rows = 1;
+            } else if (kind == WAE_GMRES_STEP) {        // pool: hd[j+2][nb] Vnew[n][nb]
+                d2d(vsq.p + (size_t)(j + 1) * nb, dinv.p + (size_t)e * 2 * nb, (size_t)nb * sizeof(cplx));       // (axpy_neg_norm in the solver)
+                launch_gmres_step(S, a, (int)j, tol, lim, use_mask, a + (j + 2) * N, n, st);
+                row0 = (int)j + 1; rows = 1;
+            } else if (kind == WAE_GMRES_PAIR) {        // pool: c1 c2 [j+1][nb] gram[3][nb] norms[2][nb] W1 W2 [n][nb] alpha[nb] c2m[j+1][nb] hd2[j+2][nb]
+                cplx *c1 = a, *c2 = c1 + (j + 1) * N, *gram = c2 + (j + 1) * N, *norms = gram + 3 * N, *W1 = norms + 2 * N, *W2 = W1 + blk,
+                     *alpha = W2 + blk, *c2m = alpha + N, *hd2 = c2m + (j + 1) * N;
+                launch_gmres_pair_coef(S, (int)j, c1, c2, gram, alpha, c2m, hd2, st);
+                d2d(vsq.p + (size_t)(j + 1) * nb, dinv.p + (size_t)e * 2 * nb, (size_t)2 * nb * sizeof(cplx));   // (axpy2_norm in the solver)
+                launch_gmres_step(S, c1, (int)j, tol, 1e300, use_mask, W1, n, st, norms);
+                launch_gmres_step(S, hd2, (int)j + 1, tol, lim, use_mask, W2, n, st, norms + N);
+                row0 = (int)j + 1; rows = 2;
+            } else {                                    // pool: out[m][nb] (rows < max(ju, steps[b]) are written)
+                launch_gmres_solve_y(S, (int)j, a, st);
+            }
+            d2d(s_relres.p + (size_t)e * nb, relres.p, (size_t)nb * sizeof(double));
+            d2d(s_int.p + (size_t)e * nint, ints.p, (size_t)nint * sizeof(int));
+            d2d(s_cmask.p + (size_t)e * nch, cmask.p, (size_t)nch);
+            d2d(s_rescale.p + (size_t)e * nb, rescale.p, (size_t)nb * sizeof(cplx));
+            if (rows) {
+                d2d(s_sv.p + (size_t)e * 2 * nb, sv.p + (size_t)row0 * nb, (size_t)rows * nb * sizeof(double));
+                d2d(s_vsq.p + (size_t)e * 2 * nb, vsq.p + (size_t)row0 * nb, (size_t)rows * nb * sizeof(cplx));
+            }
+        }
+        auto back = [&](void *dst, const void *src, size_t bytes) { HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); };
+        cplx *oc = (cplx *)cstate;
+        back(pool, dpool.p, (size_t)plen * sizeof(cplx));
+        back(oc, R.p, nR * sizeof(cplx)); back(oc + nR, sn.p, nrow * sizeof(cplx)); back(oc + nR + nrow, g.p, (nrow + nb) * sizeof(cplx));
+        back(oc + nR + 2 * nrow + nb, vsq.p, (nrow + 2 * nb) * sizeof(cplx)); back(oc + nR + 3 * nrow + 3 * nb, Hraw.p, nR * sizeof(cplx));
+        back(dstate, cs.p, nrow * sizeof(double)); back(dstate + nrow, sv.p, (nrow + 2 * nb) * sizeof(double));
+        back(dstate + 2 * nrow + 2 * nb, sub.p, nrow * sizeof(double)); back(dstate + 3 * nrow + 2 * nb, hist.p, (size_t)histcap * nb * sizeof(double));
+        back(snap_relres, s_relres.p, (size_t)nev * nb * sizeof(double)); back(snap_int, s_int.p, (size_t)nev * nint * sizeof(int));
+        back(snap_cmask, s_cmask.p, (size_t)nev * nch); back(snap_rescale, s_rescale.p, (size_t)nev * nb * sizeof(cplx));
+        back(snap_sv, s_sv.p, (size_t)nev * 2 * nb * sizeof(double)); back(snap_vsq, s_vsq.p, (size_t)nev * 2 * nb * sizeof(cplx));
         HIP_CHECK(hipStreamSynchronize(st));
         return WAE_OK;
     });
