@@ -144,6 +144,26 @@ int wae_solve(wae_family *h, const double *coeffs, int32_t ncoef, const double *
 int wae_solve_guess(wae_family *h, const double *coeffs, int32_t ncoef, const double *B, const double *G, double *X,
                     int32_t r, int32_t op, double tol, int32_t maxit, wae_solve_info *info);
 
+/* -- forced response: x_j = L(w_j)^{-1} b_j over a list of excitation frequencies, in HBM ------------------------------
+ * The forced problem of the reference (`L(w) \ Array(rhs(w))` with the `rhs` family of `discretize(...; source=true)`, read with
+ * get_p / get_n_grad_p, src/FEM/helmholtz_getters.jl) as a sweep: neither the d x nfreq right-hand sides nor the d x nfreq solutions exist
+ * anywhere; what crosses the bus is the sparse input and what was asked for.  All row indices are 0-based, in the caller's numbering:
+ *     b_j    = sum_s src_coeff[j,s] m_s          nsrc sparse vectors (src_ptr: nsrc+1 offsets, src_idx, src_val complex)
+ *     x_j    = (sum_k coeff_table[j,k] A_k)^{-1} b_j
+ *     H[q,j] = sum_i obs_val_q[i] x_j[obs_idx_q[i]]   nobs sparse functionals, no conjugation; H_out[q + nobs*j], complex
+ *     X_out[:,k] = x_{keep[k]}                    d x nkeep column-major, keep: strictly ascending frequency indices
+ * Indices that repeat inside one sparse vector add up.  The frequencies run in chunks of the handle's batch width (opts[6] of
+ * wae_solver_setup), each chunk one lock-step solve from a zero guess with one coefficient set per column (wae_solve with ncoef == r); the
+ * right-hand sides are filled and the functionals applied on the device, without atomics and in a fixed order: the same bits on every
+ * call.  coeff_table: nfreq x T complex, row j = the coefficients of L(w_j); src_coeff: nfreq x nsrc complex, row j.
+ * WAE_ERR_INVALID, with nothing launched: nfreq < 0; a ptr array that does not start at 0 or decreases; an index outside 0..d-1; a value
+ * or coefficient that is not finite; keep out of range or not strictly ascending; nobs == 0 and nkeep == 0 (nothing was asked for); no
+ * wae_solver_setup.  nfreq == 0 returns WAE_OK and touches nothing.  info as in wae_solve, maxima and sums over all chunks. */
+int wae_forced_response(wae_family *h, int32_t nfreq, const double *coeff_table, int32_t nsrc, const int64_t *src_ptr, const int32_t *src_idx,
+                        const double *src_val, const double *src_coeff, int32_t nobs, const int64_t *obs_ptr, const int32_t *obs_idx,
+                        const double *obs_val, double *H_out, int32_t nkeep, const int32_t *keep, double *X_out, double tol, int32_t maxit,
+                        wae_solve_info *info);
+
 /* -- Beyn moments -------------------------------------------------------------------------------------
  * The whole quadrature loop of `beyn` / `compute_moment_matrices` (beyn.jl:62-74,112-138,251-268):
  *   A[:,:,p] = sum_j w_j z_j^p (sum_k c_jk A_k)^{-1} V ,  p = 0..2K-1
@@ -409,14 +429,34 @@ int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points,
  * The local K_ab and K_ba, b_ab and b_ba get the same bits.  Arguments, index checks, pipeline (sorted triplets, no atomics, the same bits
  * on every call) and handle type (wae_p1_info / wae_p1_get / wae_p1_free) are those of the per-simplex entry of the same name.
  * c_point: npoints doubles, required: NULL or a value that is not finite returns WAE_ERR_INVALID and nothing is launched.
- * Not covered: the shape sensitivity (wae_p1_shape_sensitivity* re-discretise with c_tet / c_tri), the speaker source vector (:m,
- * source=true) and Hermite elements. */
+ * Not covered: the shape sensitivity (wae_p1_shape_sensitivity* re-discretise with c_tet / c_tri) and Hermite elements. */
 int wae_p1_assemble_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_point, void **out);
 int wae_p1_assemble_boundary_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_point,
                                     void **out);
 int wae_p2_assemble_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_point, void **out);
 int wae_p2_assemble_boundary_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
                                     const int32_t *tris, const double *c_point, void **out);
+/* -- speaker source vector: `discretize(mesh, dscrp, C; source=true)` with a :speaker domain -------------------------------
+ * The second family `rhs` of the reference (src/Helmholtz.jl:251-258,488-505,519-522) holds one sparse vector m = -i s,
+ *     s_a = |(x0-x2) x (x1-x2)| int c(x) phi_a   over the triangles of the speaker domain   (wallsrc, divided by i),
+ * with the scalar functions of the admittance term and the excitation symbol: rhs(w) = w Y A m, while L gets the w Y C of an admittance
+ * boundary.  These entries return the real vector s in dense form (out: npoints doubles; P2: nout = npoints + nedges doubles, and a
+ * wrong nout is WAE_ERR_INVALID).  Element vectors from the monomial formula  int l^alpha = |..| alpha! / (|alpha| + 2)! :
+ *     P1, c per triangle:  s_a = c |..| / 6                     P1, c per point:  s_a = |..| (c_a/12 + c_b/24 + c_c/24)
+ *     P2, c per triangle:  0 on the points, c |..| / 6 on the edges
+ *     P2, c per point:     |..| (c_a/60 - c_b/120 - c_c/120) on point a,  |..| (c_i/15 + c_j/15 + c_k/30) on edge (i,j), k the third point
+ * (node order and edge numbers: wae_p2_connectivity).  Pipeline and guarantees are those of the boundary-matrix entries of the same space:
+ * (node, value) pairs per triangle, sorted and summed on the device, no atomics, the same bits on every call; the same index and argument
+ * checks, WAE_ERR_INVALID before the element kernel is launched.  c_tri == NULL means 1; c_point is required and must be finite.
+ * ntris == 0 is allowed and gives the zero vector.  Hermite elements are not covered. */
+int wae_p1_assemble_source(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_tri,
+                           double *out);
+int wae_p1_assemble_source_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_point,
+                                  double *out);
+int wae_p2_assemble_source(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                           const int32_t *tris, const double *c_tri, double *out, int64_t nout);
+int wae_p2_assemble_source_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                                  const int32_t *tris, const double *c_point, double *out, int64_t nout);
 /* Discrete-adjoint shape sensitivity (src/shape_sensitivity.jl:16-141) of an eigenvalue w.r.t. the coordinates of surface
  * points, for the interior (M, K) and the admittance-boundary (w*Y*C) parts of the P1 Helmholtz operator.  As in the
  * reference the operator derivative is a central difference (step h) of two local re-discretisations of the simplices

@@ -21,7 +21,7 @@ module WAEHip
 
 using LinearAlgebra, SparseArrays
 import FastGaussQuadrature
-import ..NLEVP: LinearOperatorFamily, Term, inpoly
+import ..NLEVP: LinearOperatorFamily, Term, inpoly, pow1
 
 const libwaehip = get(ENV, "WAEHIP_LIB", "libwaehip.so")
 
@@ -1503,13 +1503,94 @@ function assemble_p2_flame(points::Matrix{Float64}, tets::AbstractMatrix{<:Integ
     return _take_p1(h[], false), vol[]
 end
 
+"m = assemble_source(points, tris; tets, c_tri, c_point, device): the source vector of a :speaker boundary, m = -i s with s_a = |e1×e2| ∫c φ_a over
+the speaker triangles (Helmholtz.jl:488-505,519-522), as the sparse vector the `rhs` family of `discretize(...; source=true)` holds.  tets given:
+the P2 space (they number the edges), size npoints + nedges; else P1.  c_tri (per triangle, nothing = 1) or c_point (per mesh point)."
+function assemble_source(points::Matrix{Float64}, tris::AbstractMatrix{<:Integer}; tets::Union{Nothing,AbstractMatrix{<:Integer}}=nothing, c_tri=nothing,
+                         c_point=nothing, device::Integer=0)
+    s0 = _zero_based(tris); np = size(points, 2)
+    cp = _nodal(c_point, c_tri, np)
+    cc = c_tri === nothing ? C_NULL : Vector{Float64}(c_tri)
+    if tets === nothing
+        out = zeros(Float64, np)
+        if cp !== nothing
+            check(ccall((:wae_p1_assemble_source_cpoint, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                        device, np, points, size(s0, 2), s0, cp, out))
+        else
+            check(ccall((:wae_p1_assemble_source, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                        device, np, points, size(s0, 2), s0, cc, out))
+        end
+    else
+        t0 = _zero_based(tets)
+        out = zeros(Float64, np + size(p2_connectivity(np, tets; device=device)[1], 2))
+        if cp !== nothing
+            check(ccall((:wae_p2_assemble_source_cpoint, libwaehip), Cint,
+                        (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int64),
+                        device, np, points, size(t0, 2), t0, size(s0, 2), s0, cp, out, length(out)))
+        else
+            check(ccall((:wae_p2_assemble_source, libwaehip), Cint,
+                        (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int64),
+                        device, np, points, size(t0, 2), t0, size(s0, 2), s0, cc, out, length(out)))
+        end
+    end
+    I = findall(!iszero, out)
+    return sparsevec(I, ComplexF64.(out[I]) ./ 1im, length(out))
+end
+
+"rhs = speaker_source(m; adm_sym, adm_val, speak_sym, speak_val): the `rhs` family of `discretize(...; source=true)` for one :speaker boundary
+(Helmholtz.jl:79,251-258,501-505,519-522): rhs(ω) = ω·Y·A·m"
+function speaker_source(m::SparseVector{ComplexF64}; adm_sym::Symbol=:Y, adm_val=1e15, speak_sym::Symbol=:A, speak_val=1.0)
+    rhs = LinearOperatorFamily(["ω"], complex([0.0]))
+    rhs.params[adm_sym] = adm_val
+    rhs.params[speak_sym] = speak_val
+    push!(rhs, Term(m, (pow1, pow1, pow1), ((:ω,), (adm_sym,), (speak_sym,)), "speaker", "m"))
+    return rhs
+end
+
+"H, X, info = forced_response(fam, rhs, ωs; observers, keep): x_j = L(ω_j) \\ Array(rhs(ω_j)) for every excitation frequency, in HBM
+(wae_forced_response).  rhs: a family of sparse-vector terms (speaker_source); observers: sparse functionals as SparseVector{ComplexF64}
+(get_p / get_n_grad_p weights; H[q, j] = sum(observers[q] .* x_j), no conjugation); keep: ascending 1-based indices into ωs of the
+solutions returned in full (X: d x length(keep)).  Neither the right-hand sides nor the solutions of the whole sweep ever exist."
+function forced_response(fam::DeviceFamily, rhs::LinearOperatorFamily, ωs::AbstractVector; observers::Vector{SparseVector{ComplexF64,Int}}=SparseVector{ComplexF64,Int}[],
+                         keep::AbstractVector{<:Integer}=Int[], quiet::Bool=false)
+    ensure_solver!(fam)
+    L = fam.L; d = size(L.terms[1].coeff, 1); nf = length(ωs); T = length(L.terms); ns = length(rhs.terms); no = length(observers)
+    function table(F::LinearOperatorFamily, n::Int)            # n x nf, column j = F's coefficients at ω_j (row j of the C table)
+        saved = (copy(F.params), F.active, F.mode); F.active = [F.eigval]; F.mode = :all
+        tab = zeros(ComplexF64, n, nf)
+        for (j, ω) in enumerate(ωs); tab[:, j] = coefficients(F, ω); end
+        F.params, F.active, F.mode = saved
+        return tab
+    end
+    ct = table(L, T); sc = table(rhs, ns)
+    function pack(vs)                                          # compressed form, 0-based rows
+        ptr = Int64[0]; idx = Int32[]; val = ComplexF64[]
+        for v in vs
+            sv = sparsevec(v); length(sv) == d || throw(ArgumentError("forced_response: a sparse vector has $(length(sv)) rows, the family has $d"))
+            append!(idx, Int32.(sv.nzind .- 1)); append!(val, ComplexF64.(sv.nzval)); push!(ptr, length(idx))
+        end
+        return ptr, idx, val
+    end
+    sptr, sidx, sval = pack([t.coeff for t in rhs.terms]); optr, oidx, oval = pack(observers)
+    kp = Vector{Int32}(keep) .- Int32(1)
+    H = zeros(ComplexF64, no, nf); X = zeros(ComplexF64, d, length(kp)); info = Ref{SolveInfo}()
+    code = check(ccall((:wae_forced_response, libwaehip), Cint,
+                       (Ptr{Cvoid}, Int32, Ptr{ComplexF64}, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{ComplexF64}, Ptr{ComplexF64}, Int32, Ptr{Int64}, Ptr{Int32},
+                        Ptr{ComplexF64}, Ptr{ComplexF64}, Int32, Ptr{Int32}, Ptr{ComplexF64}, Float64, Int32, Ref{SolveInfo}),
+                       fam.handle, nf, ct, ns, sptr, sidx, sval, sc, no, optr, oidx, oval, H, length(kp), kp, X, fam.tol, fam.maxit, info))
+    report(code, info[], "forced_response"; quiet=quiet)
+    return H, X, info[]
+end
+
 "M, K, C, Q, V_flame = discretize_device(points, tets; order, c, c_tet, bnd_tris, bnd_c, flame): the term matrices of `discretize` assembled on the
 device, order = :lin or :quad (Helmholtz.jl:36-54).  c: the speed of sound as `discretize` takes it (Helmholtz.jl:59-74) -- one value per
 tetrahedron, or one per mesh point (then linear on every simplex, in K and in C; bnd_c is not used); c_tet = the first form alone.
 bnd_tris / bnd_c: admittance-boundary triangles and the speed of sound behind each; flame = (flame_tets, ref_tet, x_ref, n_ref,
-nglobal_scaled).  Terms that were not asked for come back as `nothing`."
+nglobal_scaled).  Terms that were not asked for come back as `nothing`.
+source=true (`discretize(...; source=true)`, Helmholtz.jl:576-577): bnd_tris is a :speaker boundary -- C is its ω·Y·C term as before, and the call
+returns ((M, K, C, Q, V_flame), rhs) with rhs = speaker_source(m; speaker...) on the same triangles, speaker = (adm_sym, adm_val, speak_sym, speak_val)."
 function discretize_device(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; order::Symbol=:lin, c=nothing, c_tet=nothing, bnd_tris=nothing,
-                           bnd_c=nothing, flame=nothing, device::Integer=0)
+                           bnd_c=nothing, flame=nothing, device::Integer=0, source::Bool=false, speaker=(:Y, 1e15, :A, 1.0))
     order in (:lin, :quad) || error("discretize_device: order must be :lin or :quad")
     quad = order == :quad
     c_point = nothing
@@ -1532,6 +1613,11 @@ function discretize_device(points::Matrix{Float64}, tets::AbstractMatrix{<:Integ
         flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled = flame
         Q, V = quad ? assemble_p2_flame(points, tets, flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled; device=device) :
                       assemble_p1_flame(points, tets, flame_tets, ref_tet, n_ref, nglobal_scaled; device=device)
+    end
+    if source
+        bnd_tris === nothing && throw(ArgumentError("discretize_device: source=true needs the speaker triangles (bnd_tris)"))
+        m = assemble_source(points, bnd_tris; tets=(quad ? tets : nothing), c_tri=bnd_c, c_point=c_point, device=device)
+        return (M, K, C, Q, V), speaker_source(m; adm_sym=speaker[1], adm_val=speaker[2], speak_sym=speaker[3], speak_val=speaker[4])
     end
     return M, K, C, Q, V
 end

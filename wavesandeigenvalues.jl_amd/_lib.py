@@ -41,6 +41,7 @@ EXPORTS = [
     "wae_p2_connectivity", "wae_p2_connectivity_info", "wae_p2_connectivity_get", "wae_p2_connectivity_free", "wae_p2_assemble",
     "wae_p2_assemble_boundary", "wae_p2_assemble_flame",
     "wae_p1_assemble_cpoint", "wae_p1_assemble_boundary_cpoint", "wae_p2_assemble_cpoint", "wae_p2_assemble_boundary_cpoint",
+    "wae_p1_assemble_source", "wae_p1_assemble_source_cpoint", "wae_p2_assemble_source", "wae_p2_assemble_source_cpoint", "wae_forced_response",
 ]
 TALL_MAXCOLS = 64           # WAE_TALL_MAXCOLS
 
@@ -132,6 +133,12 @@ def lib():
                                         C.POINTER(C.c_void_p), dp]
     for name in ("wae_p1_assemble", "wae_p1_assemble_boundary", "wae_p2_assemble", "wae_p2_assemble_boundary"):       # c_point in the place of c_tet / c_tri
         getattr(L, name + "_cpoint").argtypes = getattr(L, name).argtypes
+    for name in ("wae_p1_assemble_source", "wae_p1_assemble_source_cpoint"):
+        getattr(L, name).argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, dp, dp]
+    for name in ("wae_p2_assemble_source", "wae_p2_assemble_source_cpoint"):
+        getattr(L, name).argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, dp, dp, C.c_int64]
+    L.wae_forced_response.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, i64p, i32p, dp, dp, C.c_int32, i64p, i32p, dp, dp, C.c_int32, i32p, dp,
+                                      C.c_double, C.c_int32, C.POINTER(SolveInfo)]
     L.wae_p1_shape_sensitivity.argtypes = [C.c_int32, C.c_int64, dp, i32p, dp, C.c_int64, i32p, i32p, i32p, dp, C.c_int64, i32p, i32p,
                                            C.c_int64, C.c_int64, dp, dp, dp, dp, C.c_double, dp, dp]
     L.wae_p1_shape_sensitivity_flame.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, i32p, C.c_int32, C.c_int64, i32p, dp, dp, dp,

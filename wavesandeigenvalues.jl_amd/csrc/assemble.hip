@@ -265,6 +265,11 @@ P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k
     return H.release();
 }
 
+void pairs_to_dense(int64_t n, size_t ne, Dev<unsigned long long> &k0, Dev<double> &v, double *out) {
+    std::unique_ptr<P1Handle> H(triplets_to_csr(n, ne, k0, v, nullptr));
+    for (int64_t r = 0; r < n; ++r) out[r] = H->rowptr[r + 1] > H->rowptr[r] ? H->m[(size_t)H->rowptr[r]] : 0.0;
+}
+
 namespace {
 
 // boundary mass of one triangle: b_ab = c |(x0-x2) x (x1-x2)| (1+delta_ab)/24  (FEM.jl:9-20,435-441; Helmholtz.jl:151-156); C = -i b
@@ -317,6 +322,34 @@ __global__ __launch_bounds__(256) void p1_boundary_cpoint_kernel(const double *_
             keys[o] = (unsigned long long)v[a] * (unsigned long long)np + (unsigned long long)v[b];
             bv[o] = (a == b ? (2.0 * c[a] + S) / 60.0 : ((c[a] + c[b]) + S) / 120.0) * det;          // (c_a + c_b) first: b_ab == b_ba
         }
+}
+
+// speaker source vector of one triangle (wallsrc of the reference divided by i, Helmholtz.jl:488-505): s_a = |(x0-x2) x (x1-x2)| int c l_a with
+// int l^alpha = alpha!/(|alpha| + 2)!:  c per triangle: s_a = c |..|/6;  c per point: s_a = |..| (c_a/12 + (c_b + c_c)/24).  Three (node, value)
+// pairs per triangle, key = node * np (column 0 of triplets_to_csr)
+__global__ __launch_bounds__(256) void p1_source_kernel(const double *__restrict__ pts, const int *__restrict__ tris, const double *__restrict__ c, int nodal,
+                                                        int64_t nt, int64_t np, unsigned long long *__restrict__ keys, double *__restrict__ sv) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    int v[3];
+    double X[3][3];
+    for (int a = 0; a < 3; ++a) {
+        v[a] = tris[t * 3 + a];
+        for (int k = 0; k < 3; ++k) X[a][k] = pts[(size_t)v[a] * 3 + k];
+    }
+    const double u0 = X[0][0] - X[2][0], u1 = X[0][1] - X[2][1], u2 = X[0][2] - X[2][2];
+    const double w0 = X[1][0] - X[2][0], w1 = X[1][1] - X[2][1], w2 = X[1][2] - X[2][2];
+    const double n0 = u1 * w2 - u2 * w1, n1 = u2 * w0 - u0 * w2, n2 = u0 * w1 - u1 * w0;
+    const double det = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+    double cc[3] = {1.0, 1.0, 1.0};
+    if (nodal)
+        for (int a = 0; a < 3; ++a) cc[a] = c[v[a]];
+    const double ct = (!nodal && c) ? c[t] : 1.0;
+    for (int a = 0; a < 3; ++a) {
+        const size_t o = (size_t)t * 3 + a;
+        keys[o] = (unsigned long long)v[a] * (unsigned long long)np;
+        sv[o] = nodal ? det * (cc[a] / 12.0 + (cc[(a + 1) % 3] + cc[(a + 2) % 3]) / 24.0) : ct * det / 6.0;
+    }
 }
 
 // |det J| of the listed tetrahedra (volume source S_a = |det J|/24 per node, FEM.jl:2429-2431; flame volume = sum |det J|/6)
@@ -465,6 +498,44 @@ int wae_p1_assemble_boundary(int32_t device, int64_t npoints, const double *poin
 int wae_p1_assemble_boundary_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_point,
                                     void **out) {
     return p1_assemble_boundary(device, npoints, points, ntris, tris, c_point, true, out);
+}
+
+// c: per triangle (NULL = 1), or per mesh point (nodal; required)
+static int p1_assemble_source(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c, bool nodal,
+                              double *out) {
+    return wae_guarded([&]() {
+        if (!(npoints > 0 && ntris >= 0 && points && (ntris == 0 || tris) && out)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        if (nodal) check_c_point(npoints, c);
+        if ((size_t)ntris * 3 >= 0x7fffffffull) throw WaeError(WAE_ERR_INVALID, "too many triangles for a 32-bit pair count");
+        for (int64_t i = 0; i < ntris * 3; ++i)
+            if (tris[i] < 0 || tris[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "triangle refers to a point outside 0..npoints-1");
+        if (ntris == 0) {                                                     // an empty speaker domain: the zero vector
+            std::fill(out, out + npoints, 0.0);
+            return WAE_OK;
+        }
+        HIP_CHECK(hipSetDevice(device));
+        const size_t ne = (size_t)ntris * 3, nc = (size_t)(nodal ? npoints : ntris);
+        Dev<double> dpts((size_t)npoints * 3), dc(c ? nc : 1), sv(ne);
+        Dev<int> dt((size_t)ntris * 3);
+        Dev<unsigned long long> k0(ne);
+        HIP_CHECK(hipMemcpy(dpts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dt.p, tris, (size_t)ntris * 3 * sizeof(int), hipMemcpyHostToDevice));
+        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(p1_source_kernel, dim3((unsigned)((ntris + 255) / 256)), dim3(256), 0, 0, dpts.p, dt.p, c ? dc.p : nullptr, nodal ? 1 : 0, ntris,
+                           npoints, k0.p, sv.p);
+        HIP_CHECK(hipGetLastError());
+        pairs_to_dense(npoints, ne, k0, sv, out);
+        return WAE_OK;
+    });
+}
+
+int wae_p1_assemble_source(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_tri, double *out) {
+    return p1_assemble_source(device, npoints, points, ntris, tris, c_tri, false, out);
+}
+
+int wae_p1_assemble_source_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_point,
+                                  double *out) {
+    return p1_assemble_source(device, npoints, points, ntris, tris, c_point, true, out);
 }
 
 int wae_p1_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t nflame,

@@ -143,6 +143,35 @@ constexpr P2NodalC make_p2_nodal_c() {
 constexpr P2NodalC kNodalC = make_p2_nodal_c();
 __constant__ P2NodalC dNodalC = kNodalC;
 
+// Speaker source vector with the nodal speed of sound:  srcc[p][a] = int l_p phi_a / |(x0-x2) x (x1-x2)|  on the 6-node triangle (degree 3,
+// denominator 5!), from the same quadratic forms:  s_a = |..| sum_p c_p srcc[p][a]
+struct P2SourceC {
+    double tri[3][6];
+};
+
+constexpr P2SourceC make_p2_source_c() {
+    P2SourceC S = {};
+    int q2[6][3][3] = {};
+    p2_quadratic_forms<3>(q2);
+    for (int p = 0; p < 3; ++p)
+        for (int a = 0; a < 6; ++a) {
+            long long num = 0;
+            for (int k = 0; k < 3; ++k)
+                for (int l = 0; l < 3; ++l) {
+                    int cnt[3] = {};
+                    ++cnt[p]; ++cnt[k]; ++cnt[l];
+                    long long mono = 1;
+                    for (int v = 0; v < 3; ++v) mono *= p2_factorial(cnt[v]);
+                    num += (long long)q2[a][k][l] * mono;
+                }
+            S.tri[p][a] = (double)num / (double)(2 * p2_factorial(5));
+        }
+    return S;
+}
+
+constexpr P2SourceC kSourceC = make_p2_source_c();
+__constant__ P2SourceC dSourceC = kSourceC;
+
 // G[a] = grad l_a of the tetrahedron with corners X (l_4 = 1 - l_1 - l_2 - l_3, corner 4 is the origin: CooTrafo, FEM.jl:9-20); returns det J
 __host__ __device__ inline double p2_tet_gradients(const double X[4][3], double G[4][3]) {
     double J[3][3];
@@ -408,6 +437,31 @@ __global__ __launch_bounds__(256) void p2_boundary_cpoint_kernel(const double *_
     }
 }
 
+// node a of the speaker source vector of triangle t (wallsrc of the reference divided by i, Helmholtz.jl:488-505):
+//     s_a = |(x0-x2) x (x1-x2)| int c(x) phi_a,   c per triangle (c_tri, NULL = 1) or linear between the corner values (nodal).
+// One (node, value) pair per thread, key = node * dim (column 0 of triplets_to_csr); p runs in one order.
+__global__ __launch_bounds__(256) void p2_source_kernel(const double *__restrict__ pts, const int *__restrict__ s6, const double *__restrict__ c, int nodal,
+                                                        int64_t ns, u64 dim, u64 *__restrict__ keys, double *__restrict__ sv) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= ns * 6) return;
+    const int64_t t = e / 6;
+    const int a = (int)(e - t * 6);
+    int nd[3];
+    double X[3][3];
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        nd[v] = s6[t * 6 + v];
+        for (int k = 0; k < 3; ++k) X[v][k] = pts[(size_t)nd[v] * 3 + k];
+    }
+    const double u0 = X[0][0] - X[2][0], u1 = X[0][1] - X[2][1], u2 = X[0][2] - X[2][2];
+    const double w0 = X[1][0] - X[2][0], w1 = X[1][1] - X[2][1], w2 = X[1][2] - X[2][2];
+    const double n0 = u1 * w2 - u2 * w1, n1 = u2 * w0 - u0 * w2, n2 = u0 * w1 - u1 * w0;
+    const double det = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+    keys[e] = (u64)s6[t * 6 + a] * dim;
+    if (nodal) sv[e] = det * fma(c[nd[2]], dSourceC.tri[2][a], fma(c[nd[1]], dSourceC.tri[1][a], c[nd[0]] * dSourceC.tri[0][a]));
+    else sv[e] = (c ? c[t] : 1.0) * det * dTri.src[a];
+}
+
 // |det J| of the listed tetrahedra (flame volume = sum |det J| / 6)
 __global__ __launch_bounds__(256) void p2_det_kernel(const double *__restrict__ pts, const int *__restrict__ t10, const int *__restrict__ list, int64_t n,
                                                      double *__restrict__ adet) {
@@ -594,6 +648,43 @@ static int p2_assemble_boundary(int32_t device, int64_t npoints, const double *p
         *out = triplets_to_csr(m.dim, ne, k0, bv, nullptr);
         return WAE_OK;
     });
+}
+
+// c: per triangle (NULL = 1), or per mesh point (nodal; required).  nout is checked against the edge count of the device numbering, before
+// the element kernel is launched.
+static int p2_assemble_source(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                              const int32_t *tris, const double *c, bool nodal, double *out, int64_t nout) {
+    return wae_guarded([&]() {
+        if (!(points && out && ntris >= 0 && nout > 0)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        p2_check_mesh(npoints, ntets, tets, ntris, tris);
+        if (nodal) check_c_point(npoints, c);
+        HIP_CHECK(hipSetDevice(device));
+        P2Mesh m(npoints, points, ntets, tets, ntris, tris);
+        if (nout != m.dim) throw WaeError(WAE_ERR_INVALID, "nout is not npoints + nedges");
+        if (ntris == 0) {                                                     // an empty speaker domain: the zero vector
+            std::fill(out, out + nout, 0.0);
+            return WAE_OK;
+        }
+        const size_t ne = (size_t)ntris * 6, nc = (size_t)(nodal ? npoints : ntris);
+        Dev<double> dc(c ? nc : 1), sv(ne);
+        Dev<u64> k0(ne);
+        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(p2_source_kernel, dim3((unsigned)((ntris * 6 + 255) / 256)), dim3(256), 0, 0, m.pts.p, m.s6.p, c ? dc.p : nullptr, nodal ? 1 : 0,
+                           ntris, (u64)m.dim, k0.p, sv.p);
+        HIP_CHECK(hipGetLastError());
+        pairs_to_dense(m.dim, ne, k0, sv, out);
+        return WAE_OK;
+    });
+}
+
+int wae_p2_assemble_source(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                           const int32_t *tris, const double *c_tri, double *out, int64_t nout) {
+    return p2_assemble_source(device, npoints, points, ntets, tets, ntris, tris, c_tri, false, out, nout);
+}
+
+int wae_p2_assemble_source_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                                  const int32_t *tris, const double *c_point, double *out, int64_t nout) {
+    return p2_assemble_source(device, npoints, points, ntets, tets, ntris, tris, c_point, true, out, nout);
 }
 
 int wae_p2_assemble(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_tet, void **out) {

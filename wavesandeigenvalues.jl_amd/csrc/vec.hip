@@ -1,5 +1,6 @@
 // Vector kernels of libwaehip.so on interleaved multivectors X[row][b] (layout: kernels.hip) -- gfx950 (MI355X, CDNA4; wave64) only:
 // the Krylov streams and their reductions, the snapshot-basis helpers, the GMRES bookkeeping and the perturbation recurrence.
+#include "block_reduce.h"
 #include "kernel_helpers.h"
 
 // ---------------------------------------------------------------------------------------------------
@@ -30,37 +31,8 @@ void launch_add(const cplx *X, cplx *Y, size_t count, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// the two stages of every reduction over the rows
+// the two stages of every reduction over the rows (the first, block_colsum, is in block_reduce.h)
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ cplx vadd(cplx a, cplx b) { return cplx{a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ double vadd(double a, double b) { return a + b; }
-__device__ __forceinline__ cplx vshfl_xor(cplx a, int m) { return cplx{__shfl_xor(a.x, m), __shfl_xor(a.y, m)}; }
-__device__ __forceinline__ double vshfl_xor(double a, int m) { return __shfl_xor(a, m); }
-// First stage, inside a workgroup of NT threads in which thread t owns column t % nb: the sum of v over the threads of a column, returned
-// to the threads tid < nb (the others get a value that means nothing).  EVERY thread of the workgroup calls it: idle threads (beyond
-// R*nb, R = NT / nb) and threads of a masked chunk with v = 0.  sm: NT values of LDS scratch, free again on return (the closing barrier).
-// POW2 (nb a power of two <= 64): the lanes of a wavefront that own the same column are reduced with xor shuffles, m = 32 ... nb, and only
-// one value per wavefront and column goes through LDS; the NT/64 of them are added in index order.  Otherwise the R LDS entries of a
-// column are added serially in index order (at nb = 1 that was 256 serial reads per vector: 168 us per launch in the narrow-batch
-// solves of the Newton-type iterations).  The two orders give different bits: a kernel keeps the arm it has.
-template <bool POW2, int NT, class T>
-__device__ __forceinline__ T block_colsum(T v, int nb, T *sm) {
-    const int tid = threadIdx.x;
-    if (POW2) {
-        for (int m = 32; m >= nb; m >>= 1) v = vadd(v, vshfl_xor(v, m));
-        if ((tid & 63) < nb) sm[(tid >> 6) * nb + (tid & 63)] = v;
-    } else {
-        sm[tid] = v;
-    }
-    __syncthreads();
-    if (tid < nb) {
-        const int terms = POW2 ? NT / 64 : NT / nb;
-        v = sm[tid];
-        for (int k = 1; k < terms; ++k) v = vadd(v, sm[k * nb + tid]);
-    }
-    __syncthreads();
-    return v;
-}
 // Second stage: the sum over the nblk first-stage partials of output e = blockIdx.x * EPB + threadIdx.x % EPB, returned to the threads
 // threadIdx.x < EPB (meaningful where e < count).  EPB outputs per workgroup, 256/EPB slices of the partials each, LDS tree over the
 // slices: with 32 outputs per workgroup the norms of one batch (64 outputs, 768-1024 partials) ran on 2 workgroups, ~100

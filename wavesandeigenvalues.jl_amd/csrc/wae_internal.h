@@ -255,6 +255,9 @@ template <class T> struct Dev {     // function-local device array of the assemb
 };
 // keyed triplets (key = row * npoints + col, ne of them with ne <= INT_MAX; one or two value streams) -> CSR of npoints rows
 P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k0, Dev<double> &mv, Dev<double> *kv);
+// keyed values (key = node * n, ne of them, 0 < ne <= INT_MAX) -> the dense real vector of their sums per node (out: n doubles, host), through
+// triplets_to_csr with the single column 0: the same stable sort and reduce-by-key as the matrices
+void pairs_to_dense(int64_t n, size_t ne, Dev<unsigned long long> &k0, Dev<double> &v, double *out);
 // the nodal speed of sound of the *_cpoint entries: required, one finite value per mesh point (checked before anything is launched)
 inline void check_c_point(int64_t npoints, const double *c_point) {
     if (!c_point) throw WaeError(WAE_ERR_INVALID, "c_point is required: one speed of sound per mesh point");
@@ -373,5 +376,10 @@ void launch_axpy2_norm(const cplx *V, size_t stride, int nv, const cplx *c1, con
                        cplx *partial, cplx *norms, cplx *inv_out, hipStream_t s, const unsigned char *cmask = nullptr);
 void launch_gmres_pair_coef(const GmresDev &S, int j, const cplx *c1, const cplx *c2, const cplx *gram, cplx *alpha, cplx *c2m, cplx *hd2, hipStream_t s);
 void launch_gmres_solve_y(const GmresDev &S, int ju, cplx *out, hipStream_t s);
+// forced response (forced.hip): interleaved multivectors of one chunk of frequencies, leading dimension nb, the handle's row numbering
+// B[rows[r]][b] = sum_{s<nsrc} G[b][s] M[r][s] for the nr listed rows (distinct; the other rows of B are not touched)
+void launch_forced_rhs(const int *rows, const cplx *M, int64_t nr, int nsrc, const cplx *G, cplx *B, int nb, hipStream_t s);
+// H[q + nobs*(j0 + b)] = sum_{ptr[q] <= i < ptr[q+1]} val[i] X[idx[i]][b], b < nb: fixed summation order
+void launch_forced_observe(const int64_t *ptr, const int *idx, const cplx *val, int nobs, const cplx *X, int nb, cplx *H, int64_t j0, hipStream_t s);
 // triad for bandwidth measurement
 void launch_triad(double *a, const double *b, const double *c, double s, int64_t n, hipStream_t st, unsigned grid_cap = 8192);

@@ -1,3 +1,3 @@
 """Producers of LinearOperatorFamily objects for the device hot path (the slot Helmholtz.discretize fills)."""
 from . import annulus  # noqa: F401
-from .family import annulus_family, helmholtz_family  # noqa: F401
+from .family import annulus_family, helmholtz_family, speaker_source  # noqa: F401

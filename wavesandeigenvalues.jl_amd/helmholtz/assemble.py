@@ -199,6 +199,58 @@ def assemble_p2_flame(points, tets, flame_tets, ref_tet, x_ref, n_ref, nglobal_s
     return _take_csr(L, h, np.complex128), vol.value
 
 
+# ---- speaker source vector: `discretize(...; source=true)` with a :speaker domain ---------------------------------------------
+def _source_column(s):
+    """the term m = -i·s of the `rhs` family as a complex d x 1 sparse column (sparsevec(I, V, dim) with V ./= 1im, Helmholtz.jl:500,520)"""
+    s = np.asarray(s, dtype=np.float64)
+    idx = np.nonzero(s)[0]
+    return sp.csc_matrix((-1j * s[idx], (idx, np.zeros(len(idx), dtype=np.int64))), shape=(len(s), 1))
+
+
+def _source_c(points, ntris, c_tri, c_point):
+    """(values or None, nodal?) of the speed of sound of a source vector, checked"""
+    cp = _nodal(c_point, c_tri, points.shape[0], "c_tri")
+    if cp is not None:
+        return cp, True
+    if c_tri is None:
+        return None, False
+    cc = np.ascontiguousarray(c_tri, dtype=np.float64)
+    if cc.shape != (ntris,):
+        raise ValueError(f"c_tri has shape {cc.shape}, the speaker domain has {ntris} triangles")
+    return cc, False
+
+
+def assemble_p1_source(points, tris, c_tri=None, device=0, c_point=None):
+    """Source vector of a :speaker boundary on the device (wae_p1_assemble_source, wae_p1_assemble_source_cpoint; src/Helmholtz.jl:488-505):
+    s_a = |e1×e2|·∫c φ_a over the speaker triangles, c per triangle (``c_tri``, None = 1) or per mesh point (``c_point``, linear on every
+    triangle).  Returns the term m = -i·s of the ``rhs`` family as a complex npoints x 1 scipy sparse column."""
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    tt = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    cc, nodal = _source_c(pts, tt.shape[0], c_tri, c_point)
+    L = _lib.lib()
+    dp = C.POINTER(C.c_double)
+    out = np.zeros(pts.shape[0], dtype=np.float64)
+    entry = L.wae_p1_assemble_source_cpoint if nodal else L.wae_p1_assemble_source
+    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
+                     None if cc is None else cc.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+    return _source_column(out)
+
+
+def assemble_p2_source(points, tets, tris, c_tri=None, device=0, c_point=None):
+    """P2 source vector of a :speaker boundary on the device (wae_p2_assemble_source, wae_p2_assemble_source_cpoint): as
+    ``assemble_p1_source`` on the 6-node triangles; ``tets`` gives the edge numbers.  Returns m = -i·s, complex (npoints + nedges) x 1."""
+    pts, tt, tr = _mesh_args(points, tets, tris)
+    cc, nodal = _source_c(pts, tr.shape[0], c_tri, c_point)
+    nedges = len(np.unique(np.sort(np.concatenate([tt[:, [i, j]] for i in range(4) for j in range(i + 1, 4)]), axis=1), axis=0))
+    L = _lib.lib()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    out = np.zeros(pts.shape[0] + nedges, dtype=np.float64)
+    entry = L.wae_p2_assemble_source_cpoint if nodal else L.wae_p2_assemble_source
+    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), tr.shape[0], tr.ctypes.data_as(ip),
+                     None if cc is None else cc.ctypes.data_as(dp), out.ctypes.data_as(dp), len(out)))
+    return _source_column(out)
+
+
 def discrete_adjoint_shape_sensitivity(points, tets, c_tet, surface_points, sol, L, bnd_tris=None, bnd_c=None, Y=None, h=1e-9,
                                        device=0, flame=None, v_ext=None):
     """sens = discrete_adjoint_shape_sensitivity(...)   (src/shape_sensitivity.jl:16-141, full mesh, P1)

@@ -30,6 +30,17 @@ def helmholtz_family(terms, Y=1e15, n=1.0, tau=1e-3, device=0, flame=True):
     return L
 
 
+def speaker_source(m, Y=1e15, A=1.0, device=0):
+    """The ``rhs`` family that ``discretize(mesh, dscrp, c, source=true)`` returns for a :speaker boundary (src/Helmholtz.jl:79,251-258,
+    501-505,519-522): rhs(ω) = ω·Y·A·m with m = -i·s the column of ``assemble_p1_source`` / ``assemble_p2_source``; the response to an
+    excitation at ω is L(ω) \\ rhs(ω) (``nlevp.forced_response``), L carrying the ω·Y·C term of the same triangles."""
+    rhs = LinearOperatorFamily(["ω"], [0.0], device=device)
+    rhs.params["Y"] = complex(Y)
+    rhs.params["A"] = complex(A)
+    rhs.push(Term(m, (pow1, pow1, pow1), (("ω",), ("Y",), ("A",)), "speaker", "m"))
+    return rhs
+
+
 def annulus_family(preset="C2", device=0, **kw):
     """The synthetic annular combustor as a device-backed family; returns (L, problem dict)."""
     pb = annulus.build(preset, **{k: v for k, v in kw.items() if k in ("Y", "n", "tau", "grid")})

@@ -4,6 +4,7 @@ from .algebra import (exp_az, exp_delay, exp_pm, generate_1_gz, generate_exp_az,
 from .beyn import (beyn, beyn_native, compute_moment_matrices, gauss_points, generate_subspace, initialize_V, inpoly,  # noqa: F401
                    moments2eigs, moments2eigs_native, pos_test, project, wn)
 from .tall import TallMatrix  # noqa: F401
+from .forcing import ForcedResponse, forced_response  # noqa: F401
 from .linopfam import (DeviceFamily, LinearOperatorFamily, Operator, Solution, Term, conv_radius, estimate_pol, pade,  # noqa: F401
                        pade_, poly_roots, polyval)
 from .local_solvers import (count_poles_and_zeros, decode_error_flag, eigs, eigs_many, householder, householder_many,

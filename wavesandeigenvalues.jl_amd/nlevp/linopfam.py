@@ -203,6 +203,26 @@ class DeviceFamily:
         self._report(code, info, "solve", quiet=quiet)
         return X[:, 0].copy() if one else X
 
+    def forced_response(self, coeff_table, src, src_coeff, obs, keep=(), tol=1e-12, maxit=300, quiet=False):
+        """wae_forced_response: coeff_table (nfreq, T); src, obs = (ptr, idx, val) sparse vectors in compressed form (nlevp/forcing.py
+        pack_sparse_vectors); src_coeff (nfreq, nsrc); keep: ascending frequency indices.  Returns H (nobs, nfreq), X (d, nkeep), info."""
+        ct = np.ascontiguousarray(coeff_table, dtype=np.complex128).reshape(-1, self.T)
+        nfreq = ct.shape[0]
+        (sptr, sidx, sval), (optr, oidx, oval) = [(np.ascontiguousarray(p, dtype=np.int64), np.ascontiguousarray(i, dtype=np.int32),
+                                                   np.ascontiguousarray(v, dtype=np.complex128)) for p, i, v in (src, obs)]
+        nsrc, nobs = len(sptr) - 1, len(optr) - 1
+        sc = np.ascontiguousarray(src_coeff, dtype=np.complex128).reshape(nfreq, nsrc)
+        kp = np.ascontiguousarray(keep, dtype=np.int32).reshape(-1)
+        H = np.zeros((nobs, nfreq), dtype=np.complex128, order="F")
+        X = np.zeros((self.d, len(kp)), dtype=np.complex128, order="F")
+        info = SolveInfo()
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        code = check(_lib.lib().wae_forced_response(self.handle, nfreq, zptr(ct), nsrc, sptr.ctypes.data_as(i64p), sidx.ctypes.data_as(i32p), zptr(sval),
+                                                    zptr(sc), nobs, optr.ctypes.data_as(i64p), oidx.ctypes.data_as(i32p), zptr(oval), zptr(H),
+                                                    len(kp), kp.ctypes.data_as(i32p), zptr(X), float(tol), int(maxit), C.byref(info)))
+        self._report(code, info, "forced_response", quiet=quiet)
+        return H, X, self.last_info
+
     def beyn_moments(self, z, w, coeff_table, V, K=1, tol=1e-10, maxit=300, out_dev=0):
         z = np.ascontiguousarray(z, dtype=np.complex128)
         w = np.ascontiguousarray(w, dtype=np.complex128)
