@@ -429,7 +429,7 @@ int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points,
  * The local K_ab and K_ba, b_ab and b_ba get the same bits.  Arguments, index checks, pipeline (sorted triplets, no atomics, the same bits
  * on every call) and handle type (wae_p1_info / wae_p1_get / wae_p1_free) are those of the per-simplex entry of the same name.
  * c_point: npoints doubles, required: NULL or a value that is not finite returns WAE_ERR_INVALID and nothing is launched.
- * Not covered: the shape sensitivity (wae_p1_shape_sensitivity* re-discretise with c_tet / c_tri) and Hermite elements. */
+ * The shape sensitivity with a nodal c: wae_p1_shape_sensitivity_cpoint, wae_p2_shape_sensitivity_cpoint below.  Not covered: Hermite elements. */
 int wae_p1_assemble_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, const double *c_point, void **out);
 int wae_p1_assemble_boundary_cpoint(int32_t device, int64_t npoints, const double *points, int64_t ntris, const int32_t *tris, const double *c_point,
                                     void **out);
@@ -483,6 +483,46 @@ int wae_p1_shape_sensitivity_flame(int32_t device, int64_t npoints, const double
                                    const int32_t *pair_pt, const int32_t *pair_tet, int32_t ref_tet, int64_t npair_r, const int32_t *pair_pt_r,
                                    const double *n_ref, const double *v, const double *v_adj, double h, double *det_pm, double *ssum,
                                    double *g_pm, double *g0);
+
+/* The same sensitivity for P2 elements and for a nodal speed of sound.  Semantics, conventions and outputs are those of the two entries
+ * above: per (point, simplex) pair and coordinate the central difference (step h) of two local re-discretisations with the point moved by
+ * +h and -h, contracted with the local entries of v_adj and v; 0-based int32 indices, interleaved complex, out_t[3*npair_t] and
+ * out_s[3*npair_s] summed per point by the caller in pair order.  A pair whose point is no corner of its simplex contributes zero.
+ * npair_t == 0 and npair_s == 0 are allowed; nothing is launched for an empty list, and with both empty nothing at all (the P2 entries then
+ * check nv against an edge count made on the host).  No atomics: the same bits on every call.
+ *  - wae_p2_shape_sensitivity: P2 elements, c per simplex (c_tet, c_tri: NULL = 1).  tets / tris are the plain 4-point / 3-point lists;
+ *    the entry numbers the edges itself (the wae_p2_connectivity pipeline of wae_p2_assemble*: ntets > 0 always, the triangles only if
+ *    npair_s > 0).  Straight-sided elements depend on their corner points only, so only corner points move.  v, v_adj: nv = npoints + nedges
+ *    entries; a wrong nv returns WAE_ERR_INVALID.  The kernel contracts the geometry-free element tensors with the local vector entries
+ *    once per pair and differences only |det J| and |det J| grad l_i . grad l_j  (resp. |(x0-x2) x (x1-x2)|)  at +-h.
+ *  - wae_p1_shape_sensitivity_cpoint, wae_p2_shape_sensitivity_cpoint: c_point (npoints doubles, required, finite) in the place of c_tet
+ *    and c_tri, element matrices of wae_p1_assemble_cpoint / wae_p2_assemble_cpoint and their boundary forms; the nodal values stay with
+ *    their points while a point moves.
+ * WAE_ERR_INVALID with a message in wae_last_error, before any launch: a point, tetrahedron or triangle index out of range in the meshes or
+ * the pair lists, h not finite or <= 0, a c_point value that is not finite, a wrong nv. */
+int wae_p2_shape_sensitivity(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_tet, int64_t npair_t,
+                             const int32_t *pair_pt_t, const int32_t *pair_tet, const int32_t *tris, const double *c_tri, int64_t npair_s,
+                             const int32_t *pair_pt_s, const int32_t *pair_tri, int64_t ntets, int64_t ntris, const double *omega,
+                             const double *omegaY, int64_t nv, const double *v, const double *v_adj, double h, double *out_t, double *out_s);
+int wae_p1_shape_sensitivity_cpoint(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_point, int64_t npair_t,
+                                    const int32_t *pair_pt_t, const int32_t *pair_tet, const int32_t *tris, int64_t npair_s, const int32_t *pair_pt_s,
+                                    const int32_t *pair_tri, int64_t ntets, int64_t ntris, const double *omega, const double *omegaY, const double *v,
+                                    const double *v_adj, double h, double *out_t, double *out_s);
+int wae_p2_shape_sensitivity_cpoint(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_point, int64_t npair_t,
+                                    const int32_t *pair_pt_t, const int32_t *pair_tet, const int32_t *tris, int64_t npair_s, const int32_t *pair_pt_s,
+                                    const int32_t *pair_tri, int64_t ntets, int64_t ntris, const double *omega, const double *omegaY, int64_t nv,
+                                    const double *v, const double *v_adj, double h, double *out_t, double *out_s);
+/* P2 form of wae_p1_shape_sensitivity_flame: the same outputs and the same combination by the caller, with
+ *   ssum = sum_a s_a conj(v_adj_a) over the 10 nodes of the flame tetrahedron, s_a = int phi_a / |det J| (-1/120 on points, 1/30 on edges), so
+ *          that v_adj' S+- = sum over the point's pairs of det_pm * ssum  (P1: det_pm / 24 * ssum);
+ *   g_pm / g0 = sum_b (grad(phi_b)(x_ref) . n_ref) v_b over the 10 nodes of the reference tetrahedron.  x_ref (3 doubles) is fixed in space,
+ *          so its barycentric coordinates are taken in the displaced reference tetrahedron, as wae_p2_assemble_flame takes them in the mesh's.
+ * v, v_adj: nv = npoints + nedges entries (a wrong nv: WAE_ERR_INVALID, as are ref_tet or a flame tetrahedron out of range, an index out of
+ * range, h not finite or <= 0).  The flame does not depend on c. */
+int wae_p2_shape_sensitivity_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t npair,
+                                   const int32_t *pair_pt, const int32_t *pair_tet, int32_t ref_tet, int64_t npair_r, const int32_t *pair_pt_r,
+                                   const double *x_ref, const double *n_ref, int64_t nv, const double *v, const double *v_adj, double h, double *det_pm,
+                                   double *ssum, double *g_pm, double *g0);
 
 /* -- tall matrices: Beyn's eigenpair extraction on the device ------------------------------------------------------
  * The step that turns the moments into eigenpairs (beyn.jl:76-107; `moments2eigs`, beyn.jl:289-323): block Hankel matrices

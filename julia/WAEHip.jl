@@ -1628,34 +1628,100 @@ v, v_adj normalised as there (vᴴv = 1, v_adjᴴ L'(ω) v = 1).  One device thr
 point are summed here in order."
 function discrete_adjoint_shape_sensitivity_p1(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, c_tet, surface_points::AbstractVector{<:Integer},
                                                ω::ComplexF64, v::Vector{ComplexF64}, v_adj::Vector{ComplexF64};
-                                               bnd_tris=nothing, bnd_c=nothing, Y=0.0, h::Float64=1e-9, device::Integer=0)
+                                               bnd_tris=nothing, bnd_c=nothing, c_point=nothing, Y=0.0, h::Float64=1e-9, device::Integer=0)
     t0 = _zero_based(tets)
-    lut = zeros(Int, size(points, 2)); for (i, p) in enumerate(surface_points); lut[p] = i; end
-    pair_pt_t = Int32[]; pair_tet = Int32[]; own_t = Int[]
-    for e in 1:size(t0, 2), a in 1:4
-        p = t0[a, e] + 1
-        lut[p] > 0 && (push!(pair_pt_t, p - 1); push!(pair_tet, e - 1); push!(own_t, lut[p]))
-    end
     s0 = bnd_tris === nothing ? zeros(Int32, 3, 0) : _zero_based(bnd_tris)
-    pair_pt_s = Int32[]; pair_tri = Int32[]; own_s = Int[]
-    for e in 1:size(s0, 2), a in 1:3
-        p = s0[a, e] + 1
-        lut[p] > 0 && (push!(pair_pt_s, p - 1); push!(pair_tri, e - 1); push!(own_s, lut[p]))
-    end
+    pair_pt_t, pair_tet, own_t = _shape_pairs(t0, surface_points, size(points, 2))
+    pair_pt_s, pair_tri, own_s = _shape_pairs(s0, surface_points, size(points, 2))
+    length(v) == size(points, 2) && length(v_adj) == size(points, 2) || throw(ArgumentError("v and v_adj need one entry per mesh point"))
     out_t = zeros(ComplexF64, 3, length(pair_tet)); out_s = zeros(ComplexF64, 3, length(pair_tri))
-    cc = c_tet === nothing ? C_NULL : Vector{Float64}(c_tet)
-    bc = (bnd_c === nothing || isempty(pair_tri)) ? C_NULL : Vector{Float64}(bnd_c)
     om = Float64[real(ω), imag(ω)]; omy = Float64[real(ω * Y), imag(ω * Y)]
-    check(ccall((:wae_p1_shape_sensitivity, libwaehip), Cint,
-                (Int32, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32},
-                 Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Float64, Ptr{ComplexF64}, Ptr{ComplexF64}),
-                device, size(points, 2), points, t0, cc, length(pair_tet), pair_pt_t, pair_tet, isempty(pair_tri) ? C_NULL : s0, bc, length(pair_tri),
-                isempty(pair_tri) ? C_NULL : pair_pt_s, isempty(pair_tri) ? C_NULL : pair_tri, size(t0, 2), size(s0, 2), om, omy, v, v_adj, h,
-                isempty(pair_tet) ? C_NULL : out_t, isempty(pair_tri) ? C_NULL : out_s))
-    sens = zeros(ComplexF64, 3, length(surface_points))
+    if c_point !== nothing
+        (c_tet === nothing && bnd_c === nothing) || throw(ArgumentError("give the speed of sound per point (c_point) or per simplex (c_tet, bnd_c), not both"))
+        length(c_point) == size(points, 2) || throw(ArgumentError("c_point needs one value per mesh point"))
+        check(ccall((:wae_p1_shape_sensitivity_cpoint, libwaehip), Cint,
+                    (Int32, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32},
+                     Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Float64, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                    device, size(points, 2), points, t0, Vector{Float64}(c_point), length(pair_tet), pair_pt_t, pair_tet, isempty(pair_tri) ? C_NULL : s0,
+                    length(pair_tri), isempty(pair_tri) ? C_NULL : pair_pt_s, isempty(pair_tri) ? C_NULL : pair_tri, size(t0, 2), size(s0, 2), om, omy, v,
+                    v_adj, h, isempty(pair_tet) ? C_NULL : out_t, isempty(pair_tri) ? C_NULL : out_s))
+    else
+        cc = c_tet === nothing ? C_NULL : Vector{Float64}(c_tet)
+        bc = (bnd_c === nothing || isempty(pair_tri)) ? C_NULL : Vector{Float64}(bnd_c)
+        check(ccall((:wae_p1_shape_sensitivity, libwaehip), Cint,
+                    (Int32, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32},
+                     Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Float64, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                    device, size(points, 2), points, t0, cc, length(pair_tet), pair_pt_t, pair_tet, isempty(pair_tri) ? C_NULL : s0, bc, length(pair_tri),
+                    isempty(pair_tri) ? C_NULL : pair_pt_s, isempty(pair_tri) ? C_NULL : pair_tri, size(t0, 2), size(s0, 2), om, omy, v, v_adj, h,
+                    isempty(pair_tet) ? C_NULL : out_t, isempty(pair_tri) ? C_NULL : out_s))
+    end
+    return _shape_sum(length(surface_points), own_t, out_t, own_s, out_s)
+end
+
+"(pair_pt, pair_simplex, own): every (surface point, simplex that has it as a corner) pair, 0-based for the library, in simplex order;
+own = position of the point in surface_points.  `simplices`: 0-based, one column each."
+function _shape_pairs(simplices::AbstractMatrix{<:Integer}, surface_points::AbstractVector{<:Integer}, npoints::Integer)
+    lut = zeros(Int, npoints); for (i, p) in enumerate(surface_points); lut[p] = i; end
+    pair_pt = Int32[]; pair_sx = Int32[]; own = Int[]
+    for e in 1:size(simplices, 2), a in 1:size(simplices, 1)
+        p = simplices[a, e] + 1
+        lut[p] > 0 && (push!(pair_pt, p - 1); push!(pair_sx, e - 1); push!(own, lut[p]))
+    end
+    return pair_pt, pair_sx, own
+end
+
+"the pairs of a point summed in pair order: tetrahedra first, then triangles"
+function _shape_sum(ns::Integer, own_t, out_t, own_s, out_s)
+    sens = zeros(ComplexF64, 3, ns)
     for (q, i) in enumerate(own_t); sens[:, i] .+= out_t[:, q]; end
     for (q, i) in enumerate(own_s); sens[:, i] .+= out_s[:, q]; end
     return sens
+end
+
+"number of distinct edges of the tetrahedra (0- or 1-based columns): the edge DoFs of the P2 space"
+function _p2_edge_count(tets::AbstractMatrix{<:Integer})
+    E = Set{Tuple{Int,Int}}()
+    for e in 1:size(tets, 2), i in 1:3, j in i+1:4
+        push!(E, minmax(Int(tets[i, e]), Int(tets[j, e])))
+    end
+    return length(E)
+end
+
+"sens (3 x length(surface_points)) = discrete_adjoint_shape_sensitivity_p2(points, tets, c_tet, surface_points, ω, v, v_adj; ...): the same
+sensitivity for P2 elements (wae_p2_shape_sensitivity; c_point=: wae_p2_shape_sensitivity_cpoint).  tets / bnd_tris are the plain 4-point /
+3-point lists, the library numbers the edges (wae_p2_connectivity); v, v_adj have npoints + nedges entries in that numbering.  Only the
+corner points of the straight-sided elements move."
+function discrete_adjoint_shape_sensitivity_p2(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, c_tet, surface_points::AbstractVector{<:Integer},
+                                               ω::ComplexF64, v::Vector{ComplexF64}, v_adj::Vector{ComplexF64};
+                                               bnd_tris=nothing, bnd_c=nothing, c_point=nothing, Y=0.0, h::Float64=1e-9, device::Integer=0)
+    t0 = _zero_based(tets)
+    s0 = bnd_tris === nothing ? zeros(Int32, 3, 0) : _zero_based(bnd_tris)
+    pair_pt_t, pair_tet, own_t = _shape_pairs(t0, surface_points, size(points, 2))
+    pair_pt_s, pair_tri, own_s = _shape_pairs(s0, surface_points, size(points, 2))
+    nv = size(points, 2) + _p2_edge_count(t0)
+    length(v) == nv && length(v_adj) == nv || throw(ArgumentError("v and v_adj need npoints + nedges = $nv entries"))
+    out_t = zeros(ComplexF64, 3, length(pair_tet)); out_s = zeros(ComplexF64, 3, length(pair_tri))
+    om = Float64[real(ω), imag(ω)]; omy = Float64[real(ω * Y), imag(ω * Y)]
+    if c_point !== nothing
+        (c_tet === nothing && bnd_c === nothing) || throw(ArgumentError("give the speed of sound per point (c_point) or per simplex (c_tet, bnd_c), not both"))
+        length(c_point) == size(points, 2) || throw(ArgumentError("c_point needs one value per mesh point"))
+        check(ccall((:wae_p2_shape_sensitivity_cpoint, libwaehip), Cint,
+                    (Int32, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32},
+                     Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{ComplexF64}, Ptr{ComplexF64}, Float64, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                    device, size(points, 2), points, t0, Vector{Float64}(c_point), length(pair_tet), pair_pt_t, pair_tet, isempty(pair_tri) ? C_NULL : s0,
+                    length(pair_tri), isempty(pair_tri) ? C_NULL : pair_pt_s, isempty(pair_tri) ? C_NULL : pair_tri, size(t0, 2), size(s0, 2), om, omy, nv,
+                    v, v_adj, h, isempty(pair_tet) ? C_NULL : out_t, isempty(pair_tri) ? C_NULL : out_s))
+    else
+        cc = c_tet === nothing ? C_NULL : Vector{Float64}(c_tet)
+        bc = (bnd_c === nothing || isempty(pair_tri)) ? C_NULL : Vector{Float64}(bnd_c)
+        check(ccall((:wae_p2_shape_sensitivity, libwaehip), Cint,
+                    (Int32, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32},
+                     Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{ComplexF64}, Ptr{ComplexF64}, Float64, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                    device, size(points, 2), points, t0, cc, length(pair_tet), pair_pt_t, pair_tet, isempty(pair_tri) ? C_NULL : s0, bc, length(pair_tri),
+                    isempty(pair_tri) ? C_NULL : pair_pt_s, isempty(pair_tri) ? C_NULL : pair_tri, size(t0, 2), size(s0, 2), om, omy, nv, v, v_adj, h,
+                    isempty(pair_tet) ? C_NULL : out_t, isempty(pair_tri) ? C_NULL : out_s))
+    end
+    return _shape_sum(length(surface_points), own_t, out_t, own_s, out_s)
 end
 
 "flame part of the same sensitivity (a :flame entry in dscrp; shape_sensitivity.jl:62-141): -v_adjᴴ coeff (Q₊ - Q₋)/(2h) v per surface
@@ -1665,8 +1731,42 @@ function discrete_adjoint_shape_sensitivity_p1_flame(points::Matrix{Float64}, te
                                                      flame_tets::AbstractVector{<:Integer}, ref_tet::Integer, n_ref::Vector{Float64}, nglobal_scaled::Real,
                                                      coeff::ComplexF64, v::Vector{ComplexF64}, v_adj::Vector{ComplexF64}; h::Float64=1e-9, device::Integer=0)
     t0 = _zero_based(tets)
-    ns = length(surface_points)
-    lut = zeros(Int, size(points, 2)); for (i, p) in enumerate(surface_points); lut[p] = i; end
+    pair_pt, pair_tet, own, pair_pt_r, own_r = _flame_pairs(t0, surface_points, size(points, 2), flame_tets, ref_tet)
+    np, nr = length(pair_tet), length(pair_pt_r)
+    det_pm = zeros(Float64, 2, 3, np); ssum = zeros(ComplexF64, np); g_pm = zeros(ComplexF64, 2, 3, nr); g0 = zeros(ComplexF64, 1)
+    check(ccall((:wae_p1_shape_sensitivity_flame, libwaehip), Cint,
+                (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32}, Int32, Int64, Ptr{Int32}, Ptr{Float64},
+                 Ptr{ComplexF64}, Ptr{ComplexF64}, Float64, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                device, size(points, 2), points, size(t0, 2), t0, np, np == 0 ? C_NULL : pair_pt, np == 0 ? C_NULL : pair_tet, ref_tet - 1, nr,
+                nr == 0 ? C_NULL : pair_pt_r, n_ref, v, v_adj, h, np == 0 ? C_NULL : det_pm, np == 0 ? C_NULL : ssum, nr == 0 ? C_NULL : g_pm, g0))
+    return _flame_combine(length(surface_points), own, own_r, det_pm, ssum, g_pm, g0, 24, nglobal_scaled, coeff, h)
+end
+
+"the P2 form (wae_p2_shape_sensitivity_flame): v, v_adj have npoints + nedges entries, and x_ref is the point of the reference tetrahedron
+at which the gradients are taken (as for assemble_p2_flame); it stays where it is while the tetrahedron's corners move."
+function discrete_adjoint_shape_sensitivity_p2_flame(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, surface_points::AbstractVector{<:Integer},
+                                                     flame_tets::AbstractVector{<:Integer}, ref_tet::Integer, x_ref::Vector{Float64}, n_ref::Vector{Float64},
+                                                     nglobal_scaled::Real, coeff::ComplexF64, v::Vector{ComplexF64}, v_adj::Vector{ComplexF64};
+                                                     h::Float64=1e-9, device::Integer=0)
+    t0 = _zero_based(tets)
+    nv = size(points, 2) + _p2_edge_count(t0)
+    length(v) == nv && length(v_adj) == nv || throw(ArgumentError("v and v_adj need npoints + nedges = $nv entries"))
+    pair_pt, pair_tet, own, pair_pt_r, own_r = _flame_pairs(t0, surface_points, size(points, 2), flame_tets, ref_tet)
+    np, nr = length(pair_tet), length(pair_pt_r)
+    det_pm = zeros(Float64, 2, 3, np); ssum = zeros(ComplexF64, np); g_pm = zeros(ComplexF64, 2, 3, nr); g0 = zeros(ComplexF64, 1)
+    check(ccall((:wae_p2_shape_sensitivity_flame, libwaehip), Cint,
+                (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32}, Int32, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+                 Int64, Ptr{ComplexF64}, Ptr{ComplexF64}, Float64, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                device, size(points, 2), points, size(t0, 2), t0, np, np == 0 ? C_NULL : pair_pt, np == 0 ? C_NULL : pair_tet, ref_tet - 1, nr,
+                nr == 0 ? C_NULL : pair_pt_r, x_ref, n_ref, nv, v, v_adj, h, np == 0 ? C_NULL : det_pm, np == 0 ? C_NULL : ssum, nr == 0 ? C_NULL : g_pm,
+                g0))
+    return _flame_combine(length(surface_points), own, own_r, det_pm, ssum, g_pm, g0, 1, nglobal_scaled, coeff, h)       # the weights of S are inside ssum
+end
+
+"(pair_pt, pair_tet, own) of the flame tetrahedra and (pair_pt_r, own_r) of the reference tetrahedron's corners that are surface points"
+function _flame_pairs(t0::AbstractMatrix{<:Integer}, surface_points::AbstractVector{<:Integer}, npoints::Integer, flame_tets::AbstractVector{<:Integer},
+                      ref_tet::Integer)
+    lut = zeros(Int, npoints); for (i, p) in enumerate(surface_points); lut[p] = i; end
     pair_pt = Int32[]; pair_tet = Int32[]; own = Int[]
     for e in flame_tets, a in 1:4
         p = t0[a, e] + 1
@@ -1677,16 +1777,15 @@ function discrete_adjoint_shape_sensitivity_p1_flame(points::Matrix{Float64}, te
         p = t0[a, ref_tet] + 1
         lut[p] > 0 && (push!(pair_pt_r, p - 1); push!(own_r, lut[p]))
     end
-    np, nr = length(pair_tet), length(pair_pt_r)
-    det_pm = zeros(Float64, 2, 3, np); ssum = zeros(ComplexF64, np); g_pm = zeros(ComplexF64, 2, 3, nr); g0 = zeros(ComplexF64, 1)
-    check(ccall((:wae_p1_shape_sensitivity_flame, libwaehip), Cint,
-                (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32}, Int32, Int64, Ptr{Int32}, Ptr{Float64},
-                 Ptr{ComplexF64}, Ptr{ComplexF64}, Float64, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}),
-                device, size(points, 2), points, size(t0, 2), t0, np, np == 0 ? C_NULL : pair_pt, np == 0 ? C_NULL : pair_tet, ref_tet - 1, nr,
-                nr == 0 ? C_NULL : pair_pt_r, n_ref, v, v_adj, h, np == 0 ? C_NULL : det_pm, np == 0 ? C_NULL : ssum, nr == 0 ? C_NULL : g_pm, g0))
+    return pair_pt, pair_tet, own, pair_pt_r, own_r
+end
+
+"the host side of both flame entries: per point v_adjᴴ S± = Σ det_pm/divisor·ssum over its pairs, the volume of ITS flame tetrahedra, and
+-coeff (v_adjᴴ Q₊ v - v_adjᴴ Q₋ v)/(2h) with Q = S ⊗ g, g = -(nglobal_scaled / volume) ∇φ·n_ref"
+function _flame_combine(ns::Integer, own, own_r, det_pm, ssum, g_pm, g0, divisor::Real, nglobal_scaled::Real, coeff::ComplexF64, h::Float64)
     a_pm = zeros(ComplexF64, 2, 3, ns); V_pm = zeros(Float64, 2, 3, ns)      # v_adjᴴ S± and the volume of the point's flame tetrahedra
     for (q, i) in enumerate(own)
-        a_pm[:, :, i] .+= det_pm[:, :, q] ./ 24 .* ssum[q]; V_pm[:, :, i] .+= det_pm[:, :, q] ./ 6
+        a_pm[:, :, i] .+= det_pm[:, :, q] ./ divisor .* ssum[q]; V_pm[:, :, i] .+= det_pm[:, :, q] ./ 6
     end
     b_pm = fill(g0[1], 2, 3, ns)                                             # Σ_b ∇φ_b·n_ref v_b on the reference tetrahedron
     for (q, i) in enumerate(own_r); b_pm[:, :, i] = g_pm[:, :, q]; end

@@ -42,6 +42,7 @@ EXPORTS = [
     "wae_p2_assemble_boundary", "wae_p2_assemble_flame",
     "wae_p1_assemble_cpoint", "wae_p1_assemble_boundary_cpoint", "wae_p2_assemble_cpoint", "wae_p2_assemble_boundary_cpoint",
     "wae_p1_assemble_source", "wae_p1_assemble_source_cpoint", "wae_p2_assemble_source", "wae_p2_assemble_source_cpoint", "wae_forced_response",
+    "wae_p2_shape_sensitivity", "wae_p1_shape_sensitivity_cpoint", "wae_p2_shape_sensitivity_cpoint", "wae_p2_shape_sensitivity_flame",
 ]
 TALL_MAXCOLS = 64           # WAE_TALL_MAXCOLS
 
@@ -143,6 +144,14 @@ def lib():
                                            C.c_int64, C.c_int64, dp, dp, dp, dp, C.c_double, dp, dp]
     L.wae_p1_shape_sensitivity_flame.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, i32p, C.c_int32, C.c_int64, i32p, dp, dp, dp,
                                                  C.c_double, dp, dp, dp, dp]
+    L.wae_p2_shape_sensitivity.argtypes = [C.c_int32, C.c_int64, dp, i32p, dp, C.c_int64, i32p, i32p, i32p, dp, C.c_int64, i32p, i32p,
+                                           C.c_int64, C.c_int64, dp, dp, C.c_int64, dp, dp, C.c_double, dp, dp]
+    L.wae_p1_shape_sensitivity_cpoint.argtypes = [C.c_int32, C.c_int64, dp, i32p, dp, C.c_int64, i32p, i32p, i32p, C.c_int64, i32p, i32p,
+                                                  C.c_int64, C.c_int64, dp, dp, dp, dp, C.c_double, dp, dp]
+    L.wae_p2_shape_sensitivity_cpoint.argtypes = [C.c_int32, C.c_int64, dp, i32p, dp, C.c_int64, i32p, i32p, i32p, C.c_int64, i32p, i32p,
+                                                  C.c_int64, C.c_int64, dp, dp, C.c_int64, dp, dp, C.c_double, dp, dp]
+    L.wae_p2_shape_sensitivity_flame.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, i32p, C.c_int32, C.c_int64, i32p, dp, dp,
+                                                 C.c_int64, dp, dp, C.c_double, dp, dp, dp, dp]
     L.wae_bench_spmv.argtypes = [C.c_void_p, dp, C.c_int32, C.c_int32, dp]
     L.wae_bench_triad.argtypes = [C.c_int32, C.c_int64, C.c_int32, dp]
     L.wae_bench_spmv_level.argtypes = [C.c_void_p, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(C.c_int64)]

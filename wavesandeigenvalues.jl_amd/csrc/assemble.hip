@@ -72,7 +72,10 @@ __device__ inline void p1_local_cpoint(const double X[4][3], const double c[4], 
 // Discrete-adjoint shape sensitivity (src/shape_sensitivity.jl:16-141), interior part: for the pair (surface point p,
 // adjacent tetrahedron t) and coordinate x:  out = -v_adj_loc^H [ w^2 (M+ - M-) + (K+ - K-) ] v_loc / (2h), M+-/K+- the local
 // matrices with x_p moved by +-h (central difference of two local re-discretisations, as the reference does).
-__global__ __launch_bounds__(256) void shape_tet_kernel(const double *__restrict__ pts, const int *__restrict__ tets, const double *__restrict__ c_tet,
+// NODAL: cs holds one speed of sound per mesh point (p1_local_cpoint; the values stay with their points while a point moves), else one per
+// tetrahedron (NULL = 1).
+template <bool NODAL>
+__global__ __launch_bounds__(256) void shape_tet_kernel(const double *__restrict__ pts, const int *__restrict__ tets, const double *__restrict__ cs,
                                                         int64_t npair, const int *__restrict__ pair_pt, const int *__restrict__ pair_tet,
                                                         double wr, double wi, const cplx *__restrict__ v, const cplx *__restrict__ vadj, double h,
                                                         cplx *__restrict__ out) {
@@ -90,11 +93,27 @@ __global__ __launch_bounds__(256) void shape_tet_kernel(const double *__restrict
         for (int k = 0; k < 3; ++k) X[a][k] = pts[(size_t)vtx[a] * 3 + k];
     }
     if (a0 < 0) { out[e] = cplx{0.0, 0.0}; return; }
-    const double c = c_tet ? c_tet[t] : 1.0;
-    const double x0 = X[a0][crd];
     double Mp[16], Kp[16], Mm[16], Km[16];
-    X[a0][crd] = x0 + h; p1_local(X, c, Mp, Kp);
-    X[a0][crd] = x0 - h; p1_local(X, c, Mm, Km);
+    if (NODAL) {                                           // the moved corner enters through selects on unrolled counters: no run-time index, no scratch
+        double c[4], Xp[4][3], Xm[4][3];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            c[a] = cs[vtx[a]];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const bool moved = a == a0 && k == crd;
+                Xp[a][k] = moved ? X[a][k] + h : X[a][k];
+                Xm[a][k] = moved ? X[a][k] - h : X[a][k];
+            }
+        }
+        p1_local_cpoint(Xp, c, Mp, Kp);
+        p1_local_cpoint(Xm, c, Mm, Km);
+    } else {
+        const double c = cs ? cs[t] : 1.0;
+        const double x0 = X[a0][crd];
+        X[a0][crd] = x0 + h; p1_local(X, c, Mp, Kp);
+        X[a0][crd] = x0 - h; p1_local(X, c, Mm, Km);
+    }
     const double w2r = wr * wr - wi * wi, w2i = 2.0 * wr * wi;
     const double s = 1.0 / (2.0 * h);
     cplx acc = {0.0, 0.0};
@@ -113,8 +132,10 @@ __global__ __launch_bounds__(256) void shape_tet_kernel(const double *__restrict
 }
 
 // boundary (admittance) part: C_ab = -i c |(x0-x2) x (x1-x2)| (1+delta_ab)/24 (FEM.jl:435-441, Helmholtz.jl:151-156,459),
-// operator term w*Y*C:  out = -v_adj_loc^H [ w Y (C+ - C-) ] v_loc / (2h)
-__global__ __launch_bounds__(256) void shape_tri_kernel(const double *__restrict__ pts, const int *__restrict__ tris, const double *__restrict__ c_tri,
+// operator term w*Y*C:  out = -v_adj_loc^H [ w Y (C+ - C-) ] v_loc / (2h).  NODAL: cs holds one speed of sound per mesh point and the weights
+// are those of p1_boundary_cpoint_kernel, b_aa = |..| (2 c_a + S)/60, b_ab = |..| (c_a + c_b + S)/120; else one value per triangle.
+template <bool NODAL>
+__global__ __launch_bounds__(256) void shape_tri_kernel(const double *__restrict__ pts, const int *__restrict__ tris, const double *__restrict__ cs,
                                                         int64_t npair, const int *__restrict__ pair_pt, const int *__restrict__ pair_tri,
                                                         double wyr, double wyi, const cplx *__restrict__ v, const cplx *__restrict__ vadj, double h,
                                                         cplx *__restrict__ out) {
@@ -141,14 +162,18 @@ __global__ __launch_bounds__(256) void shape_tri_kernel(const double *__restrict
     const double x0 = X[a0][crd];
     X[a0][crd] = x0 + h; const double dp = area2();
     X[a0][crd] = x0 - h; const double dm = area2();
-    const double dd = c_tri[t] * (dp - dm) / (2.0 * h) / 24.0;          // d/dx of c |..| /24; C = -i * that * (1+delta)
+    double cn[3] = {1.0, 1.0, 1.0};
+    if (NODAL)
+        for (int a = 0; a < 3; ++a) cn[a] = cs[vtx[a]];
+    const double S = cn[0] + cn[1] + cn[2];
+    const double dd = NODAL ? (dp - dm) / (2.0 * h) : cs[t] * (dp - dm) / (2.0 * h) / 24.0;          // d/dx of c |..| /24; C = -i * that * (1+delta)
     // w Y C' = (wyr + i wyi) * (-i) * dd * (1+delta) = (wyi - i wyr) dd (1+delta)
     const cplx f = {wyi * dd, -wyr * dd};
     cplx acc = {0.0, 0.0};
     for (int a = 0; a < 3; ++a) {
         const cplx ya = vadj[vtx[a]];
         for (int b = 0; b < 3; ++b) {
-            const double m = (a == b) ? 2.0 : 1.0;
+            const double m = NODAL ? (a == b ? (2.0 * cn[a] + S) / 60.0 : ((cn[a] + cn[b]) + S) / 120.0) : (a == b) ? 2.0 : 1.0;
             const cplx xb = v[vtx[b]];
             const cplx Dx = {m * (f.x * xb.x - f.y * xb.y), m * (f.x * xb.y + f.y * xb.x)};
             acc.x += ya.x * Dx.x + ya.y * Dx.y;
@@ -631,12 +656,18 @@ int wae_p1_assemble_cpoint(int32_t device, int64_t npoints, const double *points
     return p1_assemble_interior(device, npoints, points, ntets, tets, c_point, true, out);
 }
 
-int wae_p1_shape_sensitivity(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_tet, int64_t npair_t,
-                             const int32_t *pair_pt_t, const int32_t *pair_tet, const int32_t *tris, const double *c_tri, int64_t npair_s,
-                             const int32_t *pair_pt_s, const int32_t *pair_tri, int64_t ntets, int64_t ntris, const double *omega,
-                             const double *omegaY, const double *v, const double *v_adj, double h, double *out_t, double *out_s) {
+// c_tet / c_tri: per tetrahedron (NULL = 1) / per triangle, or, nodal, both the one array per mesh point (required, finite)
+static int p1_shape_sensitivity(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_tet, int64_t npair_t,
+                                const int32_t *pair_pt_t, const int32_t *pair_tet, const int32_t *tris, const double *c_tri, bool nodal, int64_t npair_s,
+                                const int32_t *pair_pt_s, const int32_t *pair_tri, int64_t ntets, int64_t ntris, const double *omega,
+                                const double *omegaY, const double *v, const double *v_adj, double h, double *out_t, double *out_s) {
     return wae_guarded([&]() {
         if (!(npoints > 0 && points && v && v_adj && omega && h > 0.0)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        if (nodal) {
+            if (!std::isfinite(h)) throw WaeError(WAE_ERR_INVALID, "the step h must be finite and positive");
+            if (npair_t < 0 || npair_s < 0) throw WaeError(WAE_ERR_INVALID, "bad argument");
+            check_c_point(npoints, c_tet);
+        }
         if (npair_t > 0 && !(tets && pair_pt_t && pair_tet && out_t && ntets > 0)) throw WaeError(WAE_ERR_INVALID, "bad tetrahedron pair arguments");
         if (npair_s > 0 && !(tris && c_tri && pair_pt_s && pair_tri && out_s && omegaY && ntris > 0)) throw WaeError(WAE_ERR_INVALID, "bad triangle pair arguments");
         for (int64_t i = 0; i < npair_t; ++i)
@@ -655,32 +686,56 @@ int wae_p1_shape_sensitivity(int32_t device, int64_t npoints, const double *poin
         HIP_CHECK(hipMemcpy(dva.p, v_adj, (size_t)npoints * sizeof(cplx), hipMemcpyHostToDevice));
         if (npair_t > 0) {
             Dev<int> dt((size_t)ntets * 4), dpp((size_t)npair_t), dpt((size_t)npair_t);
-            Dev<double> dc(c_tet ? (size_t)ntets : 1);
+            const size_t nc = (size_t)(nodal ? npoints : ntets);
+            Dev<double> dc(c_tet ? nc : 1);
             Dev<cplx> dout((size_t)npair_t * 3);
             HIP_CHECK(hipMemcpy(dt.p, tets, (size_t)ntets * 4 * sizeof(int), hipMemcpyHostToDevice));
-            if (c_tet) HIP_CHECK(hipMemcpy(dc.p, c_tet, (size_t)ntets * sizeof(double), hipMemcpyHostToDevice));
+            if (c_tet) HIP_CHECK(hipMemcpy(dc.p, c_tet, nc * sizeof(double), hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(dpp.p, pair_pt_t, (size_t)npair_t * sizeof(int), hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(dpt.p, pair_tet, (size_t)npair_t * sizeof(int), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(shape_tet_kernel, dim3((unsigned)((npair_t * 3 + 255) / 256)), dim3(256), 0, 0, dpts.p, dt.p, c_tet ? dc.p : nullptr, npair_t,
-                               dpp.p, dpt.p, omega[0], omega[1], dv.p, dva.p, h, dout.p);
+            const dim3 grid((unsigned)((npair_t * 3 + 255) / 256));
+            if (nodal) hipLaunchKernelGGL(shape_tet_kernel<true>, grid, dim3(256), 0, 0, dpts.p, dt.p, dc.p, npair_t, dpp.p, dpt.p, omega[0], omega[1], dv.p,
+                                          dva.p, h, dout.p);
+            else hipLaunchKernelGGL(shape_tet_kernel<false>, grid, dim3(256), 0, 0, dpts.p, dt.p, c_tet ? dc.p : nullptr, npair_t, dpp.p, dpt.p, omega[0],
+                                    omega[1], dv.p, dva.p, h, dout.p);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipMemcpy(out_t, dout.p, (size_t)npair_t * 3 * sizeof(cplx), hipMemcpyDeviceToHost));
         }
         if (npair_s > 0) {
             Dev<int> dt((size_t)ntris * 3), dpp((size_t)npair_s), dpt((size_t)npair_s);
-            Dev<double> dc((size_t)ntris);
+            const size_t nc = (size_t)(nodal ? npoints : ntris);
+            Dev<double> dc(nc);
             Dev<cplx> dout((size_t)npair_s * 3);
             HIP_CHECK(hipMemcpy(dt.p, tris, (size_t)ntris * 3 * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dc.p, c_tri, (size_t)ntris * sizeof(double), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(dc.p, c_tri, nc * sizeof(double), hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(dpp.p, pair_pt_s, (size_t)npair_s * sizeof(int), hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(dpt.p, pair_tri, (size_t)npair_s * sizeof(int), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(shape_tri_kernel, dim3((unsigned)((npair_s * 3 + 255) / 256)), dim3(256), 0, 0, dpts.p, dt.p, dc.p, npair_s, dpp.p, dpt.p,
-                               omegaY[0], omegaY[1], dv.p, dva.p, h, dout.p);
+            const dim3 grid((unsigned)((npair_s * 3 + 255) / 256));
+            if (nodal) hipLaunchKernelGGL(shape_tri_kernel<true>, grid, dim3(256), 0, 0, dpts.p, dt.p, dc.p, npair_s, dpp.p, dpt.p, omegaY[0], omegaY[1], dv.p,
+                                          dva.p, h, dout.p);
+            else hipLaunchKernelGGL(shape_tri_kernel<false>, grid, dim3(256), 0, 0, dpts.p, dt.p, dc.p, npair_s, dpp.p, dpt.p, omegaY[0], omegaY[1], dv.p,
+                                    dva.p, h, dout.p);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipMemcpy(out_s, dout.p, (size_t)npair_s * 3 * sizeof(cplx), hipMemcpyDeviceToHost));
         }
         return WAE_OK;
     });
+}
+
+int wae_p1_shape_sensitivity(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_tet, int64_t npair_t,
+                             const int32_t *pair_pt_t, const int32_t *pair_tet, const int32_t *tris, const double *c_tri, int64_t npair_s,
+                             const int32_t *pair_pt_s, const int32_t *pair_tri, int64_t ntets, int64_t ntris, const double *omega,
+                             const double *omegaY, const double *v, const double *v_adj, double h, double *out_t, double *out_s) {
+    return p1_shape_sensitivity(device, npoints, points, tets, c_tet, npair_t, pair_pt_t, pair_tet, tris, c_tri, false, npair_s, pair_pt_s, pair_tri, ntets,
+                                ntris, omega, omegaY, v, v_adj, h, out_t, out_s);
+}
+
+int wae_p1_shape_sensitivity_cpoint(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_point, int64_t npair_t,
+                                    const int32_t *pair_pt_t, const int32_t *pair_tet, const int32_t *tris, int64_t npair_s, const int32_t *pair_pt_s,
+                                    const int32_t *pair_tri, int64_t ntets, int64_t ntris, const double *omega, const double *omegaY, const double *v,
+                                    const double *v_adj, double h, double *out_t, double *out_s) {
+    return p1_shape_sensitivity(device, npoints, points, tets, c_point, npair_t, pair_pt_t, pair_tet, tris, c_point, true, npair_s, pair_pt_s, pair_tri, ntets,
+                                ntris, omega, omegaY, v, v_adj, h, out_t, out_s);
 }
 
 int wae_p1_shape_sensitivity_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t npair,

@@ -16,8 +16,10 @@
 // gives every local matrix exactly: the tables below are made from it at compile time, none is copied from anywhere.
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <climits>
 #include <memory>
+#include <vector>
 
 #include "wae_internal.h"
 
@@ -493,6 +495,361 @@ __global__ __launch_bounds__(256) void p2_flame_kernel(const int *__restrict__ t
     }
 }
 
+// ---- discrete-adjoint shape sensitivity ------------------------------------------------------------------------------------------------
+// -v_adj^H (L+ - L-)/(2h) v of src/shape_sensitivity.jl:16-141 for P2 elements, L+- the operator re-discretised with one corner of the
+// simplex moved by +-h.  Straight-sided elements: everything but |det J| and the four grad l_i is independent of the geometry, so a thread
+// contracts the element tensors with its 10 (6) vector entries once and differences only the geometric factors.  With x = v_loc,
+// y = v_adj_loc, xi_ik = sum_b d[b][i][k] x_b (grad u = sum_k l_k sum_i xi_ik grad l_i), eta likewise for y, and the symmetric
+// W_km = int c^2 l_k l_m / |det J|  (c per tetrahedron: c^2 (1 + delta_km)/120; nodal c: the quart table of p2_local_cpoint_kernel):
+//     y^H M x = |det J| (y^H Mhat x),        y^H K x = -sum_ij T_ij (|det J| grad l_i . grad l_j),   T_ij = sum_km W_km conj(eta_ik) xi_jm
+// Only p2_shape_geometry is evaluated at +-h.  Every array below is indexed by unrolled loop counters only: the moved corner a0 and the
+// coordinate enter through selects, never through an index.
+__device__ constexpr int p2_sym(int k, int m) { return k <= m ? k * 4 - k * (k - 1) / 2 + (m - k) : m * 4 - m * (m - 1) / 2 + (k - m); }
+
+__device__ inline cplx p2_cmul(cplx a, cplx b) { return cplx{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+
+// gg[p2_sym(i, j)] = |det J| grad l_i . grad l_j of the tetrahedron X with corner a0 moved by d along coordinate CRD; returns |det J|
+template <int CRD> __device__ inline double p2_shape_geometry(const double X[4][3], int a0, double d, double gg[10]) {
+    double Xd[4][3], G[4][3];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Xd[a][k] = (k == CRD && a == a0) ? X[a][k] + d : X[a][k];
+    const double adet = fabs(p2_tet_gradients(Xd, G));
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = i; j < 4; ++j) gg[p2_sym(i, j)] = adet * fma(G[i][2], G[j][2], fma(G[i][1], G[j][1], G[i][0] * G[j][0]));
+    return adet;
+}
+
+// -[w^2 mq (|det J|+ - |det J|-) - sum_ij Ts_ij (gg+ - gg-)_ij] / (2h) for one coordinate
+template <int CRD> __device__ inline cplx p2_shape_tet_term(const double X[4][3], int a0, double h, cplx w2mq, const cplx Ts[10]) {
+    double gp[10], gm[10];
+    const double dp = p2_shape_geometry<CRD>(X, a0, h, gp), dm = p2_shape_geometry<CRD>(X, a0, -h, gm);
+    const double dd = dp - dm;
+    cplx acc = {w2mq.x * dd, w2mq.y * dd};
+#pragma unroll
+    for (int ij = 0; ij < 10; ++ij) {
+        const double g = gp[ij] - gm[ij];
+        acc.x = fma(-Ts[ij].x, g, acc.x);
+        acc.y = fma(-Ts[ij].y, g, acc.y);
+    }
+    const double s = -1.0 / (2.0 * h);
+    return cplx{acc.x * s, acc.y * s};
+}
+
+// one thread per (surface point, tetrahedron) pair: out[3 pr + crd], zero if the point is no corner of the tetrahedron.
+// c: per tetrahedron (NULL = 1) or, NODAL, per mesh point
+template <bool NODAL>
+__global__ __launch_bounds__(256) void p2_shape_tet_kernel(const double *__restrict__ pts, const int *__restrict__ t10, const double *__restrict__ c,
+                                                           int64_t npair, const int *__restrict__ pair_pt, const int *__restrict__ pair_tet, double wr,
+                                                           double wi, const cplx *__restrict__ v, const cplx *__restrict__ vadj, double h,
+                                                           cplx *__restrict__ out) {
+    const int64_t pr = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pr >= npair) return;
+    const int64_t t = pair_tet[pr];
+    const int p = pair_pt[pr];
+    int nd[10];
+#pragma unroll
+    for (int b = 0; b < 10; ++b) nd[b] = t10[t * 10 + b];
+    double X[4][3];
+    int a0 = -1;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        if (nd[a] == p) a0 = a;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) X[a][k] = pts[(size_t)nd[a] * 3 + k];
+    }
+    if (a0 < 0) {
+        out[pr * 3] = out[pr * 3 + 1] = out[pr * 3 + 2] = cplx{0.0, 0.0};
+        return;
+    }
+    double W[10];
+    if (NODAL) {
+        double c4[4], cc[10];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) c4[a] = c[nd[a]];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int m = k; m < 4; ++m) cc[p2_sym(k, m)] = c4[k] * c4[m];
+#pragma unroll
+        for (int km = 0; km < 10; ++km) {
+            double s = cc[0] * dNodalC.quart[km][0];
+#pragma unroll
+            for (int pq = 1; pq < 10; ++pq) s = fma(cc[pq], dNodalC.quart[km][pq], s);
+            W[km] = s;
+        }
+    } else {
+        const double ct = c ? c[t] : 1.0;
+        const double c2 = ct * ct / 120.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int m = k; m < 4; ++m) W[p2_sym(k, m)] = k == m ? 2.0 * c2 : c2;
+    }
+    cplx x[10], yc[10];                                            // yc = conj(v_adj_loc)
+#pragma unroll
+    for (int b = 0; b < 10; ++b) {
+        x[b] = v[nd[b]];
+        const cplx y = vadj[nd[b]];
+        yc[b] = cplx{y.x, -y.y};
+    }
+    cplx mq = {0.0, 0.0};                                          // y^H Mhat x
+#pragma unroll
+    for (int a = 0; a < 10; ++a) {
+        cplx s = {0.0, 0.0};
+#pragma unroll
+        for (int b = 0; b < 10; ++b) {
+            s.x = fma(dTet.mass[a][b], x[b].x, s.x);
+            s.y = fma(dTet.mass[a][b], x[b].y, s.y);
+        }
+        const cplx q = p2_cmul(yc[a], s);
+        mq.x += q.x; mq.y += q.y;
+    }
+    cplx eta[4][4], Z[4][4];                                       // conj(eta_ik);  Z_jk = sum_m W_km xi_jm
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        cplx xi[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            cplx sx = {0.0, 0.0}, sy = {0.0, 0.0};
+#pragma unroll
+            for (int b = 0; b < 10; ++b) {
+                const double d = dTet.d[b][i][k];
+                sx.x = fma(d, x[b].x, sx.x); sx.y = fma(d, x[b].y, sx.y);
+                sy.x = fma(d, yc[b].x, sy.x); sy.y = fma(d, yc[b].y, sy.y);
+            }
+            xi[k] = sx;
+            eta[i][k] = sy;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            cplx s = {0.0, 0.0};
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                s.x = fma(W[p2_sym(k, m)], xi[m].x, s.x);
+                s.y = fma(W[p2_sym(k, m)], xi[m].y, s.y);
+            }
+            Z[i][k] = s;
+        }
+    }
+    cplx Ts[10];                                                   // T_ij + T_ji (i < j), T_ii
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = i; j < 4; ++j) {
+            cplx s = {0.0, 0.0};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const cplx q = p2_cmul(eta[i][k], Z[j][k]);
+                s.x += q.x; s.y += q.y;
+                if (i != j) {
+                    const cplx r = p2_cmul(eta[j][k], Z[i][k]);
+                    s.x += r.x; s.y += r.y;
+                }
+            }
+            Ts[p2_sym(i, j)] = s;
+        }
+    const cplx w2mq = p2_cmul(cplx{wr * wr - wi * wi, 2.0 * wr * wi}, mq);
+    out[pr * 3] = p2_shape_tet_term<0>(X, a0, h, w2mq, Ts);
+    out[pr * 3 + 1] = p2_shape_tet_term<1>(X, a0, h, w2mq, Ts);
+    out[pr * 3 + 2] = p2_shape_tet_term<2>(X, a0, h, w2mq, Ts);
+}
+
+// |(x0-x2) x (x1-x2)| of the triangle X with corner a0 moved by d along coordinate CRD
+template <int CRD> __device__ inline double p2_shape_area2(const double X[3][3], int a0, double d) {
+    double Xd[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Xd[a][k] = (k == CRD && a == a0) ? X[a][k] + d : X[a][k];
+    const double u0 = Xd[0][0] - Xd[2][0], u1 = Xd[0][1] - Xd[2][1], u2 = Xd[0][2] - Xd[2][2];
+    const double w0 = Xd[1][0] - Xd[2][0], w1 = Xd[1][1] - Xd[2][1], w2 = Xd[1][2] - Xd[2][2];
+    const double n0 = u1 * w2 - u2 * w1, n1 = u2 * w0 - u0 * w2, n2 = u0 * w1 - u1 * w0;
+    return sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+}
+
+// admittance boundary, operator term w Y C with C = -i b:  -(w Y)(-i) (y^H Bhat x) (|..|+ - |..|-)/(2h), Bhat = c int phi_a phi_b resp. the
+// nodal table of p2_boundary_cpoint_kernel.  One thread per (surface point, triangle) pair.
+template <bool NODAL>
+__global__ __launch_bounds__(256) void p2_shape_tri_kernel(const double *__restrict__ pts, const int *__restrict__ s6, const double *__restrict__ c,
+                                                           int64_t npair, const int *__restrict__ pair_pt, const int *__restrict__ pair_tri, double wyr,
+                                                           double wyi, const cplx *__restrict__ v, const cplx *__restrict__ vadj, double h,
+                                                           cplx *__restrict__ out) {
+    const int64_t pr = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pr >= npair) return;
+    const int64_t t = pair_tri[pr];
+    const int p = pair_pt[pr];
+    int nd[6];
+#pragma unroll
+    for (int b = 0; b < 6; ++b) nd[b] = s6[t * 6 + b];
+    double X[3][3];
+    int a0 = -1;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (nd[a] == p) a0 = a;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) X[a][k] = pts[(size_t)nd[a] * 3 + k];
+    }
+    if (a0 < 0) {
+        out[pr * 3] = out[pr * 3 + 1] = out[pr * 3 + 2] = cplx{0.0, 0.0};
+        return;
+    }
+    double c0 = 1.0, c1 = 1.0, c2 = 1.0, ct = 1.0;
+    if (NODAL) { c0 = c[nd[0]]; c1 = c[nd[1]]; c2 = c[nd[2]]; }
+    else if (c) ct = c[t];
+    cplx bq = {0.0, 0.0};                                          // y^H Bhat x
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        cplx s = {0.0, 0.0};
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+            const double m = NODAL ? fma(c2, dNodalC.tri[2][a][b], fma(c1, dNodalC.tri[1][a][b], c0 * dNodalC.tri[0][a][b])) : dTri.mass[a][b];
+            const cplx xb = v[nd[b]];
+            s.x = fma(m, xb.x, s.x);
+            s.y = fma(m, xb.y, s.y);
+        }
+        const cplx y = vadj[nd[a]];
+        const cplx q = p2_cmul(cplx{y.x, -y.y}, s);
+        bq.x += q.x; bq.y += q.y;
+    }
+    const double s = ct / (2.0 * h);
+    const double d0 = (p2_shape_area2<0>(X, a0, h) - p2_shape_area2<0>(X, a0, -h)) * s;
+    const double d1 = (p2_shape_area2<1>(X, a0, h) - p2_shape_area2<1>(X, a0, -h)) * s;
+    const double d2 = (p2_shape_area2<2>(X, a0, h) - p2_shape_area2<2>(X, a0, -h)) * s;
+    const cplx f = p2_cmul(cplx{-wyi, wyr}, bq);                   // -(w Y)(-i) (y^H Bhat x)
+    out[pr * 3] = cplx{f.x * d0, f.y * d0};
+    out[pr * 3 + 1] = cplx{f.x * d1, f.y * d1};
+    out[pr * 3 + 2] = cplx{f.x * d2, f.y * d2};
+}
+
+// Flame part (the P2 form of shape_flame_kernel, assemble.hip): per (surface point, flame tetrahedron) pair |det J| with the point moved by
+// +h and -h along every coordinate (det_pm[pair][3][2]), and ssum = sum_a (int phi_a / |det J|) conj(v_adj_a) over the 10 nodes
+template <int CRD> __device__ inline double p2_shape_adet(const double X[4][3], int a0, double d) {
+    double Xd[4][3], G[4][3];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Xd[a][k] = (k == CRD && a == a0) ? X[a][k] + d : X[a][k];
+    return fabs(p2_tet_gradients(Xd, G));
+}
+
+__global__ __launch_bounds__(256) void p2_shape_flame_kernel(const double *__restrict__ pts, const int *__restrict__ t10, int64_t npair,
+                                                             const int *__restrict__ pair_pt, const int *__restrict__ pair_tet,
+                                                             const cplx *__restrict__ vadj, double h, double *__restrict__ det_pm,
+                                                             cplx *__restrict__ ssum) {
+    const int64_t pr = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pr >= npair) return;
+    const int64_t t = pair_tet[pr];
+    const int p = pair_pt[pr];
+    int nd[10];
+#pragma unroll
+    for (int b = 0; b < 10; ++b) nd[b] = t10[t * 10 + b];
+    double X[4][3];
+    int a0 = -1;                                                   // no corner: a0 matches nothing and the six values are the undisplaced |det J|
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        if (nd[a] == p) a0 = a;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) X[a][k] = pts[(size_t)nd[a] * 3 + k];
+    }
+    cplx sa = {0.0, 0.0};
+#pragma unroll
+    for (int b = 0; b < 10; ++b) {
+        const cplx y = vadj[nd[b]];
+        sa.x = fma(dTet.src[b], y.x, sa.x);
+        sa.y = fma(-dTet.src[b], y.y, sa.y);
+    }
+    ssum[pr] = sa;
+    double *o = det_pm + pr * 6;
+    o[0] = p2_shape_adet<0>(X, a0, h); o[1] = p2_shape_adet<0>(X, a0, -h);
+    o[2] = p2_shape_adet<1>(X, a0, h); o[3] = p2_shape_adet<1>(X, a0, -h);
+    o[4] = p2_shape_adet<2>(X, a0, h); o[5] = p2_shape_adet<2>(X, a0, -h);
+}
+
+// sum_b (grad phi_b(x_ref) . n_ref) v_b on the 10 nodes of the reference tetrahedron with corner a0 moved by d along CRD (a0 < 0: as it
+// is).  x_ref stays where it is, so its barycentric coordinates move with the tetrahedron:
+//     grad phi_b(x_ref) = sum_k lam_k sum_i d[b][i][k] grad l_i,    sum_b (..) v_b = sum_k lam_k sum_i (grad l_i . n_ref) xi_ik
+template <int CRD> __device__ inline cplx p2_shape_ref_value(const double X[4][3], int a0, double d, const double xr[3], const double n[3],
+                                                             const cplx xi[4][4]) {
+    double Xd[4][3], G[4][3], lam[4], gn[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Xd[a][k] = (k == CRD && a == a0) ? X[a][k] + d : X[a][k];
+    p2_tet_gradients(Xd, G);
+    lam[3] = 1.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lam[a] = G[a][0] * (xr[0] - Xd[3][0]) + G[a][1] * (xr[1] - Xd[3][1]) + G[a][2] * (xr[2] - Xd[3][2]);
+        lam[3] -= lam[a];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) gn[i] = G[i][0] * n[0] + G[i][1] * n[1] + G[i][2] * n[2];
+    cplx acc = {0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        cplx s = {0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            s.x = fma(gn[i], xi[i][k].x, s.x);
+            s.y = fma(gn[i], xi[i][k].y, s.y);
+        }
+        acc.x = fma(lam[k], s.x, acc.x);
+        acc.y = fma(lam[k], s.y, acc.y);
+    }
+    return acc;
+}
+
+// thread pr < npair: the six displaced values of the listed corner pair_pt[pr] (g_pm[pr][3][2]); thread npair: the undisplaced value g0
+__global__ __launch_bounds__(64) void p2_shape_ref_kernel(const double *__restrict__ pts, const int *__restrict__ t10, int ref_tet, int64_t npair,
+                                                          const int *__restrict__ pair_pt, double xr0, double xr1, double xr2, double n0, double n1,
+                                                          double n2, const cplx *__restrict__ v, double h, cplx *__restrict__ g_pm,
+                                                          cplx *__restrict__ g0) {
+    const int64_t pr = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (pr > npair) return;
+    const int p = pr < npair ? pair_pt[pr] : -1;
+    int nd[10];
+    cplx x[10];
+#pragma unroll
+    for (int b = 0; b < 10; ++b) {
+        nd[b] = t10[(int64_t)ref_tet * 10 + b];
+        x[b] = v[nd[b]];
+    }
+    double X[4][3];
+    int a0 = -1;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        if (nd[a] == p) a0 = a;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) X[a][k] = pts[(size_t)nd[a] * 3 + k];
+    }
+    cplx xi[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            cplx s = {0.0, 0.0};
+#pragma unroll
+            for (int b = 0; b < 10; ++b) {
+                s.x = fma(dTet.d[b][i][k], x[b].x, s.x);
+                s.y = fma(dTet.d[b][i][k], x[b].y, s.y);
+            }
+            xi[i][k] = s;
+        }
+    const double xr[3] = {xr0, xr1, xr2}, nr[3] = {n0, n1, n2};
+    if (pr == npair) {
+        *g0 = p2_shape_ref_value<0>(X, -1, 0.0, xr, nr, xi);
+        return;
+    }
+    cplx *o = g_pm + pr * 6;
+    o[0] = p2_shape_ref_value<0>(X, a0, h, xr, nr, xi); o[1] = p2_shape_ref_value<0>(X, a0, -h, xr, nr, xi);
+    o[2] = p2_shape_ref_value<1>(X, a0, h, xr, nr, xi); o[3] = p2_shape_ref_value<1>(X, a0, -h, xr, nr, xi);
+    o[4] = p2_shape_ref_value<2>(X, a0, h, xr, nr, xi); o[5] = p2_shape_ref_value<2>(X, a0, -h, xr, nr, xi);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 struct P2Conn {
     int64_t npoints = 0, nedges = 0, ntets = 0, ntris = 0;
@@ -538,6 +895,20 @@ int64_t p2_connect(int64_t npoints, int64_t nt, const int *dtets, int64_t ns, co
     if (hbad[0]) throw WaeError(WAE_ERR_HIP, "edge list: an edge of a tetrahedron was not found");
     if (hbad[1]) throw WaeError(WAE_ERR_INVALID, "a boundary triangle has an edge that is no tetrahedron's edge");
     return ne;
+}
+
+// number of distinct edges, counted on the host (the entries that launch nothing for empty pair lists still check nv)
+int64_t p2_host_edge_count(int64_t npoints, int64_t nt, const int32_t *tets) {
+    std::vector<u64> keys;
+    keys.reserve((size_t)nt * 6);
+    for (int64_t t = 0; t < nt; ++t)
+        for (int i = 0; i < 4; ++i)
+            for (int j = i + 1; j < 4; ++j) {
+                const int u = tets[t * 4 + i], v = tets[t * 4 + j];
+                keys.push_back((u64)std::min(u, v) * (u64)npoints + (u64)std::max(u, v));
+            }
+    std::sort(keys.begin(), keys.end());
+    return (int64_t)(std::unique(keys.begin(), keys.end()) - keys.begin());
 }
 
 // the mesh on the device with its P2 connectivity
@@ -759,6 +1130,136 @@ int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points,
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(m.dim, ne, k0, qv, nullptr);
         return WAE_OK;
+    });
+}
+
+// c_t / c_s: per tetrahedron / triangle (NULL = 1), or, nodal, both the one array per mesh point (required)
+static int p2_shape_sensitivity(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_t, int64_t npair_t,
+                                const int32_t *pair_pt_t, const int32_t *pair_tet, const int32_t *tris, const double *c_s, bool nodal, int64_t npair_s,
+                                const int32_t *pair_pt_s, const int32_t *pair_tri, int64_t ntets, int64_t ntris, const double *omega,
+                                const double *omegaY, int64_t nv, const double *v, const double *v_adj, double h, double *out_t, double *out_s) {
+    return wae_guarded([&]() {
+        if (!(points && v && v_adj && omega && npair_t >= 0 && npair_s >= 0)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        if (!(std::isfinite(h) && h > 0.0)) throw WaeError(WAE_ERR_INVALID, "the step h must be finite and positive");
+        if (npair_t > 0 && !(pair_pt_t && pair_tet && out_t)) throw WaeError(WAE_ERR_INVALID, "bad tetrahedron pair arguments");
+        if (npair_s > 0 && !(tris && pair_pt_s && pair_tri && out_s && omegaY && ntris > 0)) throw WaeError(WAE_ERR_INVALID, "bad triangle pair arguments");
+        const int64_t ns = npair_s > 0 ? ntris : 0;                          // the triangles take part only if a pair names one
+        p2_check_mesh(npoints, ntets, tets, ns, tris);
+        if (npair_t > INT_MAX / 3 || npair_s > INT_MAX / 3) throw WaeError(WAE_ERR_INVALID, "too many pairs: 3*npair must fit a 32-bit count");
+        if (nodal) check_c_point(npoints, c_t);
+        for (int64_t i = 0; i < npair_t; ++i)
+            if (pair_tet[i] < 0 || pair_tet[i] >= ntets || pair_pt_t[i] < 0 || pair_pt_t[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
+        for (int64_t i = 0; i < npair_s; ++i)
+            if (pair_tri[i] < 0 || pair_tri[i] >= ntris || pair_pt_s[i] < 0 || pair_pt_s[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
+        if (npair_t == 0 && npair_s == 0) {                                  // empty lists: nothing is launched, nv is checked against a host count
+            if (nv != npoints + p2_host_edge_count(npoints, ntets, tets)) throw WaeError(WAE_ERR_INVALID, "nv is not npoints + nedges");
+            return (int)WAE_OK;
+        }
+        HIP_CHECK(hipSetDevice(device));
+        P2Mesh m(npoints, points, ntets, tets, ns, tris);
+        if (nv != m.dim) throw WaeError(WAE_ERR_INVALID, "nv is not npoints + nedges");
+        Dev<cplx> dv((size_t)nv), dva((size_t)nv);
+        HIP_CHECK(hipMemcpy(dv.p, v, (size_t)nv * sizeof(cplx), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dva.p, v_adj, (size_t)nv * sizeof(cplx), hipMemcpyHostToDevice));
+        Dev<double> dcp(nodal ? (size_t)npoints : 1);
+        if (nodal) HIP_CHECK(hipMemcpy(dcp.p, c_t, (size_t)npoints * sizeof(double), hipMemcpyHostToDevice));
+        if (npair_t > 0) {
+            Dev<int> dpp((size_t)npair_t), dpt((size_t)npair_t);
+            Dev<double> dc(!nodal && c_t ? (size_t)ntets : 1);
+            Dev<cplx> dout((size_t)npair_t * 3);
+            if (!nodal && c_t) HIP_CHECK(hipMemcpy(dc.p, c_t, (size_t)ntets * sizeof(double), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(dpp.p, pair_pt_t, (size_t)npair_t * sizeof(int), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(dpt.p, pair_tet, (size_t)npair_t * sizeof(int), hipMemcpyHostToDevice));
+            const dim3 grid((unsigned)((npair_t + 255) / 256));
+            if (nodal) hipLaunchKernelGGL(p2_shape_tet_kernel<true>, grid, dim3(256), 0, 0, m.pts.p, m.t10.p, dcp.p, npair_t, dpp.p, dpt.p, omega[0], omega[1],
+                                          dv.p, dva.p, h, dout.p);
+            else hipLaunchKernelGGL(p2_shape_tet_kernel<false>, grid, dim3(256), 0, 0, m.pts.p, m.t10.p, c_t ? dc.p : nullptr, npair_t, dpp.p, dpt.p, omega[0],
+                                    omega[1], dv.p, dva.p, h, dout.p);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpy(out_t, dout.p, (size_t)npair_t * 3 * sizeof(cplx), hipMemcpyDeviceToHost));
+        }
+        if (npair_s > 0) {
+            Dev<int> dpp((size_t)npair_s), dpt((size_t)npair_s);
+            Dev<double> dc(!nodal && c_s ? (size_t)ntris : 1);
+            Dev<cplx> dout((size_t)npair_s * 3);
+            if (!nodal && c_s) HIP_CHECK(hipMemcpy(dc.p, c_s, (size_t)ntris * sizeof(double), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(dpp.p, pair_pt_s, (size_t)npair_s * sizeof(int), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(dpt.p, pair_tri, (size_t)npair_s * sizeof(int), hipMemcpyHostToDevice));
+            const dim3 grid((unsigned)((npair_s + 255) / 256));
+            if (nodal) hipLaunchKernelGGL(p2_shape_tri_kernel<true>, grid, dim3(256), 0, 0, m.pts.p, m.s6.p, dcp.p, npair_s, dpp.p, dpt.p, omegaY[0], omegaY[1],
+                                          dv.p, dva.p, h, dout.p);
+            else hipLaunchKernelGGL(p2_shape_tri_kernel<false>, grid, dim3(256), 0, 0, m.pts.p, m.s6.p, c_s ? dc.p : nullptr, npair_s, dpp.p, dpt.p, omegaY[0],
+                                    omegaY[1], dv.p, dva.p, h, dout.p);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpy(out_s, dout.p, (size_t)npair_s * 3 * sizeof(cplx), hipMemcpyDeviceToHost));
+        }
+        return (int)WAE_OK;
+    });
+}
+
+int wae_p2_shape_sensitivity(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_tet, int64_t npair_t,
+                             const int32_t *pair_pt_t, const int32_t *pair_tet, const int32_t *tris, const double *c_tri, int64_t npair_s,
+                             const int32_t *pair_pt_s, const int32_t *pair_tri, int64_t ntets, int64_t ntris, const double *omega,
+                             const double *omegaY, int64_t nv, const double *v, const double *v_adj, double h, double *out_t, double *out_s) {
+    return p2_shape_sensitivity(device, npoints, points, tets, c_tet, npair_t, pair_pt_t, pair_tet, tris, c_tri, false, npair_s, pair_pt_s, pair_tri, ntets,
+                                ntris, omega, omegaY, nv, v, v_adj, h, out_t, out_s);
+}
+
+int wae_p2_shape_sensitivity_cpoint(int32_t device, int64_t npoints, const double *points, const int32_t *tets, const double *c_point, int64_t npair_t,
+                                    const int32_t *pair_pt_t, const int32_t *pair_tet, const int32_t *tris, int64_t npair_s, const int32_t *pair_pt_s,
+                                    const int32_t *pair_tri, int64_t ntets, int64_t ntris, const double *omega, const double *omegaY, int64_t nv,
+                                    const double *v, const double *v_adj, double h, double *out_t, double *out_s) {
+    return p2_shape_sensitivity(device, npoints, points, tets, c_point, npair_t, pair_pt_t, pair_tet, tris, c_point, true, npair_s, pair_pt_s, pair_tri, ntets,
+                                ntris, omega, omegaY, nv, v, v_adj, h, out_t, out_s);
+}
+
+int wae_p2_shape_sensitivity_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t npair,
+                                   const int32_t *pair_pt, const int32_t *pair_tet, int32_t ref_tet, int64_t npair_r, const int32_t *pair_pt_r,
+                                   const double *x_ref, const double *n_ref, int64_t nv, const double *v, const double *v_adj, double h, double *det_pm,
+                                   double *ssum, double *g_pm, double *g0) {
+    return wae_guarded([&]() {
+        if (!(points && x_ref && n_ref && v && v_adj && g0 && npair >= 0 && npair_r >= 0)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        if (!(std::isfinite(h) && h > 0.0)) throw WaeError(WAE_ERR_INVALID, "the step h must be finite and positive");
+        if (npair > 0 && !(pair_pt && pair_tet && det_pm && ssum)) throw WaeError(WAE_ERR_INVALID, "bad flame pair arguments");
+        if (npair_r > 0 && !(pair_pt_r && g_pm)) throw WaeError(WAE_ERR_INVALID, "bad reference pair arguments");
+        p2_check_mesh(npoints, ntets, tets, 0, nullptr);
+        if (npair > INT_MAX / 6 || npair_r > INT_MAX / 6) throw WaeError(WAE_ERR_INVALID, "too many pairs: 6*npair must fit a 32-bit count");
+        if (ref_tet < 0 || ref_tet >= ntets) throw WaeError(WAE_ERR_INVALID, "reference tetrahedron out of range");
+        for (int64_t i = 0; i < npair; ++i) {
+            if (pair_tet[i] < 0 || pair_tet[i] >= ntets) throw WaeError(WAE_ERR_INVALID, "flame tetrahedron out of range");
+            if (pair_pt[i] < 0 || pair_pt[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
+        }
+        for (int64_t i = 0; i < npair_r; ++i)
+            if (pair_pt_r[i] < 0 || pair_pt_r[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
+        HIP_CHECK(hipSetDevice(device));
+        P2Mesh m(npoints, points, ntets, tets, 0, nullptr);
+        if (nv != m.dim) throw WaeError(WAE_ERR_INVALID, "nv is not npoints + nedges");
+        Dev<cplx> dv((size_t)nv), dva((size_t)nv);
+        HIP_CHECK(hipMemcpy(dv.p, v, (size_t)nv * sizeof(cplx), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dva.p, v_adj, (size_t)nv * sizeof(cplx), hipMemcpyHostToDevice));
+        if (npair > 0) {
+            Dev<int> dpp((size_t)npair), dpt((size_t)npair);
+            Dev<double> ddet((size_t)npair * 6);
+            Dev<cplx> dss((size_t)npair);
+            HIP_CHECK(hipMemcpy(dpp.p, pair_pt, (size_t)npair * sizeof(int), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(dpt.p, pair_tet, (size_t)npair * sizeof(int), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(p2_shape_flame_kernel, dim3((unsigned)((npair + 255) / 256)), dim3(256), 0, 0, m.pts.p, m.t10.p, npair, dpp.p, dpt.p, dva.p, h,
+                               ddet.p, dss.p);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpy(det_pm, ddet.p, (size_t)npair * 6 * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(ssum, dss.p, (size_t)npair * sizeof(cplx), hipMemcpyDeviceToHost));
+        }
+        {
+            Dev<int> dpr((size_t)std::max<int64_t>(npair_r, 1));
+            Dev<cplx> dg((size_t)npair_r * 6 + 1);
+            if (npair_r > 0) HIP_CHECK(hipMemcpy(dpr.p, pair_pt_r, (size_t)npair_r * sizeof(int), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(p2_shape_ref_kernel, dim3((unsigned)((npair_r + 1 + 63) / 64)), dim3(64), 0, 0, m.pts.p, m.t10.p, ref_tet, npair_r, dpr.p,
+                               x_ref[0], x_ref[1], x_ref[2], n_ref[0], n_ref[1], n_ref[2], dv.p, h, dg.p, dg.p + (size_t)npair_r * 6);
+            HIP_CHECK(hipGetLastError());
+            if (npair_r > 0) HIP_CHECK(hipMemcpy(g_pm, dg.p, (size_t)npair_r * 6 * sizeof(cplx), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(g0, dg.p + (size_t)npair_r * 6, sizeof(cplx), hipMemcpyDeviceToHost));
+        }
+        return (int)WAE_OK;
     });
 }
 

@@ -251,9 +251,32 @@ def assemble_p2_source(points, tets, tris, c_tri=None, device=0, c_point=None):
     return _source_column(out)
 
 
+def p2_edge_count(tets):
+    """number of distinct mesh edges = edge DoFs of the P2 space (host side; the device numbers them itself)"""
+    tt = np.asarray(tets, dtype=np.int64).reshape(-1, 4)
+    return len(np.unique(np.sort(np.concatenate([tt[:, [i, j]] for i in range(4) for j in range(i + 1, 4)]), axis=1), axis=0))
+
+
+def _shape_arguments(pts, tt, order, c_tet, c_point, bnd_c, flame, vectors):
+    """the checks of the shape-sensitivity keywords that need no device: element order, the form of the speed of sound, the flame's
+    reference point, the lengths of the vectors.  Returns (c_point checked or None, dimension of the space)."""
+    if order not in ("lin", "quad"):
+        raise ValueError(f"order must be 'lin' or 'quad', not {order!r}")
+    cp = _nodal(c_point, c_tet, pts.shape[0], "c_tet")
+    if cp is not None and bnd_c is not None:
+        raise ValueError("give the speed of sound per point (c_point) or per simplex (bnd_c), not both")
+    if order == "quad" and flame is not None and flame.get("x_ref") is None:
+        raise ValueError("order='quad': the flame needs x_ref, the point of the reference tetrahedron at which the gradients are taken")
+    dim = pts.shape[0] + (p2_edge_count(tt) if order == "quad" else 0)
+    for name, x in vectors:
+        if np.shape(x) != (dim,):
+            raise ValueError(f"{name} has shape {np.shape(x)}, the {'P2' if order == 'quad' else 'P1'} space has {dim} degrees of freedom")
+    return cp, dim
+
+
 def discrete_adjoint_shape_sensitivity(points, tets, c_tet, surface_points, sol, L, bnd_tris=None, bnd_c=None, Y=None, h=1e-9,
-                                       device=0, flame=None, v_ext=None):
-    """sens = discrete_adjoint_shape_sensitivity(...)   (src/shape_sensitivity.jl:16-141, full mesh, P1)
+                                       device=0, flame=None, v_ext=None, order="lin", c_point=None):
+    """sens = discrete_adjoint_shape_sensitivity(...)   (src/shape_sensitivity.jl:16-141, full mesh)
 
     Sensitivity of the eigenvalue ``sol.params[sol.eigval]`` to a displacement of every point in ``surface_points`` along
     x, y, z: -v_adj' (dL/dx) v with v'v = 1 and v_adj' L'(ω) v = 1 (the normalisation uses ``L``, the device-backed
@@ -264,10 +287,17 @@ def discrete_adjoint_shape_sensitivity(points, tets, c_tet, surface_points, sol,
     in the reference the flame domain is re-discretised REDUCED to the tetrahedra at the point, its volume included
     (``nlocal = nglobal_scaled / V_reduced``, Helmholtz.jl:325 on the reduced mesh of shape_sensitivity.jl:62-80).
     ``v_ext`` = (v, v_adj) already normalised and given on ``points`` (the unit-cell route extends the sector vectors to the
-    image points and passes them here).  Returns a complex array (3, len(surface_points))."""
+    image points and passes them here).
+    ``order``: "lin" (P1) or "quad" (P2: the vectors have npoints + nedges entries in the numbering of ``p2_connectivity``, only the
+    corner points of the straight-sided elements move, and ``flame`` needs ``x_ref``).  ``c_point`` (npoints,): the speed of sound per
+    mesh point, linear on every simplex, instead of ``c_tet`` and ``bnd_c`` (the *_cpoint entries; the values stay with their points).
+    Returns a complex array (3, len(surface_points))."""
     pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
     tt = np.ascontiguousarray(tets, dtype=np.int32).reshape(-1, 4)
-    cc = None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
+    cp, dim = _shape_arguments(pts, tt, order, c_tet, c_point, bnd_c, flame,
+                               [("v", v_ext[0]), ("v_adj", v_ext[1])] if v_ext is not None else [("sol.v", sol.v), ("sol.v_adj", sol.v_adj)])
+    quad = order == "quad"
+    cc = cp if cp is not None else None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
     sp_ = np.asarray(surface_points, dtype=np.int64)
     w0 = complex(sol.params[sol.eigval])
     if v_ext is not None:
@@ -308,27 +338,37 @@ def discrete_adjoint_shape_sensitivity(points, tets, c_tet, surface_points, sol,
     om = np.array([w0.real, w0.imag])
     wy = complex(w0 * (Y if Y is not None else 0.0))
     omy = np.array([wy.real, wy.imag])
-    bc = np.ascontiguousarray(bnd_c, dtype=np.float64) if npair_s else None
+    bc = np.ascontiguousarray(bnd_c, dtype=np.float64) if npair_s and bnd_c is not None else None
 
     def P(a, t):
         return None if a is None else a.ctypes.data_as(t)
-    _lib.check(_lib.lib().wae_p1_shape_sensitivity(
-        int(device), pts.shape[0], P(pts, dp), P(tt, ip), P(cc, dp), len(pair_tet), P(pair_pt_t, ip), P(pair_tet, ip),
-        P(tri, ip) if npair_s else None, P(bc, dp), npair_s, P(pair_pt_s, ip) if npair_s else None, P(pair_tri, ip) if npair_s else None,
-        tt.shape[0], 0 if tri is None else tri.shape[0], P(om, dp), P(omy, dp),
-        v.view(np.float64).ctypes.data_as(dp), va.view(np.float64).ctypes.data_as(dp), float(h),
-        out_t.view(np.float64).ctypes.data_as(dp) if len(pair_tet) else None, out_s.view(np.float64).ctypes.data_as(dp) if npair_s else None))
+    lib = _lib.lib()
+    entry = {(False, False): lib.wae_p1_shape_sensitivity, (False, True): lib.wae_p1_shape_sensitivity_cpoint,
+             (True, False): lib.wae_p2_shape_sensitivity, (True, True): lib.wae_p2_shape_sensitivity_cpoint}[quad, cp is not None]
+    args = [int(device), pts.shape[0], P(pts, dp), P(tt, ip), P(cc, dp), len(pair_tet), P(pair_pt_t, ip), P(pair_tet, ip),
+            P(tri, ip) if npair_s else None]
+    if cp is None:
+        args.append(P(bc, dp))
+    args += [npair_s, P(pair_pt_s, ip) if npair_s else None, P(pair_tri, ip) if npair_s else None,
+             tt.shape[0], 0 if tri is None else tri.shape[0], P(om, dp), P(omy, dp)]
+    if quad:
+        args.append(dim)
+    args += [v.view(np.float64).ctypes.data_as(dp), va.view(np.float64).ctypes.data_as(dp), float(h),
+             out_t.view(np.float64).ctypes.data_as(dp) if len(pair_tet) else None, out_s.view(np.float64).ctypes.data_as(dp) if npair_s else None]
+    _lib.check(entry(*args))
     sens = np.zeros((3, len(sp_)), dtype=np.complex128)
     np.add.at(sens.T, own_t, out_t)                                   # per point, in pair order: deterministic
     if npair_s:
         np.add.at(sens.T, own_s, out_s)
     if flame is not None:
-        sens += _flame_shape_part(pts, tt, sp_, lut, v, va, w0, L, flame, h, device)
+        sens += _flame_shape_part(pts, tt, sp_, lut, v, va, w0, L, flame, h, device, order)
     return sens
 
 
-def _flame_shape_part(pts, tt, sp_, lut, v, va, w0, L, flame, h, device):
-    """-v_adj' n e^{-iωτ} (Q₊ - Q₋)/(2h) v per surface point and coordinate (wae_p1_shape_sensitivity_flame + the per-point sums)."""
+def _flame_shape_part(pts, tt, sp_, lut, v, va, w0, L, flame, h, device, order="lin"):
+    """-v_adj' n e^{-iωτ} (Q₊ - Q₋)/(2h) v per surface point and coordinate (wae_p1_shape_sensitivity_flame resp. wae_p2_shape_sensitivity_flame
+    + the per-point sums).  The two orders differ in the entry and in the weights of S only: P1 S_a = |det J|/24 with ssum the plain sum of
+    conj(v_adj), P2 S_a = |det J|·∫φ_a with the weights already inside ssum."""
     fl = np.asarray(flame["flame_tets"], dtype=np.int64)
     ref = int(flame["ref_tet"])
     nr = np.ascontiguousarray(flame["n_ref"], dtype=np.float64)
@@ -359,14 +399,21 @@ def _flame_shape_part(pts, tt, sp_, lut, v, va, w0, L, flame, h, device):
 
     def P(a, t):
         return a.ctypes.data_as(t) if a.size else None
-    _lib.check(_lib.lib().wae_p1_shape_sensitivity_flame(
-        int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), npair, P(pair_pt, ip), P(pair_tet, ip), ref, npr,
-        P(pair_pt_r, ip), nr.ctypes.data_as(dp), v.view(np.float64).ctypes.data_as(dp), va.view(np.float64).ctypes.data_as(dp), float(h),
-        P(det_pm, dp), P(ssum.view(np.float64), dp), P(g_pm.view(np.float64), dp), g0.view(np.float64).ctypes.data_as(dp)))
+    outs = (P(det_pm, dp), P(ssum.view(np.float64), dp), P(g_pm.view(np.float64), dp), g0.view(np.float64).ctypes.data_as(dp))
+    vecs = (v.view(np.float64).ctypes.data_as(dp), va.view(np.float64).ctypes.data_as(dp), float(h))
+    mesh = (int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), npair, P(pair_pt, ip), P(pair_tet, ip), ref, npr,
+            P(pair_pt_r, ip))
+    if order == "quad":
+        xr = np.ascontiguousarray(flame["x_ref"], dtype=np.float64)
+        assert xr.shape == (3,)
+        _lib.check(_lib.lib().wae_p2_shape_sensitivity_flame(*mesh, xr.ctypes.data_as(dp), nr.ctypes.data_as(dp), len(v), *vecs, *outs))
+    else:
+        _lib.check(_lib.lib().wae_p1_shape_sensitivity_flame(*mesh, nr.ctypes.data_as(dp), *vecs, *outs))
     ns = len(sp_)
     a_pm = np.zeros((ns, 3, 2), dtype=np.complex128)                  # v_adj' S± per point and coordinate
     V_pm = np.zeros((ns, 3, 2))                                       # volume of the point's flame tetrahedra
-    np.add.at(a_pm, own, det_pm / 24.0 * ssum[:, None, None])
+    S_pm = det_pm if order == "quad" else det_pm / 24.0               # |det J| times the weight that ssum does not carry
+    np.add.at(a_pm, own, S_pm * ssum[:, None, None])
     np.add.at(V_pm, own, det_pm / 6.0)
     b_pm = np.full((ns, 3, 2), g0[0], dtype=np.complex128)            # sum_b grad(phi_b).n_ref v_b on the reference tetrahedron
     b_pm[own_r] = g_pm

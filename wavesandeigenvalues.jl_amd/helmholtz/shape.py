@@ -19,7 +19,8 @@ import numpy as np
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
-from .assemble import assemble_p1, assemble_p1_flame, discrete_adjoint_shape_sensitivity  # noqa: F401  (re-export)
+from .assemble import (_shape_arguments, assemble_p1, assemble_p1_boundary, assemble_p1_flame, assemble_p2, assemble_p2_boundary, assemble_p2_flame,
+                       discrete_adjoint_shape_sensitivity)  # noqa: F401  (re-export)
 
 
 def boundary_triangles(tets):
@@ -145,7 +146,7 @@ def _boundary_mass(points, tris, c_tri, n):
 
 
 def forward_finite_differences_shape_sensitivity(points, tets, c_tet, surface_points, L, sol, bnd_tris=None, bnd_c=None, h=1e-9,
-                                                 device=0, maxiter=5, order=3, nev=3, flame=None):
+                                                 device=0, maxiter=5, order=3, nev=3, flame=None, c_point=None, solver_order=None):
     """Eigenvalue shift per unit displacement of every point in ``surface_points`` along x, y, z, by re-solving
     (src/shape_sensitivity.jl:238-337, full mesh): the family G = L + (D₊ − D₋), D± the discretisations of the simplices
     touching the point with the point moved by ±h, is solved with ``householder`` from the known eigenvalue and
@@ -153,15 +154,31 @@ def forward_finite_differences_shape_sensitivity(points, tets, c_tet, surface_po
     ``flame`` (dict as for discrete_adjoint_shape_sensitivity): the flame operator "Q" of the tetrahedra at the point is
     re-assembled on the device too (``assemble_p1_flame`` on the reduced flame domain, volume included -- what the reference's
     ``discretize`` of the reduced mesh does).
+    ``order``: "lin" or "quad" selects the element order as in discrete_adjoint_shape_sensitivity, and ``solver_order`` (default 3) is
+    then the order of ``householder``; an integer ``order`` keeps its earlier meaning, the order of ``householder`` on P1 elements.
+    ``c_point`` (npoints,): the speed of sound per mesh point instead of ``c_tet`` and ``bnd_c``.  For "quad" the whole mesh is assembled
+    at ±h (``assemble_p2``, ``assemble_p2_boundary``) so that the edge numbers are the family's -- what does not touch the point cancels
+    bit for bit in D₊ − D₋ -- and the flame is still the flame domain REDUCED to the tetrahedra at the point (``assemble_p2_flame``).
+    With order="quad" or ``c_point`` a re-solve that breaks down (householder's flags below -1) raises RuntimeError instead of yielding a
+    zero; ``nev=1`` runs the device-resident iteration, which the P2 Rijke family needs (the block solves of nev=3 at the eigenvalue stall).
     Returns (3, len(surface_points)) complex.  One device family and one eigen-solve per point and coordinate: a
     cross-check for a handful of points, not a production gradient (that is discrete_adjoint_shape_sensitivity)."""
     from ..nlevp.linopfam import LinearOperatorFamily, Term
     from ..nlevp.local_solvers import householder
+    if isinstance(order, str):
+        element, horder = order, 3 if solver_order is None else solver_order
+    elif isinstance(order, (int, np.integer)) and not isinstance(order, bool):
+        element, horder = "lin", order if solver_order is None else solver_order
+    else:
+        raise ValueError(f"order must be 'lin' or 'quad' (or, as before, the integer order of householder), not {order!r}")
     pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
     tt = np.ascontiguousarray(tets, dtype=np.int32).reshape(-1, 4)
-    cc = np.ones(tt.shape[0]) if c_tet is None else np.asarray(c_tet, dtype=np.float64)
+    cp, _ = _shape_arguments(pts, tt, element, c_tet, c_point, bnd_c, flame, [("sol.v", sol.v)])
+    quad = element == "quad"
+    cc = None if cp is not None else np.ones(tt.shape[0]) if c_tet is None else np.asarray(c_tet, dtype=np.float64)
     n = pts.shape[0]
     tri = None if bnd_tris is None else np.asarray(bnd_tris, dtype=np.int64).reshape(-1, 3)
+    bc = None if cp is not None or tri is None else np.ones(len(tri)) if bnd_c is None else np.asarray(bnd_c, dtype=np.float64)
     w0 = complex(sol.params[sol.eigval])
     sens = np.zeros((3, len(surface_points)), dtype=complex)
     for idx, p in enumerate(np.asarray(surface_points, dtype=np.int64)):
@@ -172,13 +189,26 @@ def forward_finite_differences_shape_sensitivity(points, tets, c_tet, surface_po
             for sgn in (+1, -1):
                 ph = pts.copy()
                 ph[p, crd] += sgn * h
-                M, K = assemble_p1(ph, tt[tsel], cc[tsel], device=device)
+                if quad:
+                    M, K = assemble_p2(ph, tt, cc, device=device, c_point=cp)
+                elif cp is not None:
+                    M, K = assemble_p1(ph, tt[tsel], device=device, c_point=cp)
+                else:
+                    M, K = assemble_p1(ph, tt[tsel], cc[tsel], device=device)
                 D[sgn] = {"M": M, "K": K}
                 if len(ssel):
-                    D[sgn]["C"] = _boundary_mass(ph, tri[ssel], np.asarray(bnd_c, dtype=np.float64)[ssel], n)
+                    if quad:
+                        D[sgn]["C"] = assemble_p2_boundary(ph, tt, tri, bc, device=device, c_point=cp)
+                    elif cp is not None:
+                        D[sgn]["C"] = assemble_p1_boundary(ph, tri[ssel], device=device, c_point=cp)
+                    else:
+                        D[sgn]["C"] = _boundary_mass(ph, tri[ssel], bc[ssel], n)
                 if flame is not None:
                     fsel = np.intersect1d(np.asarray(flame["flame_tets"], dtype=np.int64), tsel)
-                    if len(fsel):
+                    if len(fsel) and quad:
+                        D[sgn]["Q"], _ = assemble_p2_flame(ph, tt, fsel, flame["ref_tet"], flame["x_ref"], flame["n_ref"], flame["nglobal_scaled"],
+                                                           device=device)
+                    elif len(fsel):
                         D[sgn]["Q"], _ = assemble_p1_flame(ph, tt, fsel, flame["ref_tet"], flame["n_ref"], flame["nglobal_scaled"], device=device)
             G = LinearOperatorFamily([L.eigval, L.auxval], [0.0, complex(np.inf, 0)], device=device)   # shape_sensitivity.jl:311
             for k, val in L.params.items():
@@ -189,7 +219,11 @@ def forward_finite_differences_shape_sensitivity(points, tets, c_tet, surface_po
                     A = sp.csr_matrix(A + D[+1][T.operator] - D[-1][T.operator])
                 G.push(Term(A, T.func, T.params, T.symbol, T.operator))
             G.params[L.eigval] = w0
-            new_sol, _, _ = householder(G, w0, maxiter=maxiter, output=False, nev=nev, order=order)
+            new_sol, _, flag = householder(G, w0, maxiter=maxiter, output=False, nev=nev, order=horder)
+            if flag < -1 and (quad or cp is not None):        # the re-solve broke down (eigs, singular, NaN): no eigenvalue to difference.  (P1 with c per simplex: as before)
+                G._drop_device()
+                raise RuntimeError(f"forward_finite_differences_shape_sensitivity: householder failed with flag {flag} at point {int(p)}, coordinate {crd}; "
+                                   "nev=1 keeps the iteration on the device")
             sens[crd, idx] = (complex(new_sol.params[new_sol.eigval]) - w0) / (2 * h)
             G._drop_device()
     return sens
