@@ -414,6 +414,42 @@ int wae_p2_assemble_boundary(int32_t device, int64_t npoints, const double *poin
 int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t nflame,
                           const int32_t *flame_tets, int32_t ref_tet, const double *x_ref, const double *n_ref, double nglobal_scaled, void **out,
                           double *volume_out);
+/* -- Bloch unit cells with P1 or P2 elements: cell numbering and operator fold on the device ------------------------
+ * `discretize(mesh, dscrp, C; order, b=:b)` on a mesh with a degree of symmetry: blochify (src/Bloch.jl:4-112), the dimension of
+ * Helmholtz.jl:107-113.  The mesh is the EXTENDED unit cell: points < naxis lie on the symmetry axis, points >= nsector are image
+ * points (the rotated copy of the reference boundary), the twin of image point p is p - (nsector - naxis).  Edge DoFs are those of
+ * wae_p2_connectivity (sorted by (smaller point, larger point), DoF of edge e = npoints + e).  The reference computes the twin of a line
+ * by a constant shift, relying on the line order of its mesh generator (annular_meshes.jl:459-489); here the twin is FOUND:
+ *  - image edge: every endpoint is an image or an axis point and at least one is an image point; its twin is the edge with the image
+ *    endpoints shifted by -(nsector - naxis), located by binary search in the sorted edge keys, one thread per edge;
+ *  - axis edge: both endpoints are axis points;
+ *  - cell numbering: points 0..nsector-1 keep their index, an edge that is no image edge gets nsector + (number of non-image edges
+ *    before it) (exclusive scan, hipCUB), image points and image edges get the cell DoF of their twin;
+ *    dim = nsector + nedges - nimage_edges.  Image edges need not be the tail of the list: (axis point, image point) sorts early.
+ * order: 1 (lin: no edges, the point rule alone) or 2 (quad).  wae_bloch_numbering returns a handle, wae_bloch_numbering_info the
+ * sizes (ndof = npoints + nedges), wae_bloch_numbering_get copies out cell_dof[ndof], flags[ndof] (WAE_BLOCH_IMAGE | WAE_BLOCH_AXIS; the
+ * axis bit marks axis points and axis edges) and edges[2*nedges] (any pointer may be NULL), wae_bloch_numbering_free releases it.
+ * WAE_ERR_INVALID, nothing returned: naxis > nsector, nsector > npoints, more image points than nsector - naxis, a point index out of
+ * range, an image edge whose twin is no edge of the mesh (the cell is not periodic; the message counts them), a twin that is an image
+ * edge itself, or a mesh beyond the 32-bit limits of wae_p2_connectivity.
+ *
+ * wae_bloch_fold: a square CSR matrix on the extended numbering (n = ndof rows; rowptr, col, real values v0 and, sharing the
+ * pattern, v1 or NULL -- M and K, or the real and imaginary part of a complex operator) -> its nparts parts of dimension dim.  Entry
+ * (i, j) goes to (cell_dof[i], cell_dof[j]) of the part  base (image bits of i and j equal), plus (only j an image DoF) or minus
+ * (only i); with nparts = 6 the entries with an axis bit on i or j go to the axis / axis-plus / axis-minus parts instead
+ * (Bloch.jl:54-104).  nparts = 3: parts 0..2, the axis bits are ignored.  Duplicates created by the fold are summed by the assembly
+ * pipeline: key (part, row, column), stable radix sort, reduce-by-key in input order -- no atomics, the same bits on every call.
+ * out: nparts handles of the assembly type (wae_p1_info / wae_p1_get / wae_p1_free; v0 comes back as `mass`, v1 as `stiff`); a part
+ * without entries is a valid handle with nnz = 0.  WAE_ERR_INVALID, nothing launched: a malformed CSR, an index outside its range in
+ * col or cell_dof, an unknown flag bit, nparts not 3 or 6, dim outside 1..n, or nparts * dim beyond a 32-bit index. */
+#define WAE_BLOCH_IMAGE 1
+#define WAE_BLOCH_AXIS  2
+int wae_bloch_numbering(int32_t device, int64_t npoints, int64_t ntets, const int32_t *tets, int64_t nsector, int64_t naxis, int32_t order, void **out);
+int wae_bloch_numbering_info(const void *handle, int64_t *ndof, int64_t *dim, int64_t *nedges, int64_t *nimage_edges, int64_t *naxis_edges);
+int wae_bloch_numbering_get(const void *handle, int32_t *cell_dof, int32_t *flags, int32_t *edges);
+int wae_bloch_numbering_free(void *handle);
+int wae_bloch_fold(int32_t device, int64_t n, const int32_t *rowptr, const int32_t *col, const double *v0, const double *v1, const int32_t *cell_dof,
+                   const int32_t *flags, int64_t dim, int32_t nparts, void **out);
 /* -- nodal speed of sound: K and C of the P1 and P2 spaces from one value per mesh point -----------------------------
  * The second form of `C` in `discretize(mesh, dscrp, C; order)` (src/Helmholtz.jl:43,59-74): length(C) == size(mesh.points, 2), the
  * speed of sound interpolated linearly between the vertices, generate_field(mesh, f; order=:lin).  On every simplex

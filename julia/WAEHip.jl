@@ -1582,16 +1582,92 @@ function forced_response(fam::DeviceFamily, rhs::LinearOperatorFamily, ωs::Abst
     return H, X, info[]
 end
 
+# Bloch unit cells with P1 or P2 elements (`discretize(mesh, dscrp, C; order, b=:b)`; blochify, Bloch.jl:4-112): the cell numbering and the fold
+# of an operator into its base / plus / minus (/ axis) parts on the device.  The mesh is the EXTENDED cell: points <= naxis on the symmetry axis,
+# points > nsector image points whose twin is p - (nsector - naxis) (1-based, as in the reference).
+"Cell numbering of an extended unit-cell mesh: per extended DoF (points, then the P2 edges) cell_dof (1-based) and the flags image / axis; edges
+(2 x nedges, 1-based), dim and the counts"
+struct BlochNumbering
+    npoints::Int
+    nsector::Int
+    naxis::Int
+    order::Symbol
+    cell_dof::Vector{Int32}
+    image::BitVector
+    axis::BitVector
+    edges::Matrix{Int32}
+    dim::Int
+    nimage_edges::Int
+    naxis_edges::Int
+end
+
+"nb = bloch_numbering(npoints, tets, nsector; naxis=0, order=:quad, device): number the DoFs of a Bloch unit cell on the device.  An edge whose
+endpoints are all image or axis points (one image point at least) is an image edge and takes the cell DoF of its twin, which is searched in the
+sorted edge list (not computed by a shift: the edge order is that of p2_connectivity, not the reference generator's); the other edges are
+renumbered densely behind the points; dim = nsector + nedges - nimage_edges.  order = :lin: no edges, the point rule alone."
+function bloch_numbering(npoints::Integer, tets::AbstractMatrix{<:Integer}, nsector::Integer; naxis::Integer=0, order::Symbol=:quad, device::Integer=0)
+    order in (:lin, :quad) || throw(ArgumentError("bloch_numbering: order must be :lin or :quad"))
+    t0 = _zero_based(tets); h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:wae_bloch_numbering, libwaehip), Cint, (Int32, Int64, Int64, Ptr{Int32}, Int64, Int64, Int32, Ref{Ptr{Cvoid}}),
+                device, npoints, size(t0, 2), t0, nsector, naxis, order == :quad ? 2 : 1, h))
+    try
+        nd = Ref{Int64}(0); dim = Ref{Int64}(0); ne = Ref{Int64}(0); ni = Ref{Int64}(0); na = Ref{Int64}(0)
+        check(ccall((:wae_bloch_numbering_info, libwaehip), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                    h[], nd, dim, ne, ni, na))
+        cell = zeros(Int32, nd[]); flags = zeros(Int32, nd[]); edges = zeros(Int32, 2, ne[])
+        check(ccall((:wae_bloch_numbering_get, libwaehip), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), h[], cell, flags, edges))
+        return BlochNumbering(npoints, nsector, naxis, order, cell .+ Int32(1), BitVector(flags .& 1 .!= 0), BitVector(flags .& 2 .!= 0),
+                              edges .+ Int32(1), dim[], ni[], na[])
+    finally
+        ccall((:wae_bloch_numbering_free, libwaehip), Cint, (Ptr{Cvoid},), h[])
+    end
+end
+
+"parts = bloch_fold(A, nb; axis=true, device): `blochify` of the square sparse matrix A (extended numbering) by the cell numbering nb -- the tuple
+(base, plus, minus[, axis, axis_plus, axis_minus]) of dimension nb.dim: six parts if axis and nb.naxis > 0, else three.  The real and the imaginary
+part go through the device as two value streams on one pattern; duplicates are summed by the sorted-triplet pipeline (no atomics)."
+function bloch_fold(A::SparseMatrixCSC, nb::BlochNumbering; axis::Bool=true, device::Integer=0)
+    n = length(nb.cell_dof)
+    size(A, 1) == size(A, 2) || throw(ArgumentError("bloch_fold: the matrix must be square"))
+    size(A, 1) == n || throw(ArgumentError("bloch_fold: the numbering has $n DoFs, the matrix $(size(A, 1)) rows"))
+    At = SparseMatrixCSC{ComplexF64,Int32}(sparse(transpose(A)))              # CSC of the transpose = CSR of A
+    rowptr = At.colptr .- Int32(1); col = At.rowval .- Int32(1)
+    vre = Vector{Float64}(real.(At.nzval)); vim = Vector{Float64}(imag.(At.nzval))
+    cell0 = nb.cell_dof .- Int32(1); flags = Int32.(nb.image) .+ Int32(2) .* Int32.(nb.axis)
+    nparts = (axis && nb.naxis > 0) ? 6 : 3
+    hs = fill(Ptr{Cvoid}(C_NULL), nparts)
+    check(ccall((:wae_bloch_fold, libwaehip), Cint,
+                (Int32, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Int64, Int32, Ptr{Ptr{Cvoid}}),
+                device, n, rowptr, col, vre, vim, cell0, flags, nb.dim, nparts, hs))
+    parts = Vector{SparseMatrixCSC{ComplexF64,UInt32}}()
+    taken = 0
+    try
+        for p in 1:nparts
+            taken = p                                                             # _take_p1 releases the handle it is given
+            a, b = _take_p1(hs[p], true)
+            push!(parts, a + 1im * b)
+        end
+    finally
+        for p in taken+1:nparts
+            ccall((:wae_p1_free, libwaehip), Cint, (Ptr{Cvoid},), hs[p])
+        end
+    end
+    return Tuple(parts)
+end
+
 "M, K, C, Q, V_flame = discretize_device(points, tets; order, c, c_tet, bnd_tris, bnd_c, flame): the term matrices of `discretize` assembled on the
 device, order = :lin or :quad (Helmholtz.jl:36-54).  c: the speed of sound as `discretize` takes it (Helmholtz.jl:59-74) -- one value per
 tetrahedron, or one per mesh point (then linear on every simplex, in K and in C; bnd_c is not used); c_tet = the first form alone.
 bnd_tris / bnd_c: admittance-boundary triangles and the speed of sound behind each; flame = (flame_tets, ref_tet, x_ref, n_ref,
 nglobal_scaled).  Terms that were not asked for come back as `nothing`.
 source=true (`discretize(...; source=true)`, Helmholtz.jl:576-577): bnd_tris is a :speaker boundary -- C is its ω·Y·C term as before, and the call
-returns ((M, K, C, Q, V_flame), rhs) with rhs = speaker_source(m; speaker...) on the same triangles, speaker = (adm_sym, adm_val, speak_sym, speak_val)."
+returns ((M, K, C, Q, V_flame), rhs) with rhs = speaker_source(m; speaker...) on the same triangles, speaker = (adm_sym, adm_val, speak_sym, speak_val).
+bloch=(nsector, naxis): the mesh is the extended unit cell of a Bloch computation -- M, K, C, Q come back as tuples of their parts (bloch_fold) and
+the call returns (M, K, C, Q, V_flame, numbering); not together with source=true.  bloch=nothing (the default): the plain matrices."
 function discretize_device(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; order::Symbol=:lin, c=nothing, c_tet=nothing, bnd_tris=nothing,
-                           bnd_c=nothing, flame=nothing, device::Integer=0, source::Bool=false, speaker=(:Y, 1e15, :A, 1.0))
+                           bnd_c=nothing, flame=nothing, device::Integer=0, source::Bool=false, speaker=(:Y, 1e15, :A, 1.0), bloch=nothing)
     order in (:lin, :quad) || error("discretize_device: order must be :lin or :quad")
+    bloch === nothing || !source || throw(ArgumentError("discretize_device: bloch and source=true cannot be combined"))
     quad = order == :quad
     c_point = nothing
     if c !== nothing
@@ -1618,6 +1694,11 @@ function discretize_device(points::Matrix{Float64}, tets::AbstractMatrix{<:Integ
         bnd_tris === nothing && throw(ArgumentError("discretize_device: source=true needs the speaker triangles (bnd_tris)"))
         m = assemble_source(points, bnd_tris; tets=(quad ? tets : nothing), c_tri=bnd_c, c_point=c_point, device=device)
         return (M, K, C, Q, V), speaker_source(m; adm_sym=speaker[1], adm_val=speaker[2], speak_sym=speaker[3], speak_val=speaker[4])
+    end
+    if bloch !== nothing
+        nb = bloch_numbering(size(points, 2), tets, bloch[1]; naxis=bloch[2], order=order, device=device)
+        foldit(A) = A === nothing ? nothing : bloch_fold(A, nb; device=device)
+        return foldit(M), foldit(K), foldit(C), foldit(Q), V, nb
     end
     return M, K, C, Q, V
 end

@@ -21,6 +21,7 @@
 #include <memory>
 #include <vector>
 
+#include "edge_keys.h"
 #include "wae_internal.h"
 
 namespace {
@@ -205,8 +206,7 @@ __host__ __device__ inline void p2_grad_coeffs(const double d[4][4], const doubl
 }
 
 // ---- edge numbering ------------------------------------------------------------------------------------------------------------
-__device__ inline u64 p2_edge_key(int u, int v, u64 np) { return (u64)min(u, v) * np + (u64)max(u, v); }
-
+// (p2_edge_key and p2_find_edge: edge_keys.h)
 __global__ __launch_bounds__(256) void p2_edge_keys_kernel(const int *__restrict__ tets, int64_t nt, u64 np, u64 *__restrict__ keys) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= nt) return;
@@ -214,17 +214,6 @@ __global__ __launch_bounds__(256) void p2_edge_keys_kernel(const int *__restrict
     u64 *k = keys + t * 6;
     k[0] = p2_edge_key(v0, v1, np); k[1] = p2_edge_key(v0, v2, np); k[2] = p2_edge_key(v0, v3, np);
     k[3] = p2_edge_key(v1, v2, np); k[4] = p2_edge_key(v1, v3, np); k[5] = p2_edge_key(v2, v3, np);
-}
-
-// position of the edge (u, v) in the sorted list, or -1
-__device__ inline int p2_find_edge(const u64 *__restrict__ ek, int64_t ne, u64 np, int u, int v) {
-    const u64 key = p2_edge_key(u, v, np);
-    int64_t lo = 0, hi = ne;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ek[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return (lo < ne && ek[lo] == key) ? (int)lo : -1;
 }
 
 // threads 0..nt-1: 10-node connectivity of a tetrahedron; nt..nt+ns-1: 6-node connectivity of a boundary triangle.
@@ -928,6 +917,13 @@ struct P2Mesh {
 };
 
 }  // namespace
+
+// the sorted unique edge keys of a mesh whose tetrahedra are on the device (declared in wae_internal.h: bloch.hip numbers unit cells with them)
+int64_t p2_edge_list(int64_t npoints, int64_t nt, const int *dtets, Dev<unsigned long long> &ek) {
+    Dev<int> t10((size_t)nt * 10), s6(1);
+    return p2_connect(npoints, nt, dtets, 0, nullptr, ek, t10, s6);
+}
+void p2_check_tets(int64_t npoints, int64_t ntets, const int32_t *tets) { p2_check_mesh(npoints, ntets, tets, 0, nullptr); }
 
 extern "C" {
 

@@ -258,6 +258,10 @@ P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k
 // keyed values (key = node * n, ne of them, 0 < ne <= INT_MAX) -> the dense real vector of their sums per node (out: n doubles, host), through
 // triplets_to_csr with the single column 0: the same stable sort and reduce-by-key as the matrices
 void pairs_to_dense(int64_t n, size_t ne, Dev<unsigned long long> &k0, Dev<double> &v, double *out);
+// assemble_p2.hip: argument and range checks of a tetrahedral mesh (WaeError), and its sorted unique edge keys min(u,v) * npoints + max(u,v)
+// on the device (dtets: 4 * nt device ints; ek: room for 6 * nt keys); returns the number of edges
+void p2_check_tets(int64_t npoints, int64_t ntets, const int32_t *tets);
+int64_t p2_edge_list(int64_t npoints, int64_t nt, const int *dtets, Dev<unsigned long long> &ek);
 // the nodal speed of sound of the *_cpoint entries: required, one finite value per mesh point (checked before anything is launched)
 inline void check_c_point(int64_t npoints, const double *c_point) {
     if (!c_point) throw WaeError(WAE_ERR_INVALID, "c_point is required: one speed of sound per mesh point");

@@ -195,3 +195,81 @@ def build_unit_cell(grid=(8, 26, 7), DOS=N_SECTOR, Y=1e15, n=1.0, tau=1e-3):
         "points": pts,
         "info": info,
     }
+
+
+# ---- P2 (second-order) unit cell and ring: the Bloch family with edge DoFs -----------------------------------------------------
+def _assemble_p2_terms(pts, mesh, device):
+    """M, K, C, Q of the P2 space on the device from the mesh description of _assemble (info["mesh"]); the flames are summed"""
+    from .assemble import assemble_p2, assemble_p2_boundary, assemble_p2_flame
+    M, K = assemble_p2(pts, mesh["tets"], mesh["c_tet"], device=device)
+    C = assemble_p2_boundary(pts, mesh["tets"], mesh["outlet_tris"], mesh["outlet_c"], device=device)
+    Q = None
+    for f in mesh["flames"]:
+        Qf, _ = assemble_p2_flame(pts, mesh["tets"], f["flame_tets"], f["ref_tet"], f["x_ref"], f["n_ref"], f["nglobal_scaled"], device=device)
+        Q = Qf if Q is None else Q + Qf
+    Q = sp.csr_matrix(Q)
+    Q.sum_duplicates()
+    Q.sort_indices()
+    return {"M": M, "K": K, "C": C, "Q": Q}
+
+
+def build_unit_cell_p2(grid=(8, 26, 7), DOS=N_SECTOR, Y=1e15, n=1.0, tau=1e-3, device=0):
+    """build_unit_cell with P2 elements: the mesh of the existing builder, M, K, C, Q assembled on the device (assemble_p2*) on the
+    EXTENDED numbering (points, then the edges of p2_connectivity), and the cell numbering of helmholtz.bloch.bloch_numbering
+    attached (``numbering``; ``dim`` = its folded dimension).  helmholtz.bloch.bloch_family folds the terms by it."""
+    from .bloch import bloch_numbering
+    cell = build_unit_cell(grid, DOS, Y, n, tau)
+    pts, mesh = cell["points"], cell["info"]["mesh"]
+    numbering = bloch_numbering(pts.shape[0], mesh["tets"], cell["nsector"], 0, "quad", device)
+    cell["terms_ext"] = _assemble_p2_terms(pts, mesh, device)
+    cell.update(d_ext=numbering.ndof, dim=numbering.dim, numbering=numbering, order="quad")
+    return cell
+
+
+def build_ring_p2(grid=(8, 26, 7), DOS=N_SECTOR, Y=1e15, n=1.0, tau=1e-3, device=0):
+    """The full ring of DOS sectors of ``grid`` = (nθc, nz, nr) with P2 elements -- the comparator of build_unit_cell_p2: build(...,
+    ref_offset="polar") for the mesh, the P2 terms from the device with the DOS flames summed.  ``edges``: the ring's edge list."""
+    from .assemble import p2_connectivity
+    nthc, nz, nr = grid
+    ring = build(grid=(DOS * nthc, nz, nr), Y=Y, n=n, tau=tau, n_sector=DOS, ref_offset="polar")
+    pts, mesh = ring["points"], ring["info"]["mesh"]
+    ring["terms"] = _assemble_p2_terms(pts, mesh, device)
+    ring["edges"] = p2_connectivity(pts.shape[0], mesh["tets"], device=device)[0]
+    ring["d"] = pts.shape[0] + len(ring["edges"])
+    ring["order"] = "quad"
+    return ring
+
+
+def ring_cell_map(grid, DOS, numbering, ring_edges=None):
+    """(ring_cell_dof, ring_sector) of every DoF of the ring of DOS sectors of ``grid`` = (nθc, nz, nr): ring DoF k is DoF
+    ring_cell_dof[k] of the unit cell, in sector ring_sector[k] (helmholtz.bloch.bloch_expand_dofs).  A ring point in θ-plane t belongs
+    to sector t // nθc.  A ring edge inside one sector is that cell's edge; one whose endpoints lie in sectors s and s+1 (mod DOS) is,
+    in the cell of sector s, the edge to the image point -- and if that cell edge is an image edge, the DoF is its twin's, in sector
+    s+1.  ``numbering``: the cell's (bloch_numbering); ``ring_edges`` (nedges, 2): the ring's edge list (None for order "lin")."""
+    nthc, nz, nr = grid
+    ns = nthc * nz * nr
+    if numbering.nsector != ns or numbering.npoints != ns + nz * nr or numbering.naxis != 0:
+        raise ValueError("the numbering does not belong to the unit cell of this grid")
+    p = np.arange(DOS * ns)
+    cell_dof = [numbering.cell_dof[p % ns].astype(np.int64)]
+    sector = [p // ns]
+    if ring_edges is not None and len(ring_edges):
+        e = np.asarray(ring_edges, dtype=np.int64).reshape(-1, 2)
+        su, sv = e[:, 0] // ns, e[:, 1] // ns
+        if not np.all((su == sv) | ((su + 1) % DOS == sv) | ((sv + 1) % DOS == su)):
+            raise ValueError("a ring edge joins sectors that are no neighbours")
+        s = np.where((sv + 1) % DOS == su, sv, su)               # the sector whose cell holds the edge (su == sv: that sector)
+        lu = np.where(su == s, e[:, 0] % ns, ns + e[:, 0] % ns)   # local point of the cell; a point of sector s+1 is an image point
+        lv = np.where(sv == s, e[:, 1] % ns, ns + e[:, 1] % ns)
+        if np.any(np.maximum(lu, lv) >= numbering.npoints):
+            raise ValueError("a ring edge reaches beyond the first plane of the next sector")
+        np_ext = numbering.npoints
+        key = np.minimum(lu, lv) * np_ext + np.maximum(lu, lv)
+        ck = numbering.edges[:, 0].astype(np.int64) * np_ext + numbering.edges[:, 1]
+        pos = np.searchsorted(ck, key)
+        if np.any(pos >= len(ck)) or np.any(ck[np.minimum(pos, len(ck) - 1)] != key):
+            raise ValueError("a ring edge is no edge of the unit cell")
+        ext = np_ext + pos
+        cell_dof.append(numbering.cell_dof[ext].astype(np.int64))
+        sector.append(np.where(numbering.image[ext], (s + 1) % DOS, s))
+    return np.concatenate(cell_dof), np.concatenate(sector)
