@@ -629,6 +629,30 @@ int wae_debug_spmv(wae_family *h, int32_t which, int32_t level, int32_t mode, co
                    const double *B, double *Y, double *B2, int32_t r, int32_t op, double jac_w, const uint8_t *cmask, int32_t flags,
                    int64_t *n_in_q, int64_t *n_out_q);
 
+/* ONE application of the multigrid preconditioner -- the V-cycle the solvers run, on the handle's own workspaces -- started at
+ * multigrid level `level`, so that tests/ can compare the composition (which weight goes to which sweep, the light cycle, the fused
+ * first sweep, the redirected last sweep, the coefficient table of every level, op = T/C on the coarse levels, the masks passed
+ * down the recursion) with a reference of their own.  Needs wae_solver_setup.
+ *   level   0 ... number of levels - 1; the last level is the dense one: the call is then the dense apply alone (wae_debug_spmv
+ *           has no form for that level).
+ *   coeffs  ncoef x T (ncoef = 1: one system; ncoef = r: one coefficient row per column).  The batch and the per-level plane tables are
+ *           built as wae_solve builds them (conjugated for op = C), uploaded, and the dense level is assembled and inverted first.
+ *   B, Y    column-major n_level x r complex, 1 <= r <= the batch width of the set-up (opts[6]): Y = M_level^-1 B.  Level 0 is in the
+ *           caller's row numbering, coarser levels in the hierarchy's own (sizes: wae_debug_spmv; the dense level has as many rows as
+ *           the last restriction).
+ *   flags   bit 0: the light cycle of the projected phase of a contour integral (pre-smoothing weight opts[11], no post-smoothing),
+ *                  for this call only;
+ *           bit 1: the result is delivered through a separate output buffer, as the Krylov steps that let the last post-smoothing
+ *                  sweep write into a basis slot (without a post-smoothing sweep: a copy);
+ *           bit 2 (level 0 only): B is a vector V and Y = M^-1 A V as one Krylov step forms it -- the product that also writes
+ *                  the first sweep, then the cycle without its first sweep.
+ *   cmask   NULL or one byte per 8-column chunk, handed down as the solver hands it down (batches narrower than 8 columns run
+ *           unmasked); the columns of a chunk with byte 0 return what Y held on entry.
+ * No set-up, a level that does not exist, r outside 1..opts[6], ncoef other than 1 or r, an op outside 0..2, an unknown flag, or
+ * flags bit 2 on a level >= 1: WAE_ERR_INVALID with a message, nothing is launched and the handle stays usable. */
+int wae_debug_vcycle(wae_family *h, int32_t level, const double *coeffs, int32_t ncoef, const double *B, double *Y, int32_t r, int32_t op,
+                     int32_t flags, const uint8_t *cmask);
+
 /* The streaming and reduction kernels under the lock-step GMRES, the snapshot basis, the Beyn accumulation, the batched
  * perturbation and the dense coarse level, ONE library launch per call (the dense level: assemble, invert, apply), so that tests/
  * can compare each with a reference of its own.  Needs no family and no solver set-up: the entry uploads the caller's arrays to

@@ -44,14 +44,13 @@ class TermProducts:
         return Y, bound, dg
 
 
-class FamilyProducts:
-    """The same for ANY family: A_k X and |A_k| |X| for every term of ``L`` (host matrices ``t.coeff``), coefficient rows as
-    ``L.coefficients(z)`` gives them (one per term, 0 where the functor skips a term) -- e.g. the 11 terms of a Bloch unit cell
-    (base / seam parts times exp(+-i b 2 pi / DOS), src/Helmholtz.jl:508-513)."""
+class MatrixProducts:
+    """The same for ANY list of term matrices: A_k X and |A_k| |X| for every term, coefficient rows with one entry per term (0 where a
+    term does not take part).  tests/test_gpu_multigrid.py builds it from the coarse-level matrices it recovered from the device."""
 
-    def __init__(self, L, X, op="N"):
+    def __init__(self, mats, X, op="N"):
         self.op = op
-        mats = [t.coeff.tocsr() for t in L.terms]
+        mats = [A.tocsr() for A in mats]
         if op == "C":
             mats = [A.conj().T.tocsr() for A in mats]
         self.AX = [A @ X for A in mats]
@@ -70,6 +69,15 @@ class FamilyProducts:
         bound = sum(self.absAX[k] * np.abs(cj[None, :, k]) for k in nz)
         dg = sum(self.diag[k][:, None] * cj[None, :, k] for k in nz)
         return Y, bound, dg
+
+
+class FamilyProducts(MatrixProducts):
+    """... for the host matrices ``t.coeff`` of a family ``L``, coefficient rows as ``L.coefficients(z)`` gives them (one per term, 0
+    where the functor skips a term) -- e.g. the 11 terms of a Bloch unit cell (base / seam parts times exp(+-i b 2 pi / DOS),
+    src/Helmholtz.jl:508-513)."""
+
+    def __init__(self, L, X, op="N"):
+        super().__init__([t.coeff for t in L.terms], X, op)
 
 
 def scipy_operator_product(L, coeffs, V):
@@ -99,8 +107,9 @@ def _random_block(rng, d, r):
     return _RANDOM[(d, r)]
 
 
-def check_modes(fam, tp, ct, X, rng, what, modes=(0, 1, 2, 3, 4, 5, 6), cmask=None, op=0, jac_w=0.8):
-    """every fused form of the operator product (include/waehip.h wae_debug_spmv) against the scipy term products `tp`"""
+def check_modes(fam, tp, ct, X, rng, what, modes=(0, 1, 2, 3, 4, 5, 6), cmask=None, op=0, jac_w=0.8, level=0, no_tiles=False):
+    """every fused form of the operator product (include/waehip.h wae_debug_spmv) against the scipy term products `tp`; level >= 1: the
+    operator of that multigrid level (`tp` from its matrices, X in its numbering)"""
     want, bound, dg = tp.apply(ct)
     d, r = X.shape
     B0, Y0 = _random_block(rng, d, r)                                # Y0: what a masked chunk must keep
@@ -111,7 +120,8 @@ def check_modes(fam, tp, ct, X, rng, what, modes=(0, 1, 2, 3, 4, 5, 6), cmask=No
     on, off = np.nonzero(act)[0], np.nonzero(~act)[0]
     adg = np.abs(dg)
     for mode in modes:
-        out = fam.debug_spmv(ct, X, mode=mode, B=None if mode in (0, 4, 6) else B, Y0=Y0, op=op, jac_w=jac_w, cmask=cmask)
+        out = fam.debug_spmv(ct, X, mode=mode, B=None if mode in (0, 4, 6) else B, Y0=Y0, op=op, jac_w=jac_w, cmask=cmask, level=level,
+                             no_tiles=no_tiles)
         Y, B2 = out if mode == 6 else (out, None)
         if mode in (0, 6):
             ref, bnd = want, bound

@@ -2633,6 +2633,68 @@ int wae_debug_spmv(wae_family *h, int32_t which, int32_t level, int32_t mode, co
     });
 }
 
+// ONE application of vcycle() -- the solver's own, not a copy -- from `level` down, on the handle's workspaces (include/waehip.h)
+int wae_debug_vcycle(wae_family *h, int32_t level, const double *coeffs, int32_t ncoef, const double *B, double *Y, int32_t r, int32_t op,
+                     int32_t flags, const uint8_t *cmask) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && coeffs && B && Y, "bad argument");
+        require_solver(h);
+        const int L = (int)h->ops.size() - 1;
+        WAE_REQUIRE(level >= 0 && level <= L, "no such level");
+        WAE_REQUIRE(r >= 1 && r <= h->NB, "r must be in 1..NB (opts[6] of wae_solver_setup)");
+        WAE_REQUIRE(ncoef == 1 || ncoef == r, "ncoef must be 1 or r");
+        WAE_REQUIRE(op >= 0 && op <= 2, "bad op");
+        WAE_REQUIRE(flags >= 0 && flags < 8, "unknown flag");
+        WAE_REQUIRE(!(flags & 4) || level == 0, "flags bit 2 (Y = M^-1 A V) needs level 0");
+        HIP_CHECK(hipSetDevice(h->device));
+        hipStream_t st = h->stream;
+        struct LightRestore { bool &on; bool was; ~LightRestore() { on = was; } } light_restore{h->vc_light, h->vc_light};
+        h->vc_light = (flags & 1) != 0;
+        Batch bt;                                                   // the batch and the plane tables as wae_solve_guess builds them
+        bt.nb = r; bt.op = op;
+        bt.cps = ncoef == 1 ? r : 1;
+        bt.nsys = ncoef == 1 ? 1 : r;
+        std::vector<std::vector<zc>> pcs((size_t)bt.nsys);
+        for (int s = 0; s < bt.nsys; ++s) plane_coeffs(h, coeffs + (size_t)s * 2 * h->T, op, pcs[(size_t)s]);
+        upload_pc(h, pcs);
+        dense_setup(h, bt);
+        const int64_t n = h->ops[level].n;
+        const size_t cnt = (size_t)n * r;
+        const int *perm = level == 0 ? h->perm() : nullptr;       // level 0 is in the caller's row numbering
+        DevBuf<cplx> col, vin, fout;
+        DevBuf<unsigned char> cm;
+        col.alloc(cnt);
+        if (cmask) {
+            cm.alloc((size_t)(r + 7) / 8);
+            HIP_CHECK(hipMemcpyAsync(cm.p, cmask, (size_t)(r + 7) / 8, hipMemcpyHostToDevice, st));
+        }
+        const unsigned char *mk = (cmask && r >= 8) ? cm.p : nullptr;   // (narrower batches run unmasked in the solver)
+        // what a masked chunk holds on return is what every buffer the cycle may return held before it: the caller's Y
+        cplx *x = h->lx[level].p;
+        HIP_CHECK(hipMemcpyAsync(col.p, Y, cnt * sizeof(cplx), hipMemcpyHostToDevice, st));
+        launch_colmajor_to_inter(col.p, n, r, x, r, st, perm);
+        launch_copy(x, h->lt[level].p, cnt, st);
+        if (flags & 2) { fout.alloc(cnt); launch_copy(x, fout.p, cnt, st); }
+        cplx *b = level == 0 ? h->W.p : h->lb[level].p;            // the right-hand side where the solver keeps it
+        HIP_CHECK(hipMemcpyAsync(col.p, B, cnt * sizeof(cplx), hipMemcpyHostToDevice, st));
+        bool have_x0 = false;
+        if (flags & 4) {                                            // one Krylov step's product and cycle: B is V, b = A V
+            vin.alloc(cnt);
+            launch_colmajor_to_inter(col.p, n, r, vin.p, r, st, perm);
+            have_x0 = L > 0;
+            launch_spmv(h->ops[0].dev(op), pc_level(h, 0), bt.cps, vin.p, b, have_x0 ? x : nullptr, have_x0 ? pre_weight(h) : 0.0, r,
+                        have_x0 ? MODE_AX_J0 : MODE_AX, st, mk);
+        } else {
+            launch_colmajor_to_inter(col.p, n, r, b, r, st, perm);
+        }
+        const cplx *res = vcycle(h, bt, level, b, mk, have_x0, (flags & 2) ? fout.p : nullptr);
+        launch_inter_to_colmajor(res, r, n, r, col.p, st, perm);
+        HIP_CHECK(hipMemcpyAsync(Y, col.p, cnt * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return WAE_OK;
+    });
+}
+
 int wae_bench_spmv_level(wae_family *h, const double *coeffs, int32_t which, int32_t level, int32_t r, int32_t reps, double *ms_out,
                          int64_t *bytes_out) {
     return guarded([&]() {

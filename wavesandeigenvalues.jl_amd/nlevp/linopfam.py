@@ -489,6 +489,21 @@ class DeviceFamily:
                 lv += 1
         return out
 
+    def debug_vcycle(self, coeffs, B, level=0, Y0=None, op=OP_N, light=False, final_out=False, fused=False, cmask=None):
+        """wae_debug_vcycle (test hook): ONE application of the solver's V-cycle started at ``level`` (the last level: the dense apply
+        alone), Y = M_level^-1 B; ``fused``: B is V and Y = M^-1 A V as a Krylov step forms it.  A masked chunk returns ``Y0``."""
+        c = np.ascontiguousarray(coeffs, dtype=np.complex128).reshape(-1, self.T)
+        B = np.asarray(B, dtype=np.complex128)
+        Bf = np.asfortranarray(B if B.ndim == 2 else B.reshape(-1, 1))
+        n, r = Bf.shape
+        if level == 0 and n != self.d:                 # (coarser levels: the caller takes the row count from level_sizes())
+            raise ValueError(f"debug_vcycle: B has {n} rows, the family {self.d}")
+        Y = np.zeros((n, r), dtype=np.complex128, order="F") if Y0 is None else np.asfortranarray(np.array(Y0, dtype=np.complex128).reshape(n, r))
+        cm = None if cmask is None else (C.c_uint8 * ((r + 7) // 8))(*[1 if x else 0 for x in cmask])
+        flags = (1 if light else 0) | (2 if final_out else 0) | (4 if fused else 0)
+        check(_lib.lib().wae_debug_vcycle(self.handle, level, zptr(c), c.shape[0], zptr(Bf), zptr(Y), r, op, flags, cm))
+        return Y
+
     def bench_spmv_level(self, coeffs, which=0, level=1, r=64, reps=20):
         """(ms per launch, algorithmic bytes per launch) of a level operator / restriction of the hierarchy"""
         c = np.ascontiguousarray(coeffs, dtype=np.complex128)
