@@ -107,6 +107,10 @@ int wae_spmv_sum_multi(wae_family *h, const double *coeffs, const double *X, dou
  *   level is inverted dense by one workgroup per system and may have at most 2048 unknowns: WAE_ERR_INVALID beyond),
  *   [2] Jacobi weight (0.8), [3] pre/post sweeps (1), [4] GMRES restart (30), [5] penalty-row ratio (1e8),
  *   [6] batch width (columns solved in lock-step, 64).
+ *       Recurrence length: the Krylov basis holds opts[4] + 1 vectors of opts[6] columns, and a request of r columns runs in chunks of
+ *       opts[6], opts[6], ..., remainder.  A chunk of nb columns restarts after m = min(150, floor((opts[4] + 1) * opts[6] / nb) - 1)
+ *       steps: opts[4] for a full chunk, MORE for a chunk narrower than the batch width (16 columns, restart 6: m = 8 for 12 columns, 13
+ *       for 8, 36 for 3).  A deflated guess direction (wae_solve_guess) takes one slot: m - 1.
  *   [7] bit mask (as a double) of terms kept OUT of the shape matrix that the strength graph, the aggregates and the
  *       prolongator smoothing are built from (0).  Bloch families (src/Helmholtz.jl:508-513) pass the seam parts here:
  *       the solution jumps by exp(i b 2pi/N) across the seam, so no aggregate may span it.
@@ -120,12 +124,20 @@ int wae_solver_setup(wae_family *h, const double *coeffs_ref, const double *opts
 
 typedef struct {
     int32_t iters_max;      /* most iterations any column needed            */
-    int32_t iters_total;    /* sum over columns                              */
+    int32_t iters_total;    /* sum over columns (of the steps each column took itself, not of the lock-step iterations) */
     int32_t n_unconverged;  /* columns that stopped at maxit                 */
     int32_t levels;         /* multigrid levels used                         */
-    double  relres_max;     /* max_b ||M^-1(B_b - A X_b)|| / ||M^-1 B_b||: preconditioned (error-like) residual, recomputed */
+    double  relres_max;     /* max_b ||M^-1(B_b - A X_b)|| / ||M^-1 B_b||: preconditioned (error-like) residual.  Recomputed from X,
+                               except after a cycle of at most 12 steps that was accepted on its estimate (below): then the estimate */
     double  seconds;        /* wall time of the device work                  */
 } wae_solve_info;
+/* Stopping rule of every solve (tests/test_gpu_solve_driver.py).  Within a cycle a column stops at the first step whose residual ESTIMATE
+ * (the least-squares residual of the recurrence, relative to ||M^-1 B_b||) is <= 0.7 * tol.  A cycle that ends with every column stopped
+ * after at most 12 steps is accepted on the estimate.  Otherwise the preconditioned residual is recomputed from X at the start of the
+ * next cycle, and a column is done when it is <= tol (so a column can end between 0.7 * tol and tol at a cycle start).  A column whose
+ * estimate gained less than 10 % over 30 steps, with more than 60 steps behind it, ends as stalled (WAE_WARN_STAGNATION if above tol).
+ * A step -- or a pair of steps, where the recurrence takes two per pass over the basis -- is only started if it ends at or before maxit:
+ * no column takes more than maxit steps.  A column with a zero right-hand side takes no step and is returned as zeros. */
 
 /* -- X = op(sum_k c_k A_k)^{-1} B -------------------------------------------------------------------
  * Replaces sparse `\` / `lu` + solve (UMFPACK): beyn.jl:65,257; iterative_solvers.jl:307,397-398,570-572;
