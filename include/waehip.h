@@ -426,6 +426,49 @@ int wae_p2_assemble_boundary(int32_t device, int64_t npoints, const double *poin
 int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t nflame,
                           const int32_t *flame_tets, int32_t ref_tet, const double *x_ref, const double *n_ref, double nglobal_scaled, void **out,
                           double *volume_out);
+/* -- uniform mesh refinement on the device: `octosplit(mesh)` with the nested P1 prolongation ---------------------------
+ * Every tetrahedron is split into 8 and every boundary triangle into 4 (src/Meshutils.jl:589-747); the handle keeps `levels`
+ * successive refinements in HBM, level 0 being the input.  points: 3 doubles per point, tets: 4 point indices (0-based) per
+ * tetrahedron, tris: 3 per boundary triangle (ntris may be 0, tris NULL).  One level, index for index what the reference returns:
+ *  - points (Meshutils.jl:596-601): the old points keep their numbers, the midpoint of edge e is point npoints + e = (x_a + x_b) * 0.5;
+ *    the unique tetrahedron edges are ordered as mesh.lines (collect_lines!, Meshutils.jl:831-840, with src/Mesh/sorter.jl:9-31):
+ *    ascending by (larger point, smaller point) -- NOT the (smaller, larger) order of wae_p2_connectivity.
+ *  - children of a tetrahedron (A,B,C,D) (Meshutils.jl:604-641): the corners [A,AB,AC,AD] [B,AB,BC,BD] [C,AC,BC,CD] [D,AD,BD,CD], then the
+ *    inner octahedron cut along the shortest of its diagonals AB-CD, AC-BD, AD-BC, the <= tie-breaks tested in that order:
+ *        AB-CD: [AB,CD,AC,AD] [AB,CD,AD,BD] [AB,CD,BD,BC] [AB,CD,BC,AC]
+ *        AC-BD: [AC,BD,AB,AD] [AC,BD,AD,CD] [AC,BD,CD,BC] [AC,BD,BC,AB]
+ *        AD-BC: [AD,BC,AC,CD] [AD,BC,CD,BD] [AD,BC,BD,AB] [AD,BC,AB,AC]
+ *    The vertex order of a child is kept as listed, so the orientation is mixed as in the reference (every assembly here takes |det J|).
+ *    The diagonals are compared by d2 = (dx*dx + dy*dy) + dz*dz of the stored midpoints in double, every operation rounded on its own,
+ *    so that a host restatement gets the same children.  The reference compares LinearAlgebra.norm, whose rounding is not specified: on
+ *    tetrahedra whose two shortest diagonals are equal or within a rounding (85 of the 3380 of the tutorial Rijke tube) the package may cut
+ *    along another diagonal.
+ *  - children of a triangle (A,B,C) (Meshutils.jl:645-654): [A,AB,AC] [B,AB,BC] [C,AC,BC] [AB,AC,BC].
+ *  - list order (insert_smplx!, sorter.jl:141-150): ascending by "vertices sorted descending, compared lexicographically", which
+ *    find_smplx (a binary search) and the choice of a flame's reference tetrahedron rely on.  tet_labels[8 t + k] / tri_labels[4 s + k] is the
+ *    position of child k (in the order above) of parent t / s in the new list (Meshutils.jl:670-722, 0-based here).
+ * Edge keys, radix sorts, unique pass and binary searches run on the device (hipCUB), deterministic, no atomics; between two levels only
+ * the edge count and the error flags cross the bus.
+ * wae_octosplit returns a handle (levels >= 1), wae_octosplit_info the sizes of a level, wae_octosplit_get copies a level out:
+ * points[3*npoints], tets[4*ntets], tris[3*ntris], parents[2 per NEW point of this level: (larger, smaller) end of its edge, in the
+ * numbers of level - 1], tet_labels[8 per tetrahedron of level - 1], tri_labels[4 per triangle of level - 1]; any pointer may be NULL,
+ * and the last three must be NULL for level 0.  wae_octosplit_free releases the handle.
+ * wae_octosplit_prolong: the nested P1 embedding from_level < to_level applied level by level to ncols complex columns (X:
+ * npoints(from) x ncols column-major, interleaved re/im; Y: npoints(to) x ncols): the rows of old points are copied, the row of a new
+ * point is (x[a] + x[b]) * 0.5; one kernel per level, the intermediate levels stay in HBM.
+ * WAE_ERR_INVALID, nothing returned and nothing truncated: an index outside 0..npoints-1, a triangle edge that is no tetrahedron's
+ * edge, two equal children after the sort (a simplex listed twice or repeating a point), levels < 1, or a level whose point,
+ * tetrahedron or triangle count passes a 32-bit index.
+ * Out of scope: meshes with a degree of symmetry (the point classes of a Bloch unit cell do not survive appended points; the reference
+ * drops `dos` too), interior-triangle lists (a TODO in the reference, Meshutils.jl:656-668), P2 or Hermite prolongation, and the use of
+ * the hierarchy as a geometric multigrid. */
+int wae_octosplit(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris,
+                  int32_t levels, void **out);
+int wae_octosplit_info(const void *handle, int32_t level, int64_t *npoints, int64_t *ntets, int64_t *ntris);
+int wae_octosplit_get(const void *handle, int32_t level, double *points, int32_t *tets, int32_t *tris, int32_t *parents, int32_t *tet_labels,
+                      int32_t *tri_labels);
+int wae_octosplit_prolong(const void *handle, int32_t from_level, int32_t to_level, int32_t ncols, const double *X, double *Y);
+int wae_octosplit_free(void *handle);
 /* -- Bloch unit cells with P1 or P2 elements: cell numbering and operator fold on the device ------------------------
  * `discretize(mesh, dscrp, C; order, b=:b)` on a mesh with a degree of symmetry: blochify (src/Bloch.jl:4-112), the dimension of
  * Helmholtz.jl:107-113.  The mesh is the EXTENDED unit cell: points < naxis lie on the symmetry axis, points >= nsector are image

@@ -1438,6 +1438,91 @@ function assemble_p1_flame(points::Matrix{Float64}, tets::AbstractMatrix{<:Integ
     return _take_p1(h[], false), vol[]
 end
 
+# Uniform mesh refinement on the device: `octosplit(mesh)` (Meshutils.jl:589-747) and the nested P1 prolongation between its levels
+# (include/waehip.h, wae_octosplit*).  Out of scope, as there: meshes with a degree of symmetry, interior-triangle lists, P2 or Hermite
+# prolongation, the hierarchy as a geometric multigrid.
+"the levels 0..levels of one `octosplit_device` call, kept in HBM (level 0 = the input); `npoints[l + 1]` points on level l"
+mutable struct Refinement
+    handle::Ptr{Cvoid}
+    levels::Int
+    npoints::Vector{Int}
+end
+
+"release the device levels of a Refinement (the finalizer is only the safety net).  Idempotent."
+function free!(ref::Refinement)
+    ref.handle != C_NULL && ccall((:wae_octosplit_free, libwaehip), Cint, (Ptr{Cvoid},), ref.handle)
+    ref.handle = C_NULL
+    return nothing
+end
+
+"new_mesh, ref = octosplit_device(mesh; levels=1, device=0): `levels` applications of `octosplit(mesh)` on the device.  new_mesh is the
+package's `Mesh` of the last level exactly as `octosplit` builds it (Meshutils.jl:724-746): the first points are the old ones, the simplex
+lists are in the package's sorted order, `lines` is empty, the domains are relabelled through the children and `tri2tet` is unlinked.  On
+tetrahedra whose two shortest inner diagonals agree to a rounding the package may cut along the other one (include/waehip.h).  ref keeps
+every level in HBM for `prolong`."
+function octosplit_device(mesh; levels::Integer=1, device::Integer=0)
+    levels >= 1 || throw(ArgumentError("levels must be at least 1"))
+    mesh.dos isa Integer || throw(ArgumentError("octosplit_device: meshes with a degree of symmetry are not supported"))
+    points = Matrix{Float64}(mesh.points)
+    t0 = _zero_based(hcat(mesh.tetrahedra...))
+    s0 = isempty(mesh.triangles) ? zeros(Int32, 3, 0) : _zero_based(hcat(mesh.triangles...))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:wae_octosplit, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Int32, Ref{Ptr{Cvoid}}),
+                device, size(points, 2), points, size(t0, 2), t0, size(s0, 2), size(s0, 2) == 0 ? C_NULL : s0, levels, h))
+    ref = Refinement(h[], levels, Int[])
+    finalizer(free!, ref)
+    np = Ref{Int64}(0); nt = Ref{Int64}(0); ns = Ref{Int64}(0)
+    counts = Tuple{Int,Int,Int}[]
+    for l in 0:levels
+        check(ccall((:wae_octosplit_info, libwaehip), Cint, (Ptr{Cvoid}, Int32, Ref{Int64}, Ref{Int64}, Ref{Int64}), ref.handle, l, np, nt, ns))
+        push!(counts, (Int(np[]), Int(nt[]), Int(ns[])))
+        push!(ref.npoints, Int(np[]))
+    end
+    # reassemble the domains level by level (Meshutils.jl:724-740): the sorted children of their simplices
+    domains = Dict()
+    for (dom, domain) in mesh.domains
+        domains[dom] = Dict()
+        domains[dom]["dimension"] = domain["dimension"]
+        domains[dom]["simplices"] = collect(Int, domain["simplices"])
+    end
+    for l in 1:levels
+        tl = zeros(Int32, 8, counts[l][2]); sl = zeros(Int32, 4, counts[l][3])
+        check(ccall((:wae_octosplit_get, libwaehip), Cint,
+                    (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                    ref.handle, l, C_NULL, C_NULL, C_NULL, C_NULL, tl, sl))
+        for domain in values(domains)
+            dim = domain["dimension"]
+            domain["simplices"] = dim == 3 ? sort(Int.(vec(tl[:, domain["simplices"]])) .+ 1) :
+                                  dim == 2 ? sort(Int.(vec(sl[:, domain["simplices"]])) .+ 1) : Int[]
+        end
+    end
+    n, ntet, ntri = counts[end]
+    pts = zeros(Float64, 3, n); tets = zeros(Int32, 4, ntet); tris = zeros(Int32, 3, ntri)
+    check(ccall((:wae_octosplit_get, libwaehip), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                ref.handle, levels, pts, tets, tris, C_NULL, C_NULL, C_NULL))
+    tetrahedra = Array{UInt32}[UInt32.(tets[:, i]) .+ UInt32(1) for i in 1:ntet]
+    triangles = Array{UInt32}[UInt32.(tris[:, i]) .+ UInt32(1) for i in 1:ntri]
+    tri2tet = zeros(UInt32, ntri)
+    ntri > 0 && (tri2tet[1] = 0xffffffff)          # the package's sentinel of an unlinked list (Meshutils.jl:742-745)
+    new_mesh = typeof(mesh)(mesh.file, pts, [], triangles, Array{UInt32}[], tetrahedra, domains, mesh.file, tri2tet, 1)
+    return new_mesh, ref
+end
+
+"Y = prolong(ref, X; from=0, to=ref.levels): the nested P1 embedding of level `from` into level `to` on the device -- old points keep their
+value, a new point gets the mean of the two ends of its edge, level by level.  X: a vector or a matrix with one row per point of level
+`from`, real or complex; Y has the shape and the realness of X."
+function prolong(ref::Refinement, X::AbstractVecOrMat{<:Number}; from::Integer=0, to::Integer=ref.levels)
+    0 <= from < to <= ref.levels || throw(ArgumentError("prolong needs 0 <= from < to <= $(ref.levels), got $from and $to"))
+    size(X, 1) == ref.npoints[from + 1] || throw(ArgumentError("X has $(size(X, 1)) rows, level $from has $(ref.npoints[from + 1]) points"))
+    Xc = Matrix{ComplexF64}(reshape(X, size(X, 1), :))
+    Y = zeros(ComplexF64, ref.npoints[to + 1], size(Xc, 2))
+    check(ccall((:wae_octosplit_prolong, libwaehip), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                ref.handle, from, to, size(Xc, 2), Xc, Y))
+    Yr = eltype(X) <: Real ? real.(Y) : Y
+    return X isa AbstractVector ? vec(Yr) : Yr
+end
+
 # P2 (second-order) elements, `discretize(...; order=:quad)`: edge DoFs numbered on the device (aggregate_elements, FEM.jl:84-116) and the
 # three operators on the 10-node tetrahedra / 6-node triangles.  Arguments as for the P1 wrappers (1-based indices in, 1-based out).
 "edges (2 x nedges), tets10 (10 x ntet), tris6 (6 x ntri) = p2_connectivity(npoints, tets[, tris]; device): DoF of edge e = npoints + e, the

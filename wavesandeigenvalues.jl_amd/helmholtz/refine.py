@@ -1,0 +1,187 @@
+"""Uniform mesh refinement on the device (wae_octosplit, include/waehip.h): ``octosplit`` of the reference (src/Meshutils.jl:589-747), every
+tetrahedron split into 8 and every boundary triangle into 4, index for index the reference's lists, with the nested P1 prolongation between
+the levels.  The levels stay in HBM behind one handle; what is carried from a mesh to its refinement by the labels alone (fields per
+simplex, domains, the reference tetrahedron of a flame) is an O(n) gather on the host.
+
+Out of scope: meshes with a degree of symmetry (the point classes of a Bloch unit cell do not survive appended points), interior-triangle
+lists, P2 or Hermite prolongation, and the use of the hierarchy as a geometric multigrid."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib
+from . import probe
+
+_FACE_TOL = 1e-10          # barycentric distance from a face of the parent below which a neighbour's child may contain x_ref as well
+
+
+class RefinedMesh:
+    """The levels 0..levels of one ``octosplit`` call; level 0 is the input.  Per level l: ``points[l]`` (n, 3), ``tets[l]`` (ntets, 4),
+    ``tris[l]`` (ntris, 3); for l >= 1 also ``parents[l]`` (one (larger, smaller) pair of level-(l-1) points per new point),
+    ``tet_labels[l]`` (ntets of l-1, 8) and ``tri_labels[l]`` (ntris of l-1, 4): the positions of every parent's children in the lists of
+    level l (entry 0 of the three is None).  Everything is 0-based.  The device handle is freed with the object; without one (handle
+    None: the arrays alone) everything but ``prolong`` works."""
+
+    def __init__(self, handle, device, points, tets, tris, parents, tet_labels, tri_labels):
+        self._h, self.device, self.levels = handle, int(device), len(points) - 1
+        self.points, self.tets, self.tris = list(points), list(tets), list(tris)
+        self.parents, self.tet_labels, self.tri_labels = list(parents), list(tet_labels), list(tri_labels)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _lib.lib().wae_octosplit_free(h)
+
+    def _level(self, l, what="level"):
+        l = int(l)
+        if l < 0:
+            l += self.levels + 1
+        if not 0 <= l <= self.levels:
+            raise ValueError(f"{what} outside 0..{self.levels}")
+        return l
+
+    def prolong(self, X, from_level=0, to_level=-1):
+        """The nested P1 embedding of level ``from_level`` into ``to_level`` (wae_octosplit_prolong): old points keep their value, a new
+        point gets the mean of the two ends of its edge, level by level on the device.  X: (npoints(from),) or (npoints(from), ncols), real
+        or complex; the result has the same number of dimensions and is complex exactly if X is."""
+        f, t = self._level(from_level, "from_level"), self._level(to_level, "to_level")
+        if f >= t:
+            raise ValueError(f"prolongation needs from_level < to_level, got {f} and {t}")
+        X = np.asarray(X)
+        if X.ndim not in (1, 2) or X.shape[0] != len(self.points[f]) or X.size == 0:
+            raise ValueError(f"X has shape {X.shape}, level {f} has {len(self.points[f])} points")
+        if not (np.issubdtype(X.dtype, np.floating) or np.issubdtype(X.dtype, np.complexfloating) or np.issubdtype(X.dtype, np.integer)):
+            raise ValueError(f"X must be real or complex, got {X.dtype}")
+        if not self._h:
+            raise ValueError("this RefinedMesh holds no device handle")
+        real = not np.iscomplexobj(X)
+        ncols = 1 if X.ndim == 1 else X.shape[1]
+        Xf = np.asfortranarray(X.reshape(X.shape[0], ncols), dtype=np.complex128)
+        Y = np.zeros((len(self.points[t]), ncols), dtype=np.complex128, order="F")
+        _lib.check(_lib.lib().wae_octosplit_prolong(self._h, f, t, ncols, _zptr_f(Xf), _zptr_f(Y)))
+        Y = Y.real.copy() if real else Y
+        return Y[:, 0] if X.ndim == 1 else Y
+
+    # ---- host-side carriers: O(n) gathers through the labels ---------------------------------------------------------------------
+    def _carry(self, values, labels, count, to_level, what):
+        t = self._level(to_level, "to_level")
+        v = np.asarray(values)
+        if v.shape[:1] != (count,):
+            raise ValueError(f"{what}: {v.shape[0] if v.ndim else 'a scalar'} values for the {count} simplices of level 0")
+        for l in range(1, t + 1):
+            out = np.empty((labels[l].size,) + v.shape[1:], dtype=v.dtype)
+            out[labels[l].ravel()] = np.repeat(v, labels[l].shape[1], axis=0)
+            v = out
+        return v
+
+    def tet_field(self, c_tet, to_level=-1):
+        """a value per tetrahedron of level 0 (e.g. the speed of sound) on the tetrahedra of ``to_level``: children inherit the parent's"""
+        return self._carry(c_tet, self.tet_labels, len(self.tets[0]), to_level, "tet_field")
+
+    def tri_field(self, c_tri, to_level=-1):
+        """the same for a value per boundary triangle of level 0"""
+        return self._carry(c_tri, self.tri_labels, len(self.tris[0]), to_level, "tri_field")
+
+    def _domain(self, idx, labels, count, to_level, what):
+        t = self._level(to_level, "to_level")
+        d = np.asarray(idx, dtype=np.int64).ravel()
+        if d.size and (d.min() < 0 or d.max() >= count):
+            raise ValueError(f"{what}: an index outside the {count} simplices of level 0")
+        for l in range(1, t + 1):
+            d = np.sort(labels[l][d].ravel().astype(np.int64))
+        return d.astype(np.int32)
+
+    def tet_domain(self, idx, to_level=-1):
+        """the simplices of a 3-D domain of level 0 (indices into tets[0]) on ``to_level``: the sorted list of all their children
+        (Meshutils.jl:724-740)"""
+        return self._domain(idx, self.tet_labels, len(self.tets[0]), to_level, "tet_domain")
+
+    def tri_domain(self, idx, to_level=-1):
+        """the same for a 2-D domain (indices into tris[0])"""
+        return self._domain(idx, self.tri_labels, len(self.tris[0]), to_level, "tri_domain")
+
+    def reference_tet(self, parent_ref, x_ref, to_level=-1):
+        """The reference tetrahedron of a flame on ``to_level``: the first tetrahedron in list order that contains ``x_ref``
+        (find_tetrahedron_containing_point, Meshutils.jl:800-816), given the one of level 0, ``parent_ref``.  Inside the parent that is the
+        first of its descendants that contains the point.  Within 1e-10 (barycentric) of a face of the parent a neighbour's child could
+        come first in the list: then ``probe.find_tetrahedron`` searches the whole level."""
+        t = self._level(to_level, "to_level")
+        ref = int(parent_ref)
+        if not 0 <= ref < len(self.tets[0]):
+            raise ValueError(f"parent_ref outside the {len(self.tets[0])} tetrahedra of level 0")
+        x = np.asarray(x_ref, dtype=np.float64)
+        if x.shape != (3,):
+            raise ValueError(f"a point has 3 coordinates, got shape {x.shape}")
+        lam, _ = probe._barycentric(self.points[0][self.tets[0][ref]], x)
+        if lam.min() < _FACE_TOL:
+            return probe.find_tetrahedron(self.points[t], self.tets[t], x)
+        cand = self.tet_domain([ref], t)
+        for c in cand:                                                    # ascending: list order
+            lam, _ = probe._barycentric(self.points[t][self.tets[t][c]], x)
+            if lam.min() >= 0.0:
+                return int(c)
+        return probe.find_tetrahedron(self.points[t], self.tets[t], x)    # x_ref within a rounding of an inner face
+
+
+def _zptr_f(a):
+    """pointer to the interleaved (re, im) doubles of a column-major complex128 array"""
+    assert a.dtype == np.complex128 and a.flags.f_contiguous
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def octosplit(points, tets, tris=None, levels=1, device=0):
+    """``levels`` uniform refinements of the mesh points (npoints, 3), tets (ntets, 4), tris (ntris, 3) or None, 0-based, on the device
+    (wae_octosplit).  Returns a ``RefinedMesh``.  The library raises ``WaeError`` for an index outside the points, a triangle edge that is
+    no tetrahedron's edge, a simplex listed twice, or a level beyond 32-bit indices."""
+    pts = np.asarray(points, dtype=np.float64)
+    tt = np.asarray(tets)
+    tr = None if tris is None else np.asarray(tris)
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
+        raise ValueError(f"points must have shape (npoints, 3) with npoints > 0, got {pts.shape}")
+    if tt.ndim != 2 or tt.shape[1] != 4 or tt.shape[0] == 0 or not np.issubdtype(tt.dtype, np.integer):
+        raise ValueError(f"tets must be an integer array of shape (ntets, 4) with ntets > 0, got {tt.dtype} {tt.shape}")
+    if tr is not None and tr.size == 0:
+        tr = None
+    if tr is not None and (tr.ndim != 2 or tr.shape[1] != 3 or not np.issubdtype(tr.dtype, np.integer)):
+        raise ValueError(f"tris must be an integer array of shape (ntris, 3), got {tr.dtype} {tr.shape}")
+    for a in (tt, tr):
+        if a is not None and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError("a point index does not fit 32 bits")
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1:
+        raise ValueError(f"levels must be an integer >= 1, got {levels!r}")
+    pts = np.ascontiguousarray(pts)
+    tt = np.ascontiguousarray(tt, dtype=np.int32)
+    tr = None if tr is None else np.ascontiguousarray(tr, dtype=np.int32)
+    L = _lib.lib()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    h = C.c_void_p()
+    _lib.check(L.wae_octosplit(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), 0 if tr is None else tr.shape[0],
+                               None if tr is None else tr.ctypes.data_as(ip), int(levels), C.byref(h)))
+    return _download(L, h, int(levels), device)
+
+
+def _download(L, h, levels, device):
+    """copy every level of the handle out into a RefinedMesh, which owns the handle from here on"""
+    R = RefinedMesh(h, device, [], [], [], [None], [None], [None])
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    for l in range(levels + 1):
+        n, nt, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(L.wae_octosplit_info(h, l, C.byref(n), C.byref(nt), C.byref(ns)))
+        pts = np.zeros((n.value, 3))
+        tt = np.zeros((nt.value, 4), dtype=np.int32)
+        tr = np.zeros((ns.value, 3), dtype=np.int32)
+        par = tl = sl = None
+        if l:
+            par = np.zeros((n.value - len(R.points[-1]), 2), dtype=np.int32)
+            tl = np.zeros((len(R.tets[-1]), 8), dtype=np.int32)
+            sl = np.zeros((len(R.tris[-1]), 4), dtype=np.int32)
+        _lib.check(L.wae_octosplit_get(h, l, pts.ctypes.data_as(dp), tt.ctypes.data_as(ip), tr.ctypes.data_as(ip),
+                                       None if par is None else par.ctypes.data_as(ip), None if tl is None else tl.ctypes.data_as(ip),
+                                       None if sl is None else sl.ctypes.data_as(ip)))
+        R.points.append(pts); R.tets.append(tt); R.tris.append(tr)
+        if l:
+            R.parents.append(par); R.tet_labels.append(tl); R.tri_labels.append(sl)
+    R.levels = levels
+    return R
