@@ -312,7 +312,8 @@ int wae_perturb(wae_family *h, const double *coeff_table, int32_t N, const doubl
  *   wae_slot_axpby   dst[:, dst_cols[i]] = alpha[i] * src[:, src_cols[i]] + beta[i] * dst[:, dst_cols[i]],  i < n, one after the other
  *                    (alpha, beta: n complex numbers; src and dst may be the same slot and column: a scaling; conj_src != 0: the
  *                    conjugate of the source column is used).  The relaxed update of Householder.jl:173-176; with conj_src the left
- *                    start vectors conj(v0) of Householder.jl:84-86 from the right ones.
+ *                    start vectors conj(v0) of Householder.jl:84-86 from the right ones.  beta[i] == 0 overwrites: the destination
+ *                    column is not read (BLAS convention), so what it held -- a NaN included -- does not matter.
  *   wae_slot_forms   out[i] = a_i^H op(sum_k coeffs[i][k] A_k) b_i  for n pairs of columns a_i = slot a[:, a_cols[i]], b_i likewise
  *                    (coeffs: n x T): the normalisations v^H M v and v_adj^H L'(z) v of Householder.jl:189-190 without moving a vector.
  *   wae_arnoldi_shiftinvert_slots   wae_arnoldi_shiftinvert_batch with the start vectors taken from slot columns v0_cols[0..nsys-1] and

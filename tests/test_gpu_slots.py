@@ -243,3 +243,61 @@ def test_single_start_solvers_resident_equal_the_host_memory_forms(annulus):
                 ov = abs(np.vdot(x, y)) / (np.linalg.norm(x) * np.linalg.norm(y))
                 assert ov > 1 - 1e-8, (solver.__name__, kw, ov)
             assert abs(np.linalg.norm(a[0].v) / np.linalg.norm(b[0].v) - 1) < 1e-8          # (the same normalisation)
+
+
+def test_slot_axpby_with_beta_zero_does_not_read_the_destination(annulus):
+    """BLAS convention: beta == 0 overwrites, whatever the destination holds (0 * NaN would be NaN)"""
+    L, pb, fam, mats = annulus
+    d = pb["d"]
+    X = RNG.standard_normal((d, 3)) + 1j * RNG.standard_normal((d, 3))
+    bad = np.full((d, 3), np.nan + 0j)
+    bad[::2, 1] = np.inf
+    bad[1::2, 1] = complex(-np.inf, np.nan)
+    bad[:, 2] = complex(np.inf, np.inf)
+    fam.slot_write(0, X)
+    for conj_src in (False, True):
+        fam.slot_write(1, bad)
+        al = np.array([0.5 - 1j, 2.0, -1j])
+        fam.slot_axpby(1, [0, 1, 2], 0, [2, 0, 1], alpha=al, beta=0.0, conj_src=conj_src)
+        got = fam.slot_read(1, 0, 3)
+        src = np.conj(X) if conj_src else X
+        for c, (a, sc) in enumerate(zip(al, [2, 0, 1])):
+            assert relerr(got[:, c], a * src[:, sc]) < 1e-15, (conj_src, c)
+    fam.slot_write(1, bad)                                                 # beta != 0 still reads it; the neighbours stay
+    fam.slot_axpby(1, [0], 0, [0], alpha=1.0, beta=1.0)
+    got = fam.slot_read(1, 0, 3)
+    assert np.all(np.isnan(got[:, 0])) and np.array_equal(got[:, 2], bad[:, 2])
+    fam.slot_write(0, bad)                                                 # in place: a poisoned source is another matter, a poisoned destination is not
+    fam.slot_write(0, X[:, :1], ncols_total=3, col0=1)
+    fam.slot_axpby(0, [0], 0, [1], alpha=2.0, beta=0.0)
+    assert relerr(fam.slot_read(0, 0, 1)[:, 0], 2.0 * X[:, 0]) < 1e-15
+
+
+def test_householder_many_after_non_finite_columns_were_left_in_its_slots(annulus):
+    """`_SlotStore` builds the left start vectors with beta = 0 onto slots that an earlier call on the same family left at the same
+    width (slot_write(..., None, ncols_total) does not zero those): non-finite columns there -- dw ~ 0 in a normalisation, flag -5 --
+    must not reach the next call"""
+    L, pb, fam, mats = annulus
+    from wae_amd.nlevp import beyn, householder_many
+    d = pb["d"]
+    G = np.array([300 - 100j, 900 - 100j, 900 + 100j, 300 + 100j]) * 2 * np.pi
+    Om, P = beyn(L, G, l=10, K=1, N=48)[:2]
+    res = fam.eig_residuals(np.array([L.coefficients(w_) for w_ in Om]), P=np.asfortranarray(P))
+    ok = np.nonzero(res <= 1e-4)[0][:3]
+    assert len(ok) == 3, res
+    z0 = list(Om[ok] * (1 + 2e-4))
+    P0 = np.asfortranarray(P[:, ok])
+    tol = 1e-7 * 2 * np.pi * 500.0
+    bad = np.full((d, 3), complex(np.nan, np.inf))
+    for one in (False, True):                                              # three start values (the conjugate-span start), one (conj(v0))
+        zs, Ps = (z0[:1], P0[:, :1]) if one else (z0, P0)
+        clean = householder_many(L, zs, maxiter=14, tol=tol, v0s=Ps, v0s_adj=None)
+        for slot in (4, 5, 6, 7):
+            fam.slot_write(slot, bad[:, :len(zs)])
+        again = householder_many(L, zs, maxiter=14, tol=tol, v0s=Ps, v0s_adj=None)
+        assert len(again) == len(clean) == len(zs)
+        for (s1, n1, f1), (s2, n2, f2) in zip(again, clean):
+            w1, w2 = complex(s1.params[L.eigval]), complex(s2.params[L.eigval])
+            assert f1 == f2 and f1 in (0, 1) and n1 == n2, (one, f1, f2, n1, n2)
+            assert abs(w1 - w2) <= 1e-10 * abs(w2), (one, w1, w2)
+            assert np.all(np.isfinite(s1.v)) and np.all(np.isfinite(s1.v_adj))

@@ -1973,7 +1973,10 @@ static int arnoldi_core(wae_family *h, int32_t nsys, const double *coeffsA, cons
                 al[sy] = brk ? cplx{0.0, 0.0} : cplx{hh[sy].x, 0.0};
                 any_alive = any_alive || !brk;
             }
-            if (!any_alive) break;
+            if (!any_alive) {                                    // (column j + 1 is returned, and counted in arn_cols: not what an earlier call left there)
+                launch_fill_zero(EV.p + (size_t)(j + 1) * vec, vec, st);
+                break;
+            }
             h->ydev.upload(al.data(), nsys, st);
             launch_scale_inv(w, h->ydev.p, EV.p + (size_t)(j + 1) * vec, d, nsys, st);
             HIP_CHECK(hipStreamSynchronize(st));

@@ -701,11 +701,14 @@ void launch_scale_inv(const cplx *X, const cplx *alpha, cplx *Y, int64_t n, int 
 
 // The column-major side of these three is in the CALLER's row numbering, the interleaved side in the library's (tiles.h):
 // perm[i] = caller's row of internal row i (null: same numbering).
-// out = a x + b y (or a conj(x) + b y) for one vector (out may alias x or y): the column updates of the device-resident multivectors (wae_slot_axpby)
+// out = a x + b y (or a conj(x) + b y) for one vector (out may alias x or y): the column updates of the device-resident multivectors (wae_slot_axpby).
+// b == 0 follows the BLAS convention: y is not read and out = a x, whatever y holds (a NaN or Inf left in a slot column does not survive
+// an overwrite; 0 * NaN would)
 __global__ __launch_bounds__(256) void axpby1_kernel(cplx a, const cplx *x, cplx b, const cplx *y, cplx *out, size_t n, int conj_x) {
+    const bool use_y = b.x != 0.0 || b.y != 0.0;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
         cplx r = cmul(a, conj_x ? cconj(x[e]) : x[e]);
-        cfma(r, b, y[e]);
+        if (use_y) cfma(r, b, y[e]);
         out[e] = r;
     }
 }
