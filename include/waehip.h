@@ -121,6 +121,25 @@ int wae_spmv_sum_multi(wae_family *h, const double *coeffs, const double *X, dou
  *       its host work, instead of during the first integral.
  */
 int wae_solver_setup(wae_family *h, const double *coeffs_ref, const double *opts, int32_t nopts);
+/* The same set-up from prolongators the caller supplies -- the nested hierarchy of a refined mesh (wae_octosplit_prolongator), or any
+ * other nested hierarchy -- instead of aggregating the fine matrix.  coeffs_ref, opts, nopts as in wae_solver_setup.
+ *   nlev >= 1 real CSR prolongators, finest first, 0-based, 32-bit indices, columns ascending without duplicates in every row:
+ *   prolongator k has rows[k] rows and cols[k] columns; rows[0] = d, rows[k + 1] = cols[k]; all in the caller's numbering.  R = P^T.
+ *  - Penalty rows are found at the fine level by the rule of wae_solver_setup (|a_ii| > opts[5] x the median at coeffs_ref); their rows of
+ *    prolongator 0 are emptied.  A column left without entries is dropped from its level and from the rows of the next prolongator.
+ *    Coarser levels have no penalty rows.
+ *  - The coarse planes P^T A P of the supplied levels are formed on the device, plane by plane: one thread per stored entry writes its
+ *    keyed triplets, a stable sort and a reduce-by-key sum them in a fixed order (the pipeline of the device assembly).  Two set-ups give
+ *    the same bits.  A product that expands to more than 2^31 - 1 triplets is refused (WAE_ERR_INVALID).
+ *  - If the coarsest supplied level is larger than opts[1], smoothed aggregation continues from that level's planes and its levels are
+ *    appended; opts[7] applies to those levels only.  The dense limit of wae_solver_setup holds for the last level.
+ *  - The fine level's renumbering, the tile storage of level 1, the penalty operators, the dense level and the work spaces are those of
+ *    wae_solver_setup.
+ * WAE_ERR_INVALID with a message, before the hierarchy the handle has is touched (it keeps working): nlev < 1, a null array, dimensions
+ * that do not chain, prolongator 0 with other than d rows, a row pointer that is not monotone from 0, a column out of range, unsorted or
+ * duplicate columns in a row, a value that is not finite.  wae_solver_setup after this call replaces the hierarchy again. */
+int wae_solver_setup_nested(wae_family *h, const double *coeffs_ref, const double *opts, int32_t nopts, int32_t nlev, const int64_t *rows,
+                            const int64_t *cols, const int32_t *const *ptr, const int32_t *const *col, const double *const *val);
 
 typedef struct {
     int32_t iters_max;      /* most iterations any column needed            */
@@ -457,18 +476,22 @@ int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points,
  * wae_octosplit_prolong: the nested P1 embedding from_level < to_level applied level by level to ncols complex columns (X:
  * npoints(from) x ncols column-major, interleaved re/im; Y: npoints(to) x ncols): the rows of old points are copied, the row of a new
  * point is (x[a] + x[b]) * 0.5; one kernel per level, the intermediate levels stay in HBM.
+ * wae_octosplit_prolongator: the step from_level -> from_level + 1 of that embedding as a CSR matrix, built by a kernel from the parents
+ * table in HBM: npoints(from_level + 1) rows in the order of the finer level's points, 2 npoints(from_level + 1) - npoints(from_level)
+ * entries (ptr: rows + 1, col and val: entries; 0-based); row a < npoints(from_level) holds (a, 1.0), the row of a new point holds
+ * (parent, 0.5) twice, columns ascending.  These are the prolongators wae_solver_setup_nested takes.
  * WAE_ERR_INVALID, nothing returned and nothing truncated: an index outside 0..npoints-1, a triangle edge that is no tetrahedron's
  * edge, two equal children after the sort (a simplex listed twice or repeating a point), levels < 1, or a level whose point,
  * tetrahedron or triangle count passes a 32-bit index.
  * Out of scope: meshes with a degree of symmetry (the point classes of a Bloch unit cell do not survive appended points; the reference
- * drops `dos` too), interior-triangle lists (a TODO in the reference, Meshutils.jl:656-668), P2 or Hermite prolongation, and the use of
- * the hierarchy as a geometric multigrid. */
+ * drops `dos` too), interior-triangle lists (a TODO in the reference, Meshutils.jl:656-668), and P2 or Hermite prolongation. */
 int wae_octosplit(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris,
                   int32_t levels, void **out);
 int wae_octosplit_info(const void *handle, int32_t level, int64_t *npoints, int64_t *ntets, int64_t *ntris);
 int wae_octosplit_get(const void *handle, int32_t level, double *points, int32_t *tets, int32_t *tris, int32_t *parents, int32_t *tet_labels,
                       int32_t *tri_labels);
 int wae_octosplit_prolong(const void *handle, int32_t from_level, int32_t to_level, int32_t ncols, const double *X, double *Y);
+int wae_octosplit_prolongator(const void *handle, int32_t from_level, int32_t *ptr, int32_t *col, double *val);
 int wae_octosplit_free(void *handle);
 /* -- Bloch unit cells with P1 or P2 elements: cell numbering and operator fold on the device ------------------------
  * `discretize(mesh, dscrp, C; order, b=:b)` on a mesh with a degree of symmetry: blochify (src/Bloch.jl:4-112), the dimension of

@@ -1440,7 +1440,8 @@ end
 
 # Uniform mesh refinement on the device: `octosplit(mesh)` (Meshutils.jl:589-747) and the nested P1 prolongation between its levels
 # (include/waehip.h, wae_octosplit*).  Out of scope, as there: meshes with a degree of symmetry, interior-triangle lists, P2 or Hermite
-# prolongation, the hierarchy as a geometric multigrid.
+# prolongation.  `prolongator` returns a step of the prolongation as a sparse matrix, `solver_setup_nested` builds a family's multigrid
+# hierarchy from such matrices.
 "the levels 0..levels of one `octosplit_device` call, kept in HBM (level 0 = the input); `npoints[l + 1]` points on level l"
 mutable struct Refinement
     handle::Ptr{Cvoid}
@@ -1521,6 +1522,41 @@ function prolong(ref::Refinement, X::AbstractVecOrMat{<:Number}; from::Integer=0
                 ref.handle, from, to, size(Xc, 2), Xc, Y))
     Yr = eltype(X) <: Real ? real.(Y) : Y
     return X isa AbstractVector ? vec(Yr) : Yr
+end
+
+"P = prolongator(ref; from=0): the step `from` -> `from + 1` of the nested P1 embedding as a SparseMatrixCSC (points of level from + 1 x
+points of level from), built on the device from the parents table: an old point's row holds 1, a new point's row 0.5 at its two parents."
+function prolongator(ref::Refinement; from::Integer=0)
+    0 <= from < ref.levels || throw(ArgumentError("prolongator needs 0 <= from < $(ref.levels), got $from"))
+    nf, nc = ref.npoints[from + 2], ref.npoints[from + 1]
+    ptr = zeros(Int32, nf + 1); col = zeros(Int32, 2nf - nc); val = zeros(Float64, 2nf - nc)
+    check(ccall((:wae_octosplit_prolongator, libwaehip), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                ref.handle, from, ptr, col, val))
+    # the CSR arrays of P are the CSC arrays of its transpose
+    return sparse(transpose(SparseMatrixCSC(nc, nf, Int.(ptr) .+ 1, Int.(col) .+ 1, val)))
+end
+
+"solver_setup_nested(fam, coeffs, Ps; opts=Float64[]): the multigrid set-up of `fam` from the prolongators Ps (finest first: size(Ps[1], 1)
+unknowns of the family, size(Ps[k], 2) == size(Ps[k + 1], 1)), e.g. [prolongator(ref; from=l) for l in ref.levels-1:-1:0], instead of
+smoothed aggregation (wae_solver_setup_nested; opts as for wae_solver_setup).  coeffs: the reference coefficients, one per term."
+function solver_setup_nested(fam::DeviceFamily, coeffs::Vector{ComplexF64}, Ps::AbstractVector; opts=Float64[])
+    isempty(Ps) && throw(ArgumentError("solver_setup_nested: at least one prolongator"))
+    for k in 1:length(Ps) - 1
+        size(Ps[k], 2) == size(Ps[k + 1], 1) || throw(ArgumentError("solver_setup_nested: the prolongators' dimensions do not chain at $k"))
+    end
+    # CSR of P = CSC of its transpose
+    Ts = [SparseMatrixCSC{Float64,Int}(sparse(transpose(SparseMatrixCSC{Float64,Int}(P)))) for P in Ps]
+    rows = Int64[size(P, 1) for P in Ps]; cols = Int64[size(P, 2) for P in Ps]
+    ptrs = [Int32.(T.colptr .- 1) for T in Ts]; idxs = [Int32.(T.rowval .- 1) for T in Ts]; vals = [Vector{Float64}(T.nzval) for T in Ts]
+    o = Float64.(opts)
+    GC.@preserve ptrs idxs vals begin
+        pp = Ptr{Int32}[pointer(a) for a in ptrs]; pi = Ptr{Int32}[pointer(a) for a in idxs]; pv = Ptr{Float64}[pointer(a) for a in vals]
+        check(ccall((:wae_solver_setup_nested, libwaehip), Cint,
+                    (Ptr{Cvoid}, Ptr{ComplexF64}, Ptr{Float64}, Int32, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Int32}}, Ptr{Ptr{Int32}}, Ptr{Ptr{Float64}}),
+                    fam.handle, coeffs, o, length(o), length(Ps), rows, cols, pp, pi, pv))
+    end
+    fam.solver_ready = true
+    return nothing
 end
 
 # P2 (second-order) elements, `discretize(...; order=:quad)`: edge DoFs numbered on the device (aggregate_elements, FEM.jl:84-116) and the

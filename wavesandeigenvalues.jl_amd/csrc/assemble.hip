@@ -251,10 +251,15 @@ __global__ __launch_bounds__(256) void split_keys_kernel(const unsigned long lon
 
 // keyed triplets (key = row * np + col; up to two value streams) -> CSR: stable radix sort (duplicates adjacent, in
 // element order: the sums are deterministic, no atomics), reduce-by-key, row pointer from the unique keys  (declared in
-// wae_internal.h: assemble_p2.hip feeds it too)
-P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k0, Dev<double> &mv, Dev<double> *kv) {
-    Dev<double> ms(ne), ks(kv ? ne : 1), mu(ne), ku(kv ? ne : 1);
-    Dev<int> dcol(ne), drow((size_t)npoints + 1), dnum(1);
+// wae_internal.h: assemble_p2.hip feeds it too).  triplets_to_csr_dev leaves the result in HBM (galerkin.hip keeps it there);
+// triplets_to_csr copies it out and fills the pointer of the rows without entries.
+void triplets_to_csr_dev(int64_t npoints, size_t ne, Dev<unsigned long long> &k0, Dev<double> &mv, Dev<double> *kv, TripletCsr &out) {
+    Dev<double> ms(ne), ks(kv ? ne : 1);
+    DevBuf<double> &mu = out.m, &ku = out.k;
+    DevBuf<int> &dcol = out.col, &drow = out.rowptr;
+    mu.alloc(std::max<size_t>(ne, 1)); ku.alloc(kv ? std::max<size_t>(ne, 1) : 1);
+    dcol.alloc(std::max<size_t>(ne, 1)); drow.alloc((size_t)npoints + 1);
+    Dev<int> dnum(1);
     Dev<unsigned long long> k1(ne), ku0(ne);
     Dev<unsigned int> i0(ne), i1(ne);
     const unsigned g = (unsigned)std::min<size_t>((ne + 255) / 256, 8192);
@@ -277,13 +282,20 @@ P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k
     HIP_CHECK(hipMemset(drow.p, 0xff, ((size_t)npoints + 1) * sizeof(int)));          // -1 = row without entries
     hipLaunchKernelGGL(split_keys_kernel, dim3(g), dim3(256), 0, 0, ku0.p, (size_t)nnz, (unsigned long long)npoints, dcol.p, drow.p);
     HIP_CHECK(hipGetLastError());
+    out.np = npoints; out.nnz = nnz;
+}
+
+P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k0, Dev<double> &mv, Dev<double> *kv) {
+    TripletCsr D;
+    triplets_to_csr_dev(npoints, ne, k0, mv, kv, D);
+    const int nnz = D.nnz;
     std::unique_ptr<P1Handle> H(new P1Handle);
     H->np = npoints; H->nnz = nnz;
     H->rowptr.resize((size_t)npoints + 1); H->col.resize(nnz); H->m.resize(nnz); H->k.assign(nnz, 0.0);
-    HIP_CHECK(hipMemcpy(H->rowptr.data(), drow.p, ((size_t)npoints + 1) * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(H->col.data(), dcol.p, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(H->m.data(), mu.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
-    if (kv) HIP_CHECK(hipMemcpy(H->k.data(), ku.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(H->rowptr.data(), D.rowptr.p, ((size_t)npoints + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(H->col.data(), D.col.p, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(H->m.data(), D.m.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
+    if (kv) HIP_CHECK(hipMemcpy(H->k.data(), D.k.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
     H->rowptr[npoints] = nnz;
     for (int64_t r = npoints - 1; r >= 0; --r)
         if (H->rowptr[r] < 0) H->rowptr[r] = H->rowptr[r + 1];

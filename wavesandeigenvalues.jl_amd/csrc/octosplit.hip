@@ -210,6 +210,25 @@ __global__ __launch_bounds__(256) void octo_prolong_kernel(const cplx *__restric
     }
 }
 
+// the same embedding as a CSR matrix (nnew x nold): row i < nold holds (i, 1), row nold + e holds (b, 0.5) (a, 0.5) with b < a, columns
+// ascending; one thread per row, every entry written once
+__global__ __launch_bounds__(256) void octo_prolongator_kernel(int64_t nold, const int *__restrict__ parents, int64_t nnew, int *__restrict__ ptr,
+                                                               int *__restrict__ col, double *__restrict__ val) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > nnew) return;
+    const int64_t p = i < nold ? i : nold + 2 * (i - nold);
+    ptr[i] = (int)p;
+    if (i == nnew) return;
+    if (i < nold) {
+        col[p] = (int)i;
+        val[p] = 1.0;
+    } else {
+        const int a = parents[(i - nold) * 2], b = parents[(i - nold) * 2 + 1];
+        col[p] = min(a, b); col[p + 1] = max(a, b);
+        val[p] = 0.5; val[p + 1] = 0.5;
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 struct OctoLevel {
     int64_t np = 0, nt = 0, ns = 0;
@@ -393,6 +412,27 @@ int wae_octosplit_prolong(const void *h, int32_t from_level, int32_t to_level, i
             std::swap(a, b);
         }
         HIP_CHECK(hipMemcpy(Y, a.p, (size_t)T.np * (size_t)ncols * sizeof(cplx), hipMemcpyDeviceToHost));
+        return WAE_OK;
+    });
+}
+
+int wae_octosplit_prolongator(const void *h, int32_t from_level, int32_t *ptr, int32_t *col, double *val) {
+    return wae_guarded([&]() {
+        const OctoLevel &F = octo_level(h, from_level);
+        if (from_level + 1 >= (int32_t)((const Octo *)h)->lv.size()) throw WaeError(WAE_ERR_INVALID, "from_level must be below the last level");
+        const OctoLevel &T = octo_level(h, from_level + 1);
+        if (!(ptr && col && val)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        const int64_t nnz = 2 * T.np - F.np;
+        if (nnz > INT_MAX) throw WaeError(WAE_ERR_INVALID, "the prolongator's entries do not fit a 32-bit index");
+        HIP_CHECK(hipSetDevice(((const Octo *)h)->device));
+        DevBuf<int> dptr, dcol;
+        DevBuf<double> dval;
+        dptr.alloc((size_t)T.np + 1); dcol.alloc((size_t)nnz); dval.alloc((size_t)nnz);
+        hipLaunchKernelGGL(octo_prolongator_kernel, octo_grid(T.np + 1), dim3(256), 0, 0, F.np, T.parents.p, T.np, dptr.p, dcol.p, dval.p);
+        HIP_CHECK(hipGetLastError());
+        octo_copy_out(ptr, dptr, (size_t)T.np + 1);
+        octo_copy_out(col, dcol, (size_t)nnz);
+        octo_copy_out(val, dval, (size_t)nnz);
         return WAE_OK;
     });
 }

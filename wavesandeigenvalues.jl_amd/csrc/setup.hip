@@ -1,8 +1,10 @@
 // libwaehip.so -- construction: the family handle from the caller's term matrices (wae_family_create_opts) and the multigrid
-// hierarchy with its work spaces (wae_solver_setup).  Host code and uploads only; the solvers that use what is built here are in lib.hip.
+// hierarchy with its work spaces (wae_solver_setup, and wae_solver_setup_nested from prolongators the caller supplies).  Host code and
+// uploads only, but for the Galerkin products of the supplied levels (galerkin.hip); the solvers that use what is built here are in lib.hip.
 #include <atomic>
 #include <cmath>
 #include <exception>
+#include <limits>
 #include <map>
 #include <memory>
 #include <tuple>
@@ -859,6 +861,60 @@ template <class ColMap> static CsrZ extract_rows(const CsrZ &A, const std::vecto
     return B;
 }
 
+// ----------------------------------------------------------------------------------------------------
+// wae_solver_setup_nested: the caller's prolongators
+// ----------------------------------------------------------------------------------------------------
+// checked copies of the caller's CSR prolongators (finest first); every complaint is a WaeError(WAE_ERR_INVALID) and nothing of the
+// handle has been touched when it is raised
+static std::vector<CsrD> read_prolongators(int64_t d, int32_t nlev, const int64_t *rows, const int64_t *cols, const int32_t *const *ptr,
+                                           const int32_t *const *col, const double *const *val) {
+    WAE_REQUIRE(nlev >= 1, "nested set-up: nlev must be at least 1");
+    WAE_REQUIRE(rows && cols && ptr && col && val, "nested set-up: a null array");
+    std::vector<CsrD> Ps((size_t)nlev);
+    for (int32_t k = 0; k < nlev; ++k) {
+        const std::string at = " (prolongator " + std::to_string(k) + ")";
+        WAE_REQUIRE(ptr[k] && col[k] && val[k], "nested set-up: a null array" + at);
+        if (k == 0) WAE_REQUIRE(rows[0] == d, "nested set-up: prolongator 0 has " + std::to_string(rows[0]) + " rows, the family has " + std::to_string(d) + " unknowns");
+        else WAE_REQUIRE(rows[k] == cols[k - 1], "nested set-up: the dimensions do not chain: " + std::to_string(rows[k]) + " rows after " + std::to_string(cols[k - 1]) + " columns" + at);
+        WAE_REQUIRE(cols[k] >= 1 && cols[k] < 2147483647 && rows[k] >= 1, "nested set-up: bad dimensions" + at);
+        CsrD &P = Ps[(size_t)k];
+        P.n = rows[k]; P.m = cols[k];
+        const int32_t *pp = ptr[k];
+        WAE_REQUIRE(pp[0] == 0, "nested set-up: the row pointer does not start at 0" + at);
+        for (int64_t i = 0; i < P.n; ++i) WAE_REQUIRE(pp[i] <= pp[i + 1], "nested set-up: the row pointer is not monotone" + at);
+        const int64_t nnz = pp[P.n];
+        P.ptr.assign(pp, pp + P.n + 1);
+        P.col.assign(col[k], col[k] + nnz);
+        P.val.assign(val[k], val[k] + nnz);
+        for (int64_t i = 0; i < P.n; ++i)
+            for (int e = P.ptr[i]; e < P.ptr[i + 1]; ++e) {
+                WAE_REQUIRE(P.col[e] >= 0 && P.col[e] < P.m, "nested set-up: a column out of range" + at);
+                WAE_REQUIRE(e == P.ptr[i] || P.col[e - 1] < P.col[e], "nested set-up: unsorted or duplicate columns in a row" + at);
+                WAE_REQUIRE(std::isfinite(P.val[e]), "nested set-up: a value that is not finite" + at);
+            }
+    }
+    return Ps;
+}
+// row i of the result is row src[i] of P (empty where src[i] < 0); the columns no row uses are dropped and the others renumbered in
+// their order: kept[c'] = the old number of column c'
+static CsrD take_rows_drop_columns(const CsrD &P, const std::vector<int> &src, std::vector<int> &kept) {
+    CsrD B;
+    B.n = (int64_t)src.size();
+    B.ptr.assign(src.size() + 1, 0);
+    std::vector<int> newcol((size_t)P.m, -1);
+    for (size_t i = 0; i < src.size(); ++i) {
+        if (src[i] >= 0)
+            for (int e = P.ptr[src[i]]; e < P.ptr[src[i] + 1]; ++e) { B.col.push_back(P.col[e]); B.val.push_back(P.val[e]); newcol[(size_t)P.col[e]] = 0; }
+        B.ptr[i + 1] = (int)B.col.size();
+    }
+    kept.clear();
+    for (int64_t c = 0; c < P.m; ++c)
+        if (newcol[(size_t)c] == 0) { newcol[(size_t)c] = (int)kept.size(); kept.push_back((int)c); }
+    B.m = (int64_t)kept.size();
+    for (int &c : B.col) c = newcol[(size_t)c];             // (monotone: the rows stay sorted)
+    return B;
+}
+
 // A helper thread that is waited for when this goes out of scope, also on an exception
 struct Joined {
     std::future<void> f;
@@ -880,6 +936,7 @@ struct SolverSetup {
     std::vector<AmgLevel> lv;
     std::vector<char> pen;          // penalty rows of the fine level
     Level1Work l1;
+    std::vector<CsrD> supplied;     // wae_solver_setup_nested: the caller's prolongators, finest first (empty: smoothed aggregation)
     Lap lap{env.debug, "[setup]", 34, h->stream};
     double t_amg0 = 0.0, t_amg1 = 0.0;
     Joined basis_job, l1_job;
@@ -963,6 +1020,87 @@ struct SolverSetup {
         fprintf(stderr, "\n");
         for (size_t l = 0; l < lv.size(); ++l) {
             fprintf(stderr, "[setup] level %zu: n=%lld P nnz=%lld nnz/plane:", l + 1, (long long)lv[l].P.m, (long long)lv[l].P.col.size());
+            for (const CsrZ &A : lv[l].coarse_planes) fprintf(stderr, " %lld", (long long)A.nnz());
+            fprintf(stderr, "\n");
+        }
+    }
+
+    // wae_solver_setup_nested: the same lv and pen from the caller's prolongators.  Penalty rows by amg_setup's rule (the diagonal of the
+    // reference operator summed in plane order, as its shape-matrix pass sums it); their rows of the first prolongator are emptied, a
+    // column nobody uses any more leaves its level and the rows of the next prolongator.  The coarse planes are formed on the device
+    // (galerkin.hip), a level's result feeding the next product there; level 1 goes to the helper thread as in coarsen().
+    void find_penalty_rows() {
+        const int64_t n0 = h->d;
+        std::vector<double> dabs((size_t)n0);
+        host_ranges(n0, row_threads(n0), [&](int64_t lo, int64_t hi, int) {
+            for (int64_t i = lo; i < hi; ++i) {
+                zc dg = 0;
+                for (size_t k = 0; k < h->planes0.size(); ++k) {
+                    const CsrZ &A = h->planes0[k];
+                    const int *b = A.col.data() + A.ptr[i], *e = A.col.data() + A.ptr[i + 1];
+                    const int *f = std::lower_bound(b, e, (int)i);
+                    if (f != e && *f == (int)i) dg += pc[k] * A.val[(size_t)(f - A.col.data())];
+                }
+                dabs[(size_t)i] = std::abs(dg);
+            }
+        });
+        std::vector<double> tmp(dabs);
+        std::nth_element(tmp.begin(), tmp.begin() + n0 / 2, tmp.end());
+        const double med = tmp[(size_t)(n0 / 2)];
+        pen.assign((size_t)n0, 0);
+        for (int64_t i = 0; i < n0; ++i) pen[(size_t)i] = dabs[(size_t)i] > ao.penalty_ratio * med;
+    }
+    void coarsen_nested() {
+        const size_t nlev = supplied.size();
+        find_penalty_rows();
+        lv.clear();
+        lv.reserve(nlev + (size_t)ao.max_levels + 1);          // (the helper thread keeps a reference to lv[0])
+        const bool want_plan = env.tile_level1 && !h->tile_row_ptr.empty();
+        // rows of the first prolongator: the library's numbering of the fine level, penalty rows empty
+        std::vector<int> src((size_t)h->d), kept;
+        for (int64_t i = 0; i < h->d; ++i) src[(size_t)i] = pen[(size_t)i] ? -1 : (h->perm_h.empty() ? (int)i : h->perm_h[(size_t)i]);
+        std::vector<DevPlane> cur, next;
+        for (size_t l = 0; l < nlev; ++l) {
+            AmgLevel L;
+            L.P = take_rows_drop_columns(supplied[l], src, kept);
+            supplied[l] = CsrD();                                 // (the caller's copy is not needed again)
+            WAE_REQUIRE(L.P.m >= 1, "nested set-up: a supplied level is left without unknowns");
+            src = kept;                                        // the next prolongator keeps the rows of the columns that are left
+            L.R = csr_transpose(L.P);
+            DevProlongator Pd;
+            upload_prolongator(L.P, Pd);
+            L.coarse_planes.resize((size_t)h->nplanes);
+            next.clear();
+            next.resize((size_t)h->nplanes);
+            int64_t triplets = 0;
+            for (int q = 0; q < h->nplanes; ++q) {
+                if (l == 0) {                                  // a fine plane is in HBM only for its own product
+                    DevPlane A;
+                    upload_plane(h->planes0[(size_t)q], A);
+                    triplets += galerkin_device(A, Pd, next[(size_t)q], L.coarse_planes[(size_t)q]);
+                } else {
+                    triplets += galerkin_device(cur[(size_t)q], Pd, next[(size_t)q], L.coarse_planes[(size_t)q]);
+                    cur[(size_t)q] = DevPlane();
+                }
+            }
+            cur.swap(next);
+            if (env.debug) fprintf(stderr, "[setup] supplied level %zu: %lld -> %lld unknowns, %lld triplets\n", l + 1, (long long)L.P.n, (long long)L.P.m, (long long)triplets);
+            lv.push_back(std::move(L));
+            if (l == 0 && want_plan) l1_job.f = std::async(std::launch::async, [this]() { l1.run(h, lv[0], env); });
+        }
+        cur.clear();
+        if (lv.back().P.m > ao.max_coarse) {                   // smoothed aggregation goes on from the last supplied level (no penalty rows there)
+            AmgOptions ac = ao;
+            ac.penalty_ratio = std::numeric_limits<double>::infinity();
+            std::vector<AmgLevel> more;
+            amg_setup(lv.back().coarse_planes, pc, ac, more, nullptr, excl ? &pc_shape : nullptr);
+            for (AmgLevel &L : more) lv.push_back(std::move(L));
+        }
+        t_amg1 = now_s();
+        if (!env.debug) return;
+        fprintf(stderr, "[setup] nested levels (device products + continuation) %.3f s\n", t_amg1 - t_amg0);
+        for (size_t l = 0; l < lv.size(); ++l) {
+            fprintf(stderr, "[setup] level %zu%s: n=%lld P nnz=%lld nnz/plane:", l + 1, l < nlev ? " (supplied)" : "", (long long)lv[l].P.m, (long long)lv[l].P.col.size());
             for (const CsrZ &A : lv[l].coarse_planes) fprintf(stderr, " %lld", (long long)A.nnz());
             fprintf(stderr, "\n");
         }
@@ -1081,7 +1219,11 @@ struct SolverSetup {
         drop_hierarchy();
         t_amg0 = now_s();
         reserve_device_memory();
-        coarsen();
+        if (supplied.empty()) coarsen();
+        else {
+            h->solver_ready = false;                           // (until the new hierarchy stands)
+            coarsen_nested();
+        }
         lap.t = now_s();
         adopt_level1();
         lap("wait for level 1 (helper thread)");
@@ -1103,6 +1245,19 @@ extern "C" int wae_solver_setup(wae_family *h, const double *coeffs_ref, const d
         WAE_REQUIRE(h && coeffs_ref, "bad argument");
         HIP_CHECK(hipSetDevice(h->device));
         SolverSetup s{h, coeffs_ref, opts, nopts};
+        s.run();
+        return WAE_OK;
+    });
+}
+
+extern "C" int wae_solver_setup_nested(wae_family *h, const double *coeffs_ref, const double *opts, int32_t nopts, int32_t nlev, const int64_t *rows,
+                                       const int64_t *cols, const int32_t *const *ptr, const int32_t *const *col, const double *const *val) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && coeffs_ref, "bad argument");
+        std::vector<CsrD> Ps = read_prolongators(h->d, nlev, rows, cols, ptr, col, val);       // (before anything of the handle changes)
+        HIP_CHECK(hipSetDevice(h->device));
+        SolverSetup s{h, coeffs_ref, opts, nopts};
+        s.supplied = std::move(Ps);
         s.run();
         return WAE_OK;
     });

@@ -255,6 +255,35 @@ template <class T> struct Dev {     // function-local device array of the assemb
 };
 // keyed triplets (key = row * npoints + col, ne of them with ne <= INT_MAX; one or two value streams) -> CSR of npoints rows
 P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k0, Dev<double> &mv, Dev<double> *kv);
+// the same, the result left on the device: nnz entries in col / m / k (k only with kv); rowptr[r] = the position of row r's first entry,
+// -1 for a row without entries, rowptr[npoints] not written (the caller fills both: the row that follows, and nnz)
+struct TripletCsr {
+    int64_t np = 0;
+    int nnz = 0;
+    DevBuf<int> rowptr, col;
+    DevBuf<double> m, k;
+};
+void triplets_to_csr_dev(int64_t npoints, size_t ne, Dev<unsigned long long> &k0, Dev<double> &mv, Dev<double> *kv, TripletCsr &out);
+
+// Galerkin products on the device (galerkin.hip): a square plane and a prolongator in HBM, C = P^T A P through the triplet pipeline.
+struct DevPlane {                   // CSR in HBM, sorted columns; a real plane has no im
+    int64_t n = 0, nnz = 0;
+    bool real = true;
+    DevBuf<int> ptr, col;
+    DevBuf<double> re, im;
+};
+struct DevProlongator {             // real CSR (n x m) in HBM
+    int64_t n = 0, m = 0, nnz = 0;
+    DevBuf<int> ptr, col;
+    DevBuf<double> val;
+};
+constexpr int64_t WAE_GALERKIN_MAX_TRIPLETS = 2147483647;       // the count the sort and the reduce-by-key take
+void upload_plane(const CsrZ &A, DevPlane &D);
+void upload_prolongator(const CsrD &P, DevProlongator &D);
+// C = P^T A P: C stays in HBM (it feeds the next level's product), host receives a copy.  Deterministic: the triplets are written in
+// the order of A's entries and summed after a stable sort.  WaeError(WAE_ERR_INVALID) if the product expands to more than
+// WAE_GALERKIN_MAX_TRIPLETS triplets.  Returns the number of triplets.
+int64_t galerkin_device(const DevPlane &A, const DevProlongator &P, DevPlane &C, CsrZ &host);
 // keyed values (key = node * n, ne of them, 0 < ne <= INT_MAX) -> the dense real vector of their sums per node (out: n doubles, host), through
 // triplets_to_csr with the single column 0: the same stable sort and reduce-by-key as the matrices
 void pairs_to_dense(int64_t n, size_t ne, Dev<unsigned long long> &k0, Dev<double> &v, double *out);

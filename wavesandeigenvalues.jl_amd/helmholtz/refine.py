@@ -3,13 +3,17 @@ tetrahedron split into 8 and every boundary triangle into 4, index for index the
 the levels.  The levels stay in HBM behind one handle; what is carried from a mesh to its refinement by the labels alone (fields per
 simplex, domains, the reference tetrahedron of a flame) is an O(n) gather on the host.
 
+``RefinedMesh.prolongator`` returns a step of that prolongation as a sparse matrix, ``RefinedMesh.prolongators`` the list a family
+assembled on a refined level hands to its multigrid set-up (``LinearOperatorFamily.solver_prolongators``, wae_solver_setup_nested).
+
 Out of scope: meshes with a degree of symmetry (the point classes of a Bloch unit cell do not survive appended points), interior-triangle
-lists, P2 or Hermite prolongation, and the use of the hierarchy as a geometric multigrid."""
+lists, and P2 or Hermite prolongation."""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
+import scipy.sparse as sp
 
 from .. import _lib
 from . import probe
@@ -63,6 +67,38 @@ class RefinedMesh:
         _lib.check(_lib.lib().wae_octosplit_prolong(self._h, f, t, ncols, _zptr_f(Xf), _zptr_f(Y)))
         Y = Y.real.copy() if real else Y
         return Y[:, 0] if X.ndim == 1 else Y
+
+    def prolongator(self, from_level=0):
+        """The step ``from_level`` -> ``from_level + 1`` of the nested P1 embedding as a ``scipy.sparse.csr_matrix`` (points of the finer
+        level x points of ``from_level``): the row of an old point holds 1.0 at its own column, the row of a new point 0.5 at its two
+        parents, columns ascending.  With a device handle the matrix is built by a kernel from the parents table in HBM
+        (wae_octosplit_prolongator); without one the same matrix is formed on the host."""
+        if isinstance(from_level, bool) or not isinstance(from_level, (int, np.integer)):
+            raise ValueError(f"from_level must be an integer, got {from_level!r}")
+        f = self._level(from_level, "from_level")
+        if f >= self.levels:
+            raise ValueError(f"from_level must be below the last level {self.levels}, got {f}")
+        n_old, n_new = len(self.points[f]), len(self.points[f + 1])
+        nnz = 2 * n_new - n_old
+        if self._h:
+            ptr, col, val = np.zeros(n_new + 1, dtype=np.int32), np.zeros(nnz, dtype=np.int32), np.zeros(nnz)
+            ip = C.POINTER(C.c_int32)
+            _lib.check(_lib.lib().wae_octosplit_prolongator(self._h, f, ptr.ctypes.data_as(ip), col.ctypes.data_as(ip),
+                                                            val.ctypes.data_as(C.POINTER(C.c_double))))
+        else:
+            par = np.sort(np.asarray(self.parents[f + 1], dtype=np.int32).reshape(-1, 2), axis=1)
+            ptr = np.concatenate([np.arange(n_old, dtype=np.int32), n_old + 2 * np.arange(n_new - n_old + 1, dtype=np.int32)])
+            col = np.concatenate([np.arange(n_old, dtype=np.int32), par.ravel()])
+            val = np.concatenate([np.ones(n_old), np.full(2 * (n_new - n_old), 0.5)])
+        return sp.csr_matrix((val, col, ptr), shape=(n_new, n_old))
+
+    def prolongators(self, to_level=-1, coarsest=0):
+        """The prolongators of a family assembled on ``to_level``, finest first, down to level ``coarsest``: what
+        ``LinearOperatorFamily.solver_prolongators`` and ``DeviceFamily.setup_solver(prolongators=...)`` take."""
+        t, c = self._level(to_level, "to_level"), self._level(coarsest, "coarsest")
+        if c >= t:
+            raise ValueError(f"prolongators needs coarsest < to_level, got {c} and {t}")
+        return [self.prolongator(l) for l in range(t - 1, c - 1, -1)]
 
     # ---- host-side carriers: O(n) gathers through the labels ---------------------------------------------------------------------
     def _carry(self, values, labels, count, to_level, what):

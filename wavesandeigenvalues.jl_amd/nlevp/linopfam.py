@@ -77,6 +77,36 @@ class UnconvergedWarning(RuntimeWarning):
     """an inner multigrid-GMRES solve stopped at its iteration limit or stagnated above the requested tolerance"""
 
 
+def _check_prolongators(prolongators, d):
+    """the prolongators of DeviceFamily.setup_solver as canonical real CSR matrices; ValueError for what wae_solver_setup_nested refuses"""
+    if isinstance(prolongators, (str, bytes)) or sp.issparse(prolongators) or isinstance(prolongators, np.ndarray):
+        raise ValueError("prolongators must be a list of sparse matrices, finest first")
+    try:
+        Ps = list(prolongators)
+    except TypeError:
+        raise ValueError("prolongators must be a list of sparse matrices, finest first") from None
+    if not Ps:
+        raise ValueError("prolongators: at least one matrix is needed")
+    out, rows = [], int(d)
+    for k, P in enumerate(Ps):
+        if not sp.issparse(P):
+            raise ValueError(f"prolongator {k} is no scipy.sparse matrix")
+        if np.iscomplexobj(P):
+            raise ValueError(f"prolongator {k} is complex: the transfers are real")
+        if P.ndim != 2 or P.shape[0] != rows or P.shape[1] < 1:
+            raise ValueError(f"prolongator {k} has shape {P.shape}, {rows} rows expected" + (" (the family's unknowns)" if k == 0 else ""))
+        P = sp.csr_matrix(P, dtype=np.float64)
+        P.sum_duplicates()
+        P.sort_indices()
+        if not np.all(np.isfinite(P.data)):
+            raise ValueError(f"prolongator {k} holds a value that is not finite")
+        if P.nnz >= 2 ** 31 or P.shape[1] >= 2 ** 31:
+            raise ValueError(f"prolongator {k} does not fit 32-bit indices")
+        out.append(P)
+        rows = P.shape[1]
+    return out
+
+
 class DeviceFamily:
     """Owner of a ``wae_family`` handle: all term matrices resident in HBM (include/waehip.h).
 
@@ -168,10 +198,13 @@ class DeviceFamily:
     # -- solver --------------------------------------------------------------------------------------
     def setup_solver(self, coeffs_ref, theta=0.02, max_coarse=128, jacobi_weight=0.8, sweeps=1, restart=30,
                      penalty_ratio=1e8, batch=64, shape_exclude=(), probe_columns=0, snapshots=0, jacobi_weight_post=0.0,
-                     jacobi_weight_light=0.0):
+                     jacobi_weight_light=0.0, prolongators=None):
         """shape_exclude: indices of terms kept out of the multigrid shape matrix (e.g. the seam parts of a Bloch family);
         probe_columns, snapshots: workspace hints for the contour integrals to come (include/waehip.h opts[8], [9]);
-        jacobi_weight_post / _light: opts[10], [11] (0 = the library's defaults, 0.9 and 0.5)"""
+        jacobi_weight_post / _light: opts[10], [11] (0 = the library's defaults, 0.9 and 0.5);
+        prolongators: None = smoothed aggregation (wae_solver_setup); a list of real sparse matrices, finest first (d x n_1, n_1 x n_2, ...),
+        e.g. ``RefinedMesh.prolongators()`` = the hierarchy is built from them (wae_solver_setup_nested)"""
+        Ps = None if prolongators is None else _check_prolongators(prolongators, self.d)
         c = np.ascontiguousarray(coeffs_ref, dtype=np.complex128)
         mask = 0
         for k in shape_exclude:
@@ -179,7 +212,17 @@ class DeviceFamily:
                 mask |= 1 << int(k)
         opts = np.array([theta, max_coarse, jacobi_weight, sweeps, restart, penalty_ratio, batch, float(mask), float(probe_columns),
                          float(snapshots), float(jacobi_weight_post), float(jacobi_weight_light)], dtype=np.float64)
-        check(_lib.lib().wae_solver_setup(self.handle, zptr(c), opts.ctypes.data_as(C.POINTER(C.c_double)), len(opts)))
+        if Ps is None:
+            check(_lib.lib().wae_solver_setup(self.handle, zptr(c), opts.ctypes.data_as(C.POINTER(C.c_double)), len(opts)))
+        else:
+            n = len(Ps)
+            rows = (C.c_int64 * n)(*[P.shape[0] for P in Ps])
+            cols = (C.c_int64 * n)(*[P.shape[1] for P in Ps])
+            keep = [(np.ascontiguousarray(P.indptr, dtype=np.int32), np.ascontiguousarray(P.indices, dtype=np.int32),
+                     np.ascontiguousarray(P.data, dtype=np.float64)) for P in Ps]
+            arr = [(C.c_void_p * n)(*[k[j].ctypes.data for k in keep]) for j in range(3)]
+            check(_lib.lib().wae_solver_setup_nested(self.handle, zptr(c), opts.ctypes.data_as(C.POINTER(C.c_double)), len(opts), n, rows, cols,
+                                                     arr[0], arr[1], arr[2]))
         self.solver_ready = True
         self.batch = batch
 
@@ -580,6 +623,9 @@ class LinearOperatorFamily:
         self.solver_opts = {}
         self.solver_ref = None          # reference value of the eigenvalue parameter for the multigrid set-up
         self.solver_ref_coeffs = None   # or: explicit reference coefficients (one per term) for the set-up
+        # None: smoothed aggregation; a list of sparse prolongators, finest first (RefinedMesh.prolongators()): the hierarchy is built
+        # from them (wae_solver_setup_nested)
+        self.solver_prolongators = None
         self.rb_snapshots = None        # Beyn: snapshot points for projected initial guesses (None = automatic, 0 = off)
         # when the library may treat a term as symmetric for `A'` products (include/waehip.h wae_family_create_opts opts[0]): 0 = only
         # if it is bitwise symmetric; producers of finite-element terms (helmholtz_family) set 1e-14
@@ -640,8 +686,10 @@ class LinearOperatorFamily:
 
     def ensure_solver(self):
         fam = self.device()
+        nested = getattr(self, "solver_prolongators", None)
+        extra = {} if nested is None else {"prolongators": nested}
         if not fam.solver_ready and self.solver_ref_coeffs is not None:
-            fam.setup_solver(np.asarray(self.solver_ref_coeffs, dtype=np.complex128), **self.solver_opts)
+            fam.setup_solver(np.asarray(self.solver_ref_coeffs, dtype=np.complex128), **self.solver_opts, **extra)
         if not fam.solver_ready:
             zref = self.solver_ref
             if zref is None:
@@ -654,7 +702,7 @@ class LinearOperatorFamily:
                 c = self.coefficients(zref)
             finally:
                 self.params, self.active, self.mode = saved
-            fam.setup_solver(c, **self.solver_opts)
+            fam.setup_solver(c, **self.solver_opts, **extra)
         return fam
 
     # -- functor ---------------------------------------------------------------------------------------
