@@ -696,7 +696,8 @@ int wae_bench_triad(int32_t device, int64_t n, int32_t reps, double *gbs_out);
  * runs ONE such launch so that the parity tests can compare every form with the CPU oracle:
  *   which = 0: the operator of multigrid level `level` (0 = the family itself; >= 1 needs wae_solver_setup);
  *   which = 1: the restriction from `level` to `level + 1` (coefficients ignored; mode 0);
- *   which = 2: the prolongation from `level + 1` to `level`, Y = B + P X (coefficients ignored; mode 3).
+ *   which = 2: the prolongation from `level + 1` to `level`, Y = B + P X (coefficients ignored; mode 3): the out-of-place
+ *              form of the prolongation kernels, or, when B and Y are the same array, their in-place form.
  *   mode: 0 Y = A X | 1 Y = B - A X | 2 Y = X + w/diag (B - A X) | 3 Y = B + A X | 4 Y = (A X)/diag | 5 Y = (B - A X)/diag
  *         | 6 Y = A X and B2 = w/diag (A X)  (diag = the diagonal of sum_k c_k A_k, w = jac_w)
  *   coeffs: ncoef x T (ncoef = 1: one system; ncoef = r: one coefficient row per column);
@@ -707,6 +708,17 @@ int wae_bench_triad(int32_t device, int64_t n, int32_t reps, double *gbs_out);
 int wae_debug_spmv(wae_family *h, int32_t which, int32_t level, int32_t mode, const double *coeffs, int32_t ncoef, const double *X,
                    const double *B, double *Y, double *B2, int32_t r, int32_t op, double jac_w, const uint8_t *cmask, int32_t flags,
                    int64_t *n_in_q, int64_t *n_out_q);
+
+/* ONE launch of the prolongation from `level + 1` to `level` in the form that also delivers the column norms of its result (the light
+ * cycle of the solvers ends in it): Y = B + P X and norms[b] = ||Y[:, b]||, summed per workgroup and then in workgroup order, so that two
+ * calls give the same bits.  Needs wae_solver_setup.
+ *   X       column-major n_coarse x r complex; B, Y: column-major n_fine x r complex (sizes: wae_debug_spmv, which = 2); norms: r doubles.
+ *           Level 0 is in the caller's row numbering, coarser levels in the hierarchy's own.
+ *   cmask   NULL or one byte per 8-column chunk; the columns of a chunk with byte 0 keep what Y held on entry and get the norm 0.
+ *   flags   bit 0: the CSR kernel where the level has the tile form too; bit 1: the norms alone -- Y is returned as it was passed.
+ * No set-up, a level without a prolongation, r outside 1..256 or an unknown flag: WAE_ERR_INVALID, nothing is launched. */
+int wae_debug_prolong(wae_family *h, int32_t level, const double *X, const double *B, double *Y, double *norms, int32_t r, const uint8_t *cmask,
+                      int32_t flags);
 
 /* ONE application of the multigrid preconditioner -- the V-cycle the solvers run, on the handle's own workspaces -- started at
  * multigrid level `level`, so that tests/ can compare the composition (which weight goes to which sweep, the light cycle, the fused

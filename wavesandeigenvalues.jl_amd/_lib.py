@@ -36,7 +36,7 @@ _lib = None
 EXPORTS = [
     "wae_last_error", "wae_device_count", "wae_version", "wae_family_create", "wae_family_create_opts", "wae_family_destroy",
     "wae_family_info", "wae_family_spmv_bytes", "wae_spmv_sum", "wae_spmv_sum_cols", "wae_spmv_sum_multi", "wae_solver_setup",
-    "wae_solve", "wae_solve_guess", "wae_beyn_moments", "wae_beyn_moments_mgpu", "wae_beyn_moments_rb", "wae_rb_export", "wae_rb_import", "wae_eig_residuals", "wae_arnoldi_shiftinvert", "wae_arnoldi_shiftinvert_batch", "wae_perturb", "wae_slot_write", "wae_slot_read", "wae_slot_axpby", "wae_slot_forms", "wae_arnoldi_shiftinvert_slots", "wae_arnoldi_ritz_to_slot", "wae_perturb_slots", "wae_perturb_batch", "wae_perturb_batch_slots", "wae_p1_assemble", "wae_p1_assemble_boundary", "wae_p1_assemble_flame", "wae_p1_info", "wae_p1_get", "wae_p1_free", "wae_p1_shape_sensitivity", "wae_p1_shape_sensitivity_flame", "wae_bench_spmv", "wae_bench_spmv_level", "wae_bench_triad", "wae_debug_spmv", "wae_debug_vcycle", "wae_debug_vec", "wae_debug_gmres",
+    "wae_solve", "wae_solve_guess", "wae_beyn_moments", "wae_beyn_moments_mgpu", "wae_beyn_moments_rb", "wae_rb_export", "wae_rb_import", "wae_eig_residuals", "wae_arnoldi_shiftinvert", "wae_arnoldi_shiftinvert_batch", "wae_perturb", "wae_slot_write", "wae_slot_read", "wae_slot_axpby", "wae_slot_forms", "wae_arnoldi_shiftinvert_slots", "wae_arnoldi_ritz_to_slot", "wae_perturb_slots", "wae_perturb_batch", "wae_perturb_batch_slots", "wae_p1_assemble", "wae_p1_assemble_boundary", "wae_p1_assemble_flame", "wae_p1_info", "wae_p1_get", "wae_p1_free", "wae_p1_shape_sensitivity", "wae_p1_shape_sensitivity_flame", "wae_bench_spmv", "wae_bench_spmv_level", "wae_bench_triad", "wae_debug_spmv", "wae_debug_prolong", "wae_debug_vcycle", "wae_debug_vec", "wae_debug_gmres",
     "wae_tall_create", "wae_tall_destroy", "wae_tall_info", "wae_tall_write", "wae_tall_read", "wae_tall_gram", "wae_tall_mul", "wae_tall_hankel",
     "wae_p2_connectivity", "wae_p2_connectivity_info", "wae_p2_connectivity_get", "wae_p2_connectivity_free", "wae_p2_assemble",
     "wae_p2_assemble_boundary", "wae_p2_assemble_flame",
@@ -173,6 +173,7 @@ def lib():
     L.wae_bench_spmv_level.argtypes = [C.c_void_p, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.POINTER(C.c_int64)]
     L.wae_debug_spmv.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, C.c_double,
                                  C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.wae_debug_prolong.argtypes = [C.c_void_p, C.c_int32, dp, dp, dp, dp, C.c_int32, C.POINTER(C.c_uint8), C.c_int32]
     L.wae_debug_vcycle.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
     L.wae_debug_vec.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.c_int32,
                                 C.POINTER(C.c_uint8), ip, ip]

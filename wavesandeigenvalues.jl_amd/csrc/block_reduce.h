@@ -1,5 +1,6 @@
 // The first stage of every reduction over the rows of an interleaved multivector: the sum inside one workgroup.  Shared by vec.hip (the
-// Krylov reductions) and forced.hip (the observation functionals of a frequency sweep); nothing else belongs here.
+// Krylov reductions), forced.hip (the observation functionals of a frequency sweep) and kernels.hip (the column norms of a prolonged
+// result); nothing else belongs here.
 #pragma once
 #include "kernel_helpers.h"
 

@@ -7,6 +7,7 @@
 // rowptr/col once and its planes' values interleaved per nonzero ([nnz][nplanes], real planes as 8-B doubles),
 // so the fused multi-term SpMV reads each index once and all term values of that nonzero in one load.
 #include <type_traits>
+#include "block_reduce.h"
 #include "kernel_helpers.h"
 
 #include <cstdlib>
@@ -1394,35 +1395,62 @@ __global__ __launch_bounds__(256) void jacobi0_kernel(OpDev op, const cplx *__re
     }
 }
 
-// Prolongation + correction of the V-cycle, X[row][b] += sum_p P.val[p] * Xc[P.col[p]][b]: a streaming update of the fine
-// multivector (read + write, 32 B per entry) with ~4 gathered coarse rows per fine row.  One lane per (row, column): the
+// Prolongation + correction of the V-cycle, Y[row][b] = X[row][b] + sum_p P.val[p] * Xc[P.col[p]][b]: a streaming update of the fine
+// multivector (read + write, 32 B per entry) with ~4 gathered coarse rows per fine row.  Y may be X (the in-place form: the same
+// bits) or another multivector (the light cycle's result goes straight into a Krylov basis slot); masked chunks of Y are not written.  One lane per (row, column): the
 // lanes of a wavefront read whole 1-KB coarse rows, coalesced; no LDS, no reduction.  (As a MODE_ADD launch of the
 // general SpMV kernel this took 422 us per call at C2, longer than the operator itself.)
+__device__ __forceinline__ cplx prolong_row(const int *__restrict__ ptr, const int *__restrict__ col, const double *__restrict__ val,
+                                            const cplx *__restrict__ Xc, cplx acc, size_t row, int b, int nb) {
+    const int p0 = ptr[row], p1 = ptr[row + 1];
+    int p = p0;
+    for (; p + 4 <= p1; p += 4) {
+        cplx v[4];
+        double a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { a[u] = val[p + u]; v[u] = Xc[(size_t)col[p + u] * nb + b]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { acc.x += a[u] * v[u].x; acc.y += a[u] * v[u].y; }
+    }
+    for (; p < p1; ++p) {
+        const double a = val[p];
+        const cplx v = Xc[(size_t)col[p] * nb + b];
+        acc.x += a * v.x; acc.y += a * v.y;
+    }
+    return acc;
+}
 __global__ __launch_bounds__(256) void prolong_add_kernel(const int *__restrict__ ptr, const int *__restrict__ col, const double *__restrict__ val,
-                                                          const cplx *__restrict__ Xc, cplx *__restrict__ X, size_t total, int nb,
+                                                          const cplx *__restrict__ Xc, const cplx *X, cplx *Y, size_t total, int nb,
                                                           const unsigned char *__restrict__ cmask) {
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const size_t row = e / nb;
         const int b = (int)(e - row * nb);
         if (cmask && !cmask[b >> 3]) continue;
-        const int p0 = ptr[row], p1 = ptr[row + 1];
-        cplx acc = X[e];
-        int p = p0;
-        for (; p + 4 <= p1; p += 4) {
-            cplx v[4];
-            double a[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { a[u] = val[p + u]; v[u] = Xc[(size_t)col[p + u] * nb + b]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { acc.x += a[u] * v[u].x; acc.y += a[u] * v[u].y; }
-        }
-        for (; p < p1; ++p) {
-            const double a = val[p];
-            const cplx v = Xc[(size_t)col[p] * nb + b];
-            acc.x += a * v.x; acc.y += a * v.y;
-        }
-        X[e] = acc;
+        Y[e] = prolong_row(ptr, col, val, Xc, X[e], row, b, nb);
     }
+}
+// The same with the column norms of the result: partial[blk][b] = sum over this workgroup's rows of |Y[row][b]|^2, for a second stage in
+// block order (launch_reduce_partials): where a cycle ends in its prolongation, the norms of its result cost no pass of their own.
+// Thread t owns column t % nb and every R-th row, R = 256 / nb (as vec.hip dots_kernel); masked columns give 0.  Y == nullptr: the
+// norms alone, nothing is written.
+__global__ __launch_bounds__(256) void prolong_add_norm_kernel(const int *__restrict__ ptr, const int *__restrict__ col, const double *__restrict__ val,
+                                                               const cplx *__restrict__ Xc, const cplx *X, cplx *Y, int64_t n, int nb,
+                                                               const unsigned char *__restrict__ cmask, cplx *__restrict__ partial) {
+    __shared__ double sm[256];
+    const int tid = threadIdx.x;
+    const int R = 256 / nb;
+    const int b = tid % nb, rl = tid / nb;
+    const bool live = rl < R && !(cmask && !cmask[b >> 3]);
+    double nrm2 = 0.0;
+    if (live)
+        for (int64_t row = (int64_t)blockIdx.x * R + rl; row < n; row += (int64_t)gridDim.x * R) {
+            const size_t e = (size_t)row * nb + b;
+            const cplx acc = prolong_row(ptr, col, val, Xc, X[e], (size_t)row, b, nb);
+            if (Y) Y[e] = acc;
+            nrm2 += acc.x * acc.x + acc.y * acc.y;
+        }
+    nrm2 = nb <= 64 && (nb & (nb - 1)) == 0 ? block_colsum<true, 256>(nrm2, nb, sm) : block_colsum<false, 256>(nrm2, nb, sm);
+    if (tid < nb) partial[(size_t)blockIdx.x * nb + tid] = cplx{nrm2, 0.0};
 }
 // ---- prolongation by fine tile (wae_internal.h XferTilesDev) ------------------------------------------------------------------
 // One workgroup per fine tile, walking the 8-column chunks of the batch; thread (tid >> 3, tid & 7) = (row or slot, column): the 8
@@ -1433,10 +1461,18 @@ __global__ __launch_bounds__(256) void prolong_add_kernel(const int *__restrict_
 // (The restriction was built the same way -- a tile's fine rows staged in LDS, one partial sum per slot and tile, a second kernel
 // summing a coarse row's partials in a fixed order -- and measured: 606 + 103 us against 540 us for the tile kernel over coarse rows;
 // removed.)
-__global__ __launch_bounds__(256) void prolong_tiles_kernel(XferTilesDev T, const cplx *__restrict__ Xc, cplx *__restrict__ X, int nb,
-                                                            const unsigned char *__restrict__ cmask) {
+// Y = X + P Xc as in prolong_add_kernel (Y == X: in place).  NORM: also partial[tile][b] = sum over the tile's rows of |Y[row][b]|^2
+// (0 for the columns of a masked chunk), one block reduction per chunk, for a second stage in tile order; Y == nullptr then gives the
+// norms alone.
+template <bool NORM>
+__global__ __launch_bounds__(256) void prolong_tiles_kernel(XferTilesDev T, const cplx *__restrict__ Xc, const cplx *X, cplx *Y, int nb,
+                                                            const unsigned char *__restrict__ cmask, cplx *__restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) unsigned char xt_smem[];
+    __shared__ double nsm[NORM ? 32 : 1];                                    // (block_colsum over 8 columns: one value per wavefront and column)
     const int t = blockIdx.x, tid = threadIdx.x;
+    if (NORM)
+        for (int bb = tid; bb < nb; bb += 256)
+            if (cmask && !cmask[bb >> 3]) partial[(size_t)t * nb + bb] = cplx{0.0, 0.0};
     const int col = tid & 7, rl = tid >> 3;
     const int nch = (nb + 7) >> 3;
     const int s0 = T.tptr[t], ns = T.tptr[t + 1] - s0;
@@ -1467,14 +1503,20 @@ __global__ __launch_bounds__(256) void prolong_tiles_kernel(XferTilesDev T, cons
         const int cn = next_chunk(cmask, c + 1, nch);
         if (cn < nch) request(cn);
         __syncthreads();
+        double nrm2 = 0.0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int r = rl + 32 * k;
             if (r < nr && colok) {
                 cplx acc = cur[k];
                 for (int p = ep[r]; p < ep[r + 1]; ++p) { const double a = ev[p]; const cplx v = sl[(int)el[p] * 8 + col]; acc.x += a * v.x; acc.y += a * v.y; }
-                X[(size_t)(r0 + r) * nb + b] = acc;
+                if (!NORM || Y) Y[(size_t)(r0 + r) * nb + b] = acc;
+                if (NORM) nrm2 += acc.x * acc.x + acc.y * acc.y;
             }
+        }
+        if (NORM) {
+            nrm2 = block_colsum<true, 256>(nrm2, 8, nsm);
+            if (tid < 8 && colok) partial[(size_t)t * nb + b] = cplx{nrm2, 0.0};      // (tid < 8: col == tid)
         }
         c = cn;
     }
@@ -1482,10 +1524,17 @@ __global__ __launch_bounds__(256) void prolong_tiles_kernel(XferTilesDev T, cons
 static size_t xfer_lds_bytes(const XferTilesDev &T) {
     return (size_t)T.maxslots * 8 * sizeof(cplx) + (size_t)T.maxent * sizeof(double) + 260 * sizeof(int) + (size_t)T.maxent * sizeof(unsigned short) + 16;
 }
-void launch_prolong_tiles(const XferTilesDev &T, const cplx *Xc, cplx *X, int nb, hipStream_t st, const unsigned char *cmask) {
+void launch_prolong_tiles(const XferTilesDev &T, const cplx *Xc, const cplx *X, cplx *Y, int nb, hipStream_t st, const unsigned char *cmask,
+                          cplx *partial, cplx *norms) {
     if (!T.ntiles || nb <= 0) return;
-    hipLaunchKernelGGL(prolong_tiles_kernel, dim3(T.ntiles), dim3(256), xfer_lds_bytes(T), st, T, Xc, X, nb, cmask);
+    if (!partial) {
+        hipLaunchKernelGGL(prolong_tiles_kernel<false>, dim3(T.ntiles), dim3(256), xfer_lds_bytes(T), st, T, Xc, X, Y, nb, cmask, (cplx *)nullptr);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    hipLaunchKernelGGL(prolong_tiles_kernel<true>, dim3(T.ntiles), dim3(256), xfer_lds_bytes(T), st, T, Xc, X, Y, nb, cmask, partial);
     HIP_CHECK(hipGetLastError());
+    launch_reduce_partials(partial, T.ntiles, nb, norms, 1, st);
 }
 
 // compact <-> full row sets (penalty-block polish, lib.hip): out[i][b] = X[rows[i]][b];  X[rows[i]][b] += D[i][b]
@@ -1506,12 +1555,20 @@ __global__ __launch_bounds__(256) void scatter_add_rows_kernel(const cplx *__res
     }
 }
 
-void launch_prolong_add(const int *ptr, const int *col, const double *val, int64_t n, const cplx *Xc, cplx *X, int nb, hipStream_t st,
-                        const unsigned char *cmask) {
+void launch_prolong_add(const int *ptr, const int *col, const double *val, int64_t n, const cplx *Xc, const cplx *X, cplx *Y, int nb,
+                        hipStream_t st, const unsigned char *cmask, cplx *partial, cplx *norms) {
     const size_t total = (size_t)n * nb;
     if (!total) return;
-    hipLaunchKernelGGL(prolong_add_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, st, ptr, col, val, Xc, X, total, nb, cmask);
+    if (!partial) {
+        hipLaunchKernelGGL(prolong_add_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, st, ptr, col, val, Xc, X, Y, total, nb, cmask);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    if (nb > 256) throw WaeError(WAE_ERR_INVALID, "prolongation with norms: nb must be in 1..256");
+    const unsigned grid = row_grid(n, nb, 256, 1, PROLONG_NORM_BLOCKS).grid;
+    hipLaunchKernelGGL(prolong_add_norm_kernel, dim3(grid), dim3(256), 0, st, ptr, col, val, Xc, X, Y, n, nb, cmask, partial);
     HIP_CHECK(hipGetLastError());
+    launch_reduce_partials(partial, (int)grid, nb, norms, 1, st);
 }
 
 void launch_gather_rows(const cplx *X, const int *rows, int64_t nrows, int nb, cplx *out, hipStream_t st) {

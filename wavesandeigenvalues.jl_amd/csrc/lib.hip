@@ -56,9 +56,14 @@ static double pre_weight(const wae_family *h) {
 }
 // x = Minv b on level l;  returns pointer to the result (either lx[l] or lt[l])
 // have_x0: the first sweep of level l (x = w/diag b) is already in lx[l] (written by the SpMV that produced b, MODE_AX_J0)
-// final_out (level 0 only): the last post-smoothing sweep writes its result there (a Krylov basis slot) instead of into lx/lt
+// final_out (level 0 only): the last post-smoothing sweep -- or, in a cycle without one, the prolongation -- writes its result there (a
+// Krylov basis slot) instead of into lx/lt; masked chunks of final_out are left as they were
+// cn (level 0 only): the caller wants the column norms of the result in cn->out.  A cycle that ends in its prolongation (the light
+// cycle) takes them from that kernel and sets cn->done -- with cn->only it then writes no result at all; any other cycle leaves
+// cn->done false and the caller runs its own pass over the result.
+struct CycleNorms { cplx *out; bool only; bool done = false; };
 static cplx *vcycle(wae_family *h, const Batch &bt, int l, const cplx *b, const unsigned char *cm = nullptr, bool have_x0 = false,
-                    cplx *final_out = nullptr) {
+                    cplx *final_out = nullptr, CycleNorms *cn = nullptr) {
     const int L = (int)h->ops.size() - 1;
     hipStream_t st = h->stream;
     if (l == L) {
@@ -83,8 +88,6 @@ static cplx *vcycle(wae_family *h, const Batch &bt, int l, const cplx *b, const 
     const bool by_tile = h->xfer[l].ft.ready && bt.nb >= 8 && xfer_tiles_on();      // (wae_internal.h XferTiles: level 0, wide batches)
     launch_spmv(h->xfer[l].devR(), h->one_dev.p, 1 << 30, additive ? b : t, h->lb[l + 1].p, nullptr, 0.0, bt.nb, MODE_AX, st, cm);
     const cplx *xc = vcycle(h, bt, l + 1, h->lb[l + 1].p, cm);
-    if (by_tile) launch_prolong_tiles(h->xfer[l].ft.dev, xc, x, bt.nb, st, cm);
-    else launch_prolong_add(h->xfer[l].p_ptr.p, h->xfer[l].p_col.p, h->xfer[l].p_val.p, h->xfer[l].nf, xc, x, bt.nb, st, cm);
     // Post-smoothing on the coarse levels (WAE_VC_POST_COARSE): 1 always, 0 never, 2 (default) everywhere but in the projected phase of
     // a contour integral.  A solve that starts from a projected guess (216 of the 256 points of the benchmark contour) takes 1-5 steps:
     // there a cheaper cycle beats a better one (measured at 1M unknowns: projected phase 1.17 -> 0.99 s without the coarse
@@ -95,6 +98,17 @@ static cplx *vcycle(wae_family *h, const Batch &bt, int l, const cplx *b, const 
     static const int light_post0 = getenv("WAE_VC_LIGHT_POST0") ? atoi(getenv("WAE_VC_LIGHT_POST0")) : 0;
     const bool no_post = l >= 1 ? (post_coarse == 0 || (post_coarse == 2 && h->vc_light)) : (h->vc_light && !light_post0);
     const int npost = no_post ? 0 : h->nsweeps;
+    // x + P xc: in place, or -- when no sweep follows -- straight into final_out, with the norms of the result if they are asked for
+    const size_t npart = (size_t)(by_tile ? h->xfer[l].ft.dev.ntiles : PROLONG_NORM_BLOCKS) * bt.nb;
+    // (not fused -- the caller then runs its own norms pass, cn->done stays false -- when the partial sums do not fit the reduction
+    // scratch, when the level is empty (the launchers return at once), or when a caller wants no result AND a result in final_out)
+    const bool norms = cn && l == 0 && npost == 0 && npart <= h->partial.n && h->ops[l].n > 0 && !(cn->only && final_out);
+    cplx *const px = (norms && cn->only) ? nullptr : (final_out && npost == 0) ? final_out : x;
+    cplx *const part = norms ? h->partial.p : nullptr, *const nout = norms ? cn->out : nullptr;
+    if (by_tile) launch_prolong_tiles(h->xfer[l].ft.dev, xc, x, px, bt.nb, st, cm, part, nout);
+    else launch_prolong_add(h->xfer[l].p_ptr.p, h->xfer[l].p_col.p, h->xfer[l].p_val.p, h->xfer[l].nf, xc, x, px, bt.nb, st, cm, part, nout);
+    if (norms) cn->done = true;
+    if (px) x = px;
     // (WAE_JAC_POST: a post-smoothing weight of its own -- two sweeps with different weights form a degree-2 polynomial smoother)
     static const double w_post_env = getenv("WAE_JAC_POST") ? atof(getenv("WAE_JAC_POST")) : 0.0;
     const double w_post = w_post_env > 0.0 ? w_post_env : h->jac_w_post;
@@ -103,6 +117,7 @@ static cplx *vcycle(wae_family *h, const Batch &bt, int l, const cplx *b, const 
         launch_spmv(A, pc, bt.cps, x, dst, b, w_post, bt.nb, MODE_JAC, st, cm);
         if (dst == t) std::swap(x, t); else x = dst;
     }
+    // (for a cycle in which neither the last sweep nor the prolongation has written final_out; none is left today)
     if (final_out && x != final_out) { launch_copy(x, final_out, (size_t)h->ops[l].n * bt.nb, st); x = final_out; }
     return x;
 }
@@ -228,6 +243,7 @@ struct GmresEnv {
     int pair_min = env_int("WAE_GMRES_PAIR", 2);              // device pair steps from this step of a cycle on (< 0: off; 4 until round 4: 2.02 -> 1.99 s per pass)
     int narrow_pair = env_int("WAE_NARROW_PAIR", -1);         // narrow pair steps at every size (1), never (0), from 4 MB per basis vector (-1)
     int debug = env_int("WAE_GMRES_DEBUG", 0);                // 1: one line per solve, 2: also per cycle start, 3: also the wide batches' step counts
+    bool mask0 = env_int("WAE_GMRES_MASK0", 1) != 0;          // 0: the device recurrence masks converged chunks only in solves that start from a guess
 };
 static const GmresEnv &gmres_env() { static const GmresEnv e; return e; }
 
@@ -298,19 +314,21 @@ struct Gmres {
     cplx *pr_dev = nullptr, *pr_host = nullptr;
 
     // X = 0 unless have_x0; returns M^-1 b, whose norm scales the stopping test; from a zero guess it is also the first
-    // preconditioned residual (nothing touches the V-cycle's buffers until then)
+    // preconditioned residual (nothing touches the V-cycle's buffers until then).  From a guess nobody reads M^-1 b itself: a cycle
+    // that can deliver the norms from its last kernel does not write it.
     cplx *start() {
         if (!have_x0) launch_fill_zero(X, vec, st);
-        cplx *const zb = vcycle(h, bt, 0, B);
-        launch_norms(zb, n, nb, h->partial.p, h->hdev.p, st);
+        CycleNorms cn{h->hdev.p, have_x0};
+        cplx *const zb = vcycle(h, bt, 0, B, nullptr, false, nullptr, &cn);
+        if (!cn.done) launch_norms(zb, n, nb, h->partial.p, h->hdev.p, st);
         HIP_CHECK(hipMemcpyAsync(hp, h->hdev.p, nb * sizeof(cplx), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         for (int b = 0; b < nb; ++b) { bnorm[b] = hp[b].x; if (!(bnorm[b] > 0.0)) done[b] = 1; }
         return zb;
     }
-    cplx *residual() {                                // M^-1 (b - A x)
+    cplx *residual(CycleNorms *cn = nullptr) {        // M^-1 (b - A x)
         launch_spmv(A, pc, bt.cps, X, h->W.p, B, 0.0, nb, MODE_RES, st);
-        return vcycle(h, bt, 0, h->W.p);
+        return vcycle(h, bt, 0, h->W.p, nullptr, false, nullptr, cn);
     }
     // a guess that is worse than no guess (an ill-conditioned projected system) is dropped, column by column (true: start over)
     bool drop_bad_guess() {
@@ -381,12 +399,15 @@ struct Gmres {
     // The device recurrence: the same left-preconditioned, lock-step, unnormalised-basis GMRES(m) as the host's lazy form, with the
     // per-column Hessenberg / Givens / convergence bookkeeping in kernels (vec.hip gmres_*_kernel): an iteration is a chain of
     // launches with no device-to-host copy; the host looks at three status words every WAE_GMRES_SYNC iterations (default 4) and at
-    // the per-column figures once per restart cycle.  Columns that converge between two looks are masked on the device at once
-    // (their 8-column chunks are skipped by every kernel), so the overshoot costs launches, not traffic.
+    // the per-column figures once per restart cycle.  In batches of at least 8 columns an 8-column chunk whose columns have all
+    // converged is masked on the device at once and skipped by every kernel of the recurrence, from a guess and from zero alike, so
+    // finished systems cost launches, not traffic, while the slowest one ends.  A masked chunk of a basis slot keeps stale bits; the
+    // update x += V y never reads them, because their coefficients are exact zeros (vec.hip axpy_neg_kernel).  WAE_GMRES_MASK0=0 masks
+    // only in solves that start from a guess, as it was while that update still read every entry.
     int run_device(wae_solve_info *info) {
         const GmresEnv &env = gmres_env();
         const double lim = env.lazy_limit;
-        const bool use_mask = have_x0;
+        const bool use_mask = have_x0 || (env.mask0 && nb >= 8);
         const int nch = (nb + 7) / 8;
         const int histcap = maxit + m + 8;
         // device state
@@ -421,9 +442,10 @@ struct Gmres {
         std::vector<int> hostint((size_t)5 * nb + 4);
         bool first = !have_x0;
         while (true) {
-            cplx *const z0 = first ? zb : residual();
+            CycleNorms cn{h->hdev.p, false};
+            cplx *const z0 = first ? zb : residual(&cn);
             first = false;
-            launch_norms(z0, n, nb, h->partial.p, h->hdev.p, st);
+            if (!cn.done) launch_norms(z0, n, nb, h->partial.p, h->hdev.p, st);
             HIP_CHECK(hipMemcpyAsync(hp, h->hdev.p, (size_t)nb * sizeof(cplx), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
             if (drop_bad_guess()) continue;
@@ -2617,10 +2639,10 @@ int wae_debug_spmv(wae_family *h, int32_t which, int32_t level, int32_t mode, co
         if (flags & 1) A.tiles = nullptr;
         const Transfer *xf = which == 0 ? nullptr : &h->xfer[level];
         const bool by_tile = xf && xf->ft.ready && !(flags & 1) && r >= 8;
-        if (which == 2) {                                           // Y = B + P X, in place on the staged B
-            launch_copy(bi.p, yi.p, cout, st);                      // (masked chunks: Y and B agree there only if the caller passed them equal)
-            if (by_tile) launch_prolong_tiles(xf->ft.dev, xi.p, yi.p, r, st, cmask ? cm.p : nullptr);
-            else launch_prolong_add(xf->p_ptr.p, xf->p_col.p, xf->p_val.p, xf->nf, xi.p, yi.p, r, st, cmask ? cm.p : nullptr);
+        if (which == 2) {                                           // Y = B + P X; B and Y the same array: in place.  A masked chunk keeps what Y held
+            const cplx *src = (const void *)B == (const void *)Y ? yi.p : bi.p;
+            if (by_tile) launch_prolong_tiles(xf->ft.dev, xi.p, src, yi.p, r, st, cmask ? cm.p : nullptr);
+            else launch_prolong_add(xf->p_ptr.p, xf->p_col.p, xf->p_val.p, xf->nf, xi.p, src, yi.p, r, st, cmask ? cm.p : nullptr);
         } else
         launch_spmv(A, which == 0 ? pcd.p : h->one_dev.p, cps, xi.p, yi.p, (mode == MODE_AX || mode == MODE_AX_DS) ? nullptr : bi.p, jac_w, r, mode, st,
                     cmask ? cm.p : nullptr);
@@ -2632,6 +2654,50 @@ int wae_debug_spmv(wae_family *h, int32_t which, int32_t level, int32_t mode, co
             HIP_CHECK(hipMemcpyAsync(B2, yc.p, cout * sizeof(cplx), hipMemcpyDeviceToHost, st));
         }
         HIP_CHECK(hipStreamSynchronize(st));
+        return WAE_OK;
+    });
+}
+
+// ONE launch of a prolongation kernel with its norm output (include/waehip.h)
+int wae_debug_prolong(wae_family *h, int32_t level, const double *X, const double *B, double *Y, double *norms, int32_t r, const uint8_t *cmask,
+                      int32_t flags) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && X && B && Y && norms, "bad argument");
+        require_solver(h);
+        WAE_REQUIRE(level >= 0 && level < (int)h->xfer.size(), "no such level");
+        WAE_REQUIRE(r >= 1 && r <= 256, "bad argument (1 <= r <= 256)");
+        WAE_REQUIRE(flags >= 0 && flags < 4, "unknown flag");
+        const Transfer *xf = &h->xfer[level];
+        const int64_t nc = xf->nc, nf = xf->nf;
+        HIP_CHECK(hipSetDevice(h->device));
+        hipStream_t st = h->stream;
+        const int *perm = level == 0 ? h->perm() : nullptr;       // level 0 is in the caller's row numbering
+        const size_t cin = (size_t)nc * r, cout = (size_t)nf * r;
+        const bool by_tile = xf->ft.ready && !(flags & 1) && r >= 8;
+        DevBuf<cplx> xc, yc, xi, yi, bi, part, nrm;
+        DevBuf<unsigned char> cm;
+        xc.alloc(cin); yc.alloc(cout); xi.alloc(cin); yi.alloc(cout); bi.alloc(cout); nrm.alloc((size_t)r);
+        part.alloc((size_t)(by_tile ? xf->ft.dev.ntiles : PROLONG_NORM_BLOCKS) * r);
+        HIP_CHECK(hipMemcpyAsync(xc.p, X, cin * sizeof(cplx), hipMemcpyHostToDevice, st));
+        launch_colmajor_to_inter(xc.p, nc, r, xi.p, r, st, nullptr);
+        HIP_CHECK(hipMemcpyAsync(yc.p, Y, cout * sizeof(cplx), hipMemcpyHostToDevice, st));
+        launch_colmajor_to_inter(yc.p, nf, r, yi.p, r, st, perm);
+        HIP_CHECK(hipStreamSynchronize(st));                       // (yc is staged twice)
+        HIP_CHECK(hipMemcpyAsync(yc.p, B, cout * sizeof(cplx), hipMemcpyHostToDevice, st));
+        launch_colmajor_to_inter(yc.p, nf, r, bi.p, r, st, perm);
+        if (cmask) {
+            cm.alloc((size_t)(r + 7) / 8);
+            HIP_CHECK(hipMemcpyAsync(cm.p, cmask, (size_t)(r + 7) / 8, hipMemcpyHostToDevice, st));
+        }
+        cplx *const dst = (flags & 2) ? nullptr : yi.p;
+        if (by_tile) launch_prolong_tiles(xf->ft.dev, xi.p, bi.p, dst, r, st, cmask ? cm.p : nullptr, part.p, nrm.p);
+        else launch_prolong_add(xf->p_ptr.p, xf->p_col.p, xf->p_val.p, nf, xi.p, bi.p, dst, r, st, cmask ? cm.p : nullptr, part.p, nrm.p);
+        launch_inter_to_colmajor(yi.p, r, nf, r, yc.p, st, perm);
+        HIP_CHECK(hipMemcpyAsync(Y, yc.p, cout * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        std::vector<cplx> hn((size_t)r);
+        HIP_CHECK(hipMemcpyAsync(hn.data(), nrm.p, (size_t)r * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int b = 0; b < r; ++b) norms[b] = hn[(size_t)b].x;
         return WAE_OK;
     });
 }
@@ -2746,8 +2812,8 @@ int wae_bench_spmv_level(wae_family *h, const double *coeffs, int32_t which, int
         const bool by_tile = xf && xf->ft.ready && r >= 8 && xfer_tiles_on();
         auto one = [&]() {
             if (which == 2) {
-                if (by_tile) launch_prolong_tiles(xf->ft.dev, x.p, y.p, r, st);
-                else launch_prolong_add(xf->p_ptr.p, xf->p_col.p, xf->p_val.p, xf->nf, x.p, y.p, r, st, nullptr);
+                if (by_tile) launch_prolong_tiles(xf->ft.dev, x.p, y.p, y.p, r, st);
+                else launch_prolong_add(xf->p_ptr.p, xf->p_col.p, xf->p_val.p, xf->nf, x.p, y.p, y.p, r, st, nullptr);
             } else launch_spmv(A, pcp, 1 << 30, x.p, y.p, nullptr, 0.0, r, MODE_AX, st);
         };
         if (which == 2) HIP_CHECK(hipMemsetAsync(y.p, 0, (size_t)n_out * r * sizeof(cplx), st));

@@ -1,5 +1,7 @@
 // Vector kernels of libwaehip.so on interleaved multivectors X[row][b] (layout: kernels.hip) -- gfx950 (MI355X, CDNA4; wave64) only:
 // the Krylov streams and their reductions, the snapshot-basis helpers, the GMRES bookkeeping and the perturbation recurrence.
+#include <type_traits>
+
 #include "block_reduce.h"
 #include "kernel_helpers.h"
 
@@ -108,8 +110,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const cplx *__rest
         out[e] = acc;
     }
 }
-static void launch_reduce_partials(const cplx *partial, int nblk, int count, cplx *out, int do_sqrt, hipStream_t st,
-                                   const cplx *scale = nullptr, cplx *inv_out = nullptr) {
+void launch_reduce_partials(const cplx *partial, int nblk, int count, cplx *out, int do_sqrt, hipStream_t st, const cplx *scale, cplx *inv_out) {
     if (count <= 256) hipLaunchKernelGGL(reduce_partials_kernel<2>, dim3((count + 1) / 2), dim3(256), 0, st, partial, nblk, count, out, do_sqrt, scale, inv_out);
     else hipLaunchKernelGGL(reduce_partials_kernel<8>, dim3((count + 7) / 8), dim3(256), 0, st, partial, nblk, count, out, do_sqrt, scale, inv_out);
     HIP_CHECK(hipGetLastError());
@@ -214,10 +215,15 @@ void launch_norms(const cplx *X, int64_t n, int nb, cplx *partial, cplx *out, hi
 
 // W[row][b] = base[row][b] + sign * sum_i c[i][b] V_i[row][b].  The nv x nb coefficients are staged in LDS once per
 // workgroup (reading them per element through the vector cache doubled the L1 traffic of this streaming kernel), and
-// the basis vectors are fetched AXU at a time so that AXU 16-B loads are in flight per lane.
+// the basis vectors are fetched AXU at a time so that up to AXU 16-B loads are in flight per lane.
 // Thread t owns column t % nb and every R-th row, R = 256 / nb (as in dots_kernel).
+// A lane whose coefficient for V_i is exactly (0, 0) neither loads its entry of V_i nor adds to its sum: the update x += V y at the end
+// of a lock-step cycle has zeros for every step beyond a column's own (gmres_solve_y_kernel), about half of all (vector, column) pairs
+// of a contour pass, and what a converged column's chunk of a basis slot holds is stale (any bits, a NaN included: 0 * NaN would poison
+// the sum).  The choice is per lane: the other lanes of the wavefront still have AXU loads in flight.
 constexpr int AXU = 8;
 constexpr int AX_MAXC = 4096;      // coefficients per launch (64 KB of LDS)
+__device__ __forceinline__ bool nonzero(const cplx &c) { return c.x != 0.0 || c.y != 0.0; }
 // NORM: additionally partial[blk][b] = sum over this workgroup's rows of |W[row][b]|^2 (the Gram-Schmidt step needs the norm
 // of the vector it has just written: one pass over it less)
 template <bool NORM>
@@ -236,30 +242,55 @@ __global__ __launch_bounds__(256) void axpy_neg_kernel(const cplx *__restrict__ 
     const bool live = rl < R && !(cmask && !cmask[b >> 3]);
     if (!NORM && !live) return;
     double nrm2 = 0.0;
+    // bit u: vector i0 + u exists and this lane's coefficient of it is not (0, 0).  The bits of a group of AXU vectors are taken one group
+    // ahead, while the loads of the group before are in flight, so that no load waits for LDS; they do not depend on the row, and those
+    // of the first group are taken once.  The last group may be short: its missing vectors have no bit, and their LDS reads go to the last
+    // vector's coefficient.  group_coefs reads the AXU coefficients in a row and pins them in registers: left to itself the compiler puts
+    // every read behind a branch of its own, with a wait each.
+    const cplx *const hb = hs + b;
+    auto group_coefs = [&](int i0, cplx (&c)[AXU]) {
+#pragma unroll
+        for (int u = 0; u < AXU; ++u) c[u] = hb[(i0 + u < nv ? i0 + u : nv - 1) * nb];
+#pragma unroll
+        for (int u = 0; u < AXU; ++u) asm volatile("" : "+v"(c[u].x), "+v"(c[u].y));      // no instruction
+    };
+    auto group_bits = [&](int i0) {
+        cplx c[AXU];
+        group_coefs(i0, c);
+        unsigned m = 0;
+#pragma unroll
+        for (int u = 0; u < AXU; ++u) m |= (unsigned)(i0 + u < nv) & (unsigned)nonzero(c[u]) ? 1u << u : 0u;
+        return m;
+    };
+    const unsigned nz0 = (live && nv > 0) ? group_bits(0) : 0u;
     if (live)
     for (int64_t row = (int64_t)blockIdx.x * R + rl; row < n; row += (int64_t)gridDim.x * R) {
         const size_t e = (size_t)row * nb + b;
         cplx acc = base ? base[e] : cplx{0.0, 0.0};
-        int i = 0;
-        for (; i + AXU <= nv; i += AXU) {
-            cplx v[AXU];
+        // one group: the loads its bits ask for, the bits of the next group, the sums; returns those bits.  The products are written out
+        // with fma: these are the roundings this kernel has always had -- a full group and the short last one (`full`) differ in which
+        // product of the imaginary part is rounded first -- and no compiler choice can move them.
+        auto group = [&](int i, unsigned nz, auto full) {
+            cplx v[AXU], c[AXU];
 #pragma unroll
-            for (int u = 0; u < AXU; ++u) v[u] = stream_load(V + (size_t)(i + u) * stride + e);
+            for (int u = 0; u < AXU; ++u) v[u] = (nz >> u & 1u) ? stream_load(V + (size_t)(i + u) * stride + e) : cplx{0.0, 0.0};
+            const unsigned nz_next = i + AXU < nv ? group_bits(i + AXU) : 0u;
+            group_coefs(i, c);
 #pragma unroll
             for (int u = 0; u < AXU; ++u) {
-                const cplx c = hs[(i + u) * nb + b];
-                acc.x += c.x * v[u].x - c.y * v[u].y;
-                acc.y += c.x * v[u].y + c.y * v[u].x;
+                cplx t = acc;
+                t.x += fma(c[u].x, v[u].x, -(c[u].y * v[u].y));
+                t.y += decltype(full)::value ? fma(c[u].y, v[u].x, c[u].x * v[u].y) : fma(c[u].x, v[u].y, c[u].y * v[u].x);
+                if (nz >> u & 1u) acc = t;
             }
-        }
-        for (; i < nv; ++i) {
-            const cplx c = hs[i * nb + b];
-            const cplx v = stream_load(V + (size_t)i * stride + e);
-            acc.x += c.x * v.x - c.y * v.y;
-            acc.y += c.x * v.y + c.y * v.x;
-        }
+            return nz_next;
+        };
+        int i = 0;
+        unsigned nz = nz0;
+        for (; i + AXU <= nv; i += AXU) nz = group(i, nz, std::true_type{});
+        if (i < nv) group(i, nz, std::false_type{});
         W[e] = acc;
-        if (NORM) nrm2 += acc.x * acc.x + acc.y * acc.y;
+        if (NORM) nrm2 += fma(acc.x, acc.x, acc.y * acc.y);      // (written out for the same reason)
     }
     if (NORM) {
         __syncthreads();                        // hs is re-used for the reduction

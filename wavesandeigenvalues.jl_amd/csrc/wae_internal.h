@@ -228,7 +228,10 @@ struct XferTiles {
     XferTilesDev dev;
     bool ready = false;
 };
-void launch_prolong_tiles(const XferTilesDev &T, const cplx *Xc, cplx *X, int nb, hipStream_t s, const unsigned char *cmask = nullptr);
+// Y = X + P Xc; Y == X is the in-place form; masked chunks of Y are not written.  partial (T.ntiles x nb entries) and norms (nb):
+// also norms[b] = ||Y[:, b]|| (0 for a masked column), summed per tile and then in tile order; Y may then be null (the norms alone)
+void launch_prolong_tiles(const XferTilesDev &T, const cplx *Xc, const cplx *X, cplx *Y, int nb, hipStream_t s, const unsigned char *cmask = nullptr,
+                          cplx *partial = nullptr, cplx *norms = nullptr);
 
 struct Transfer {                   // P (n_fine x n_coarse) and R = P^T as single-plane real operators
     int64_t nf = 0, nc = 0;
@@ -356,9 +359,14 @@ void launch_inter_to_colmajor(const cplx *Xi, int nb, int64_t d, int r, cplx *Xc
 // replicate V (col-major d x l) into an interleaved block: column b -> V[:, b % l]
 void launch_replicate(const cplx *Vc, int64_t d, int l, cplx *Xi, int nb, hipStream_t s, const int *perm = nullptr);
 // snapshot-basis helpers: one system's l columns out of a batch; X = sum_i y[i][b] Q_i[row][b % l]; zero selected columns
-// V-cycle prolongation: X += P Xc (P real CSR, n fine rows)
-void launch_prolong_add(const int *ptr, const int *col, const double *val, int64_t n, const cplx *Xc, cplx *X, int nb, hipStream_t s,
-                        const unsigned char *cmask = nullptr);
+// V-cycle prolongation: Y = X + P Xc (P real CSR, n fine rows; Y == X: in place; masked chunks of Y are not written); partial
+// (PROLONG_NORM_BLOCKS x nb entries) and norms as launch_prolong_tiles
+constexpr int PROLONG_NORM_BLOCKS = 1024;
+void launch_prolong_add(const int *ptr, const int *col, const double *val, int64_t n, const cplx *Xc, const cplx *X, cplx *Y, int nb, hipStream_t s,
+                        const unsigned char *cmask = nullptr, cplx *partial = nullptr, cplx *norms = nullptr);
+// out[e] = sum over the nblk first-stage partials [blk][count] in index order (vec.hip); do_sqrt: the square root of the real part
+void launch_reduce_partials(const cplx *partial, int nblk, int count, cplx *out, int do_sqrt, hipStream_t s, const cplx *scale = nullptr,
+                            cplx *inv_out = nullptr);
 // out[(i*nw + j)*nb + b] = V_i[:,b]^H W_j[:,b], nw <= 4: one pass over V for nw right-hand vectors
 void launch_dots_multi(const cplx *V, size_t sv, int nv, const cplx *W, size_t sw, int nw, int64_t n, int nb, cplx *partial, cplx *out,
                        hipStream_t s);

@@ -518,6 +518,22 @@ class DeviceFamily:
                                  None if B2 is None else zptr(B2), r, op, float(jac_w), cm, 1 if no_tiles else 0, C.byref(nin), C.byref(nout)))
         return (Y, B2) if mode == 6 else Y
 
+    def debug_prolong(self, X, B, Y0=None, level=0, cmask=None, no_tiles=False, norms_only=False):
+        """wae_debug_prolong (test hook): one launch of the prolongation that also delivers the column norms of its result.  Returns
+        (Y, norms), Y = B + P X; a masked chunk, and every column with ``norms_only``, returns ``Y0``."""
+        nin, nout = C.c_int64(0), C.c_int64(0)
+        check(_lib.lib().wae_debug_spmv(self.handle, 2, level, 0, None, 0, None, None, None, None, 0, 0, 0.0, None, 0, C.byref(nin), C.byref(nout)))
+        nf = nout.value
+        Bf = np.asfortranarray(np.asarray(B, dtype=np.complex128).reshape(nf, -1))
+        r = Bf.shape[1]
+        Xf = np.asfortranarray(np.asarray(X, dtype=np.complex128).reshape(nin.value, r))
+        Y = np.zeros((nf, r), dtype=np.complex128, order="F") if Y0 is None else np.asfortranarray(np.array(Y0, dtype=np.complex128).reshape(nf, r))
+        norms = np.zeros(r)
+        cm = None if cmask is None else (C.c_uint8 * ((r + 7) // 8))(*[1 if x else 0 for x in cmask])
+        check(_lib.lib().wae_debug_prolong(self.handle, level, zptr(Xf), zptr(Bf), zptr(Y), norms.ctypes.data_as(C.POINTER(C.c_double)), r, cm,
+                                           (1 if no_tiles else 0) | (2 if norms_only else 0)))
+        return Y, norms
+
     def level_sizes(self):
         """(n_in, n_out) of every sparse level operator / restriction of the hierarchy (test hook)"""
         out = []
