@@ -1,4 +1,4 @@
-"""Reference of the shift-invert Arnoldi entries (csrc/lib.hip arnoldi_core behind wae_arnoldi_shiftinvert, wae_arnoldi_shiftinvert_batch,
+"""Reference of the shift-invert Arnoldi entries (csrc/arnoldi.hip arnoldi_core behind wae_arnoldi_shiftinvert, wae_arnoldi_shiftinvert_batch,
 wae_arnoldi_shiftinvert_slots and wae_arnoldi_ritz_to_slot) and of their host half (nlevp/local_solvers.py _ritz, eigs_many,
 eigs_many_slots), for tests/test_gpu_arnoldi.py; tests/test_arnref.py checks it where no GPU is.
 

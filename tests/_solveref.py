@@ -1,4 +1,4 @@
-"""Reference of the lock-step GMRES DRIVERS (csrc/lib.hip struct Gmres and the chunk loop of wae_solve_guess), for
+"""Reference of the lock-step GMRES DRIVERS (csrc/gmres.hip struct Gmres and the chunk loop of wae_solve_guess), for
 tests/test_gpu_solve_driver.py; tests/test_solveref.py checks it where no GPU is.
 
 GMRES gives the drivers an implementation-independent contract: after k steps from a zero guess the iterate minimises
@@ -8,7 +8,7 @@ tests/_mgref.py (the FULL cycle, which tests/test_gpu_multigrid.py pins the devi
 passes of modified Gram-Schmidt on normalised vectors and a QR least-squares solve of the Hessenberg problem.  No Givens recurrence,
 no unnormalised basis.  Columns never mix; a block of columns is handled side by side only to share the sparse products.
 
-The rules of the driver that the reference mirrors -- the contract under test (lines of csrc/lib.hip):
+The rules of the driver that the reference mirrors -- the contract under test (lines of csrc/gmres.hip):
 
   * Recurrence length (Gmres::m, "int m = min(150, h->V.n / vec - 1) - off", the basis holding (restart + 1) vectors of d x NB):
     m = min(150, floor((restart + 1) * NB / nb) - 1), NB the set-up's batch width (opts[6]), nb the width of the chunk, restart =

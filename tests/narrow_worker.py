@@ -1,5 +1,5 @@
 """Child process of tests/test_gpu_parity.py::test_pair_steps_of_the_narrow_recurrence: the two-pass Krylov recurrence of the narrow
-batches (<= 8 columns: the Newton-type solvers, csrc/lib.hip gmres) takes two Arnoldi steps per reading of the basis once a basis
+batches (<= 8 columns: the Newton-type solvers, csrc/gmres.hip gmres) takes two Arnoldi steps per reading of the basis once a basis
 vector is >= 4 MB (32 768 DoF at 8 columns); WAE_NARROW_PAIR (read once per process, hence this child) forces that form onto the
 8 736-DoF annulus, where a sparse LU is affordable, or switches it off.
 

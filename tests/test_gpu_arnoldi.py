@@ -1,4 +1,4 @@
-"""The shift-invert Arnoldi entries (csrc/lib.hip arnoldi_core behind wae_arnoldi_shiftinvert, wae_arnoldi_shiftinvert_batch,
+"""The shift-invert Arnoldi entries (csrc/arnoldi.hip arnoldi_core behind wae_arnoldi_shiftinvert, wae_arnoldi_shiftinvert_batch,
 wae_arnoldi_shiftinvert_slots, wae_arnoldi_ritz_to_slot) against the references of tests/_arnref.py, whose docstring states the contract
 (a) .. (f) with the lines of arnoldi_core it mirrors; tests/test_arnref.py shows where no GPU is that a clean replay of arnoldi_core meets
 it and that ten seeded defects do not.  The kernels underneath are pinned one by one elsewhere (test_gpu_vector_kernels,

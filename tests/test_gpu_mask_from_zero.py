@@ -1,4 +1,4 @@
-"""The device recurrence of the lock-step GMRES masks converged 8-column chunks in solves from a ZERO guess too (csrc/lib.hip
+"""The device recurrence of the lock-step GMRES masks converged 8-column chunks in solves from a ZERO guess too (csrc/gmres.hip
 run_device): a system that has finished is skipped by every kernel while the slower ones of its batch go on, and the update x += V y
 never reads the stale basis entries of its chunk (tests/test_gpu_zero_coef_skip.py).
 

@@ -904,7 +904,7 @@ print(json.dumps({"its": i["iters_total"], "unconv": i["n_unconverged"], "sum": 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = {}
     # "host": the recurrence (Hessenberg / Givens / flags) on the host with a synchronisation per iteration, as in round 1;
-    # the default keeps it on the device (gmres_wide) and looks at the status words every 4 iterations, "sync1" every iteration
+    # the default keeps it on the device (Gmres::run_device) and looks at the status words every 4 iterations, "sync1" every iteration
     for name, extra in (("default", {}), ("guard", {"WAE_LAZY_LIMIT": "3"}), ("explicit", {"WAE_LAZY": "0"}),
                         ("host", {"WAE_GMRES_DEVICE": "0"}), ("host_guard", {"WAE_GMRES_DEVICE": "0", "WAE_LAZY_LIMIT": "3"}),
                         ("sync1", {"WAE_GMRES_SYNC": "1"}),
@@ -1160,7 +1160,7 @@ def test_pair_steps_of_the_narrow_recurrence():
 def test_snapshot_basis_shortcuts_change_nothing_but_the_bytes():
     """The snapshot basis of the projected contour integral (wae_beyn_moments_rb) is extended with a block Gram-Schmidt update that
     reads the basis once for all new vectors, and the projected real symmetric terms take their new rows from their new columns
-    (csrc/lib.hip rb_append_block).  Both off (WAE_RB_MULTI_AXPY=0, WAE_RB_HERMITIAN=0; read once per process, hence the child
+    (csrc/beyn.hip rb_append_block).  Both off (WAE_RB_MULTI_AXPY=0, WAE_RB_HERMITIAN=0; read once per process, hence the child
     processes) must give the same moments and -- the basis only provides initial guesses -- the same iteration counts to 1 %."""
     import json
     import os

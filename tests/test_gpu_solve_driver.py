@@ -1,4 +1,4 @@
-"""The lock-step GMRES DRIVERS (csrc/lib.hip struct Gmres: run_device, run_host, start, cycle_start, finish, converged_by_estimate; the
+"""The lock-step GMRES DRIVERS (csrc/gmres.hip struct Gmres: run_device, run_host, start, cycle_start, finish, converged_by_estimate; the
 chunk loop of wae_solve_guess) against a reference preconditioned solve.  The kernels they launch are pinned one by one elsewhere
 (test_gpu_vector_kernels, test_gpu_gmres_recurrence, test_gpu_multigrid); this module holds what composes them: how long a cycle is,
 when it restarts, whether a pair step may still be taken before maxit, which columns are frozen, when a true residual is recomputed,

@@ -1,10 +1,12 @@
 // libwaehip.so -- wae_debug_vec (include/waehip.h, "test hook"): ONE launch_* call of wae_internal.h on the caller's host arrays, so
 // that tests/ can pin every streaming and reduction kernel to a reference of its own.  No family, no solver set-up.
 // wae_debug_gmres: a script of launch_gmres_* calls against one GmresDev, for the recurrence kernels of the lock-step GMRES.
+// wae_debug_spmv / _prolong / _vcycle: ONE operator product, prolongation or V-cycle (gmres.hip's own vcycle) of a family that has been set up.
+// wae_bench_spmv / _spmv_level / _triad: timed launches.
 #include <algorithm>
 #include <vector>
 
-#include "family.h"
+#include "solver.h"
 
 namespace {
 struct StreamGuard {
@@ -13,6 +15,27 @@ struct StreamGuard {
 };
 // entries spanned by nv vectors of blk entries each, `stride` apart
 int64_t span(int64_t nv, int64_t stride, int64_t blk) { return nv > 0 ? (nv - 1) * stride + blk : 0; }
+// the input of the timed launches: xorshift values in [-1, 1), the same on every call
+void fill_xorshift(std::vector<cplx> &hx) {
+    uint64_t s = 0x9E3779B97F4A7C15ull;
+    for (auto &v : hx) { s ^= s << 13; s ^= s >> 7; s ^= s << 17; v.x = (double)(s & 0xFFFFF) / 524288.0 - 1.0; v.y = (double)((s >> 20) & 0xFFFFF) / 524288.0 - 1.0; }
+}
+// milliseconds per call of one() on the stream: the mean over `reps` calls, after three that are not timed
+template <class F> double mean_ms(hipStream_t st, int reps, F &&one) {
+    for (int i = 0; i < 3; ++i) one();
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    HIP_CHECK(hipEventRecord(e0, st));
+    for (int i = 0; i < reps; ++i) one();
+    HIP_CHECK(hipEventRecord(e1, st));
+    HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return (double)ms / reps;
+}
 }   // namespace
 
 extern "C" int wae_debug_vec(int32_t device, int32_t op, const int64_t *sz, int32_t nsz, double *const *bufs, const int64_t *lens, int32_t nbuf,
@@ -237,7 +260,7 @@ extern "C" int wae_debug_gmres(int32_t device, int32_t nb, int32_t m, int32_t hi
         StreamGuard sg;
         HIP_CHECK(hipStreamCreate(&sg.s));
         hipStream_t st = sg.s;
-        // the state, laid out as lib.hip run_device lays it out (one integer block: conv, steps, iters, histlen, stalled, status)
+        // the state, laid out as gmres.hip run_device lays it out (one integer block: conv, steps, iters, histlen, stalled, status)
         const size_t nR = (size_t)m * (m + 1) * nb, nrow = (size_t)m * nb;
         DevBuf<cplx> dpool, R, sn, g, vsq, Hraw, rescale, dinv, s_rescale, s_vsq;
         DevBuf<double> cs, sv, sub, hist, relres, bn, s_relres, s_sv;
@@ -316,3 +339,291 @@ extern "C" int wae_debug_gmres(int32_t device, int32_t nb, int32_t m, int32_t hi
         return WAE_OK;
     });
 }
+
+extern "C" {
+
+int wae_bench_spmv(wae_family *h, const double *coeffs, int32_t r, int32_t reps, double *ms_out) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && coeffs && r > 0 && reps > 0 && ms_out, "bad argument");
+        HIP_CHECK(hipSetDevice(h->device));
+        hipStream_t st = h->stream;
+        const size_t cnt = (size_t)h->d * r;
+        DevBuf<cplx> x, y, pcd;
+        x.alloc(cnt); y.alloc(cnt);
+        std::vector<cplx> hx(cnt);
+        fill_xorshift(hx);
+        HIP_CHECK(hipMemcpyAsync(x.p, hx.data(), cnt * sizeof(cplx), hipMemcpyHostToDevice, st));
+        std::vector<zc> pc;
+        plane_coeffs(h, coeffs, WAE_OP_N, pc);
+        std::vector<cplx> tab((size_t)h->nplanes);                 // one system, all columns
+        slot_coeffs(h, h->slot_plane[0], pc, tab.data());
+        pcd.upload(tab.data(), tab.size(), st);
+        const OpDev A = h->ops[0].dev(WAE_OP_N);
+        // WAE_BENCH_MODE (diagnostic): the fused form timed -- 0 A X (default), 1 residual, 2 Jacobi sweep, 6 product + first sweep
+        const int bmode = getenv("WAE_BENCH_MODE") ? atoi(getenv("WAE_BENCH_MODE")) : MODE_AX;
+        DevBuf<cplx> bb;
+        if (bmode != MODE_AX) { bb.alloc(cnt); HIP_CHECK(hipMemcpyAsync(bb.p, hx.data(), cnt * sizeof(cplx), hipMemcpyHostToDevice, st)); }
+        auto one = [&]() { launch_spmv(A, pcd.p, 1 << 30, x.p, y.p, bmode != MODE_AX ? bb.p : nullptr, 0.8, r, bmode, st); };
+        *ms_out = mean_ms(st, reps, one);
+        return WAE_OK;
+    });
+}
+
+int wae_debug_spmv(wae_family *h, int32_t which, int32_t level, int32_t mode, const double *coeffs, int32_t ncoef, const double *X,
+                   const double *B, double *Y, double *B2, int32_t r, int32_t op, double jac_w, const uint8_t *cmask, int32_t flags,
+                   int64_t *n_in_q, int64_t *n_out_q) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && which >= 0 && which <= 2 && level >= 0 && op >= 0 && op <= 2, "bad argument");
+        WAE_REQUIRE(level == 0 || h->solver_ready, "levels >= 1 need wae_solver_setup");
+        // (the last level of a hierarchy is dense: it has no sparse operator to launch)
+        WAE_REQUIRE(which == 0 ? (level == 0 || level < (int)h->ops.size() - 1) : level < (int)h->xfer.size(), "no such level");
+        const int64_t n_in = which == 0 ? h->ops[level].n : (which == 1 ? h->xfer[level].nf : h->xfer[level].nc);
+        const int64_t n_out = which == 0 ? h->ops[level].n : (which == 1 ? h->xfer[level].nc : h->xfer[level].nf);
+        if (n_in_q) *n_in_q = n_in;
+        if (n_out_q) *n_out_q = n_out;
+        if (!X && !Y) return WAE_OK;                               // size query
+        WAE_REQUIRE(X && Y && r > 0 && r <= 256, "bad argument (1 <= r <= 256)");
+        WAE_REQUIRE(which != 0 || (coeffs && (ncoef == 1 || ncoef == r)), "ncoef must be 1 or r");
+        WAE_REQUIRE(mode >= MODE_AX && mode <= MODE_AX_J0 && (which == 0 || mode == (which == 1 ? MODE_AX : MODE_ADD)), "bad mode");
+        WAE_REQUIRE(B || mode == MODE_AX || mode == MODE_AX_DS || mode == MODE_AX_J0, "this mode reads B");
+        WAE_REQUIRE(mode != MODE_AX_J0 || B2, "mode 6 writes B2");
+        HIP_CHECK(hipSetDevice(h->device));
+        hipStream_t st = h->stream;
+        const int *perm = level == 0 && which != 1 ? h->perm() : nullptr;                 // (numbering of the OUTPUT rows: level 0 is the caller's)
+        const int *perm_in = level == 0 && which != 2 ? h->perm() : nullptr;
+        DevBuf<cplx> xc, yc, xi, yi, bi, pcd;
+        DevBuf<unsigned char> cm;
+        const size_t cin = (size_t)n_in * r, cout = (size_t)n_out * r;
+        xc.alloc(std::max(cin, cout)); yc.alloc(cout); xi.alloc(cin); yi.alloc(cout); bi.alloc(cout);
+        HIP_CHECK(hipMemcpyAsync(xc.p, X, cin * sizeof(cplx), hipMemcpyHostToDevice, st));
+        launch_colmajor_to_inter(xc.p, n_in, r, xi.p, r, st, perm_in);
+        auto stage = [&](const double *src, cplx *dst) {           // host column-major n_out x r -> interleaved on the device
+            HIP_CHECK(hipMemcpyAsync(yc.p, src, cout * sizeof(cplx), hipMemcpyHostToDevice, st));
+            launch_colmajor_to_inter(yc.p, n_out, r, dst, r, st, perm);
+        };
+        stage(Y, yi.p);                                             // a masked chunk keeps what Y held on entry
+        if (mode == MODE_AX_J0) stage(B2, bi.p);
+        else if (B) stage(B, bi.p);
+        if (cmask) cm.upload(cmask, (size_t)(r + 7) / 8, st);
+        OpDev A;
+        int cps = 1 << 30;
+        if (which == 0) {
+            std::vector<cplx> tab((size_t)ncoef * h->nplanes);
+            std::vector<zc> pc;
+            for (int s = 0; s < ncoef; ++s) {
+                plane_coeffs(h, coeffs + (size_t)s * 2 * h->T, op, pc);
+                slot_coeffs(h, h->slot_plane[level], pc, &tab[(size_t)s * h->nplanes]);
+            }
+            pcd.upload(tab.data(), tab.size(), st);
+            A = h->ops[level].dev(op);
+            cps = ncoef == 1 ? (1 << 30) : 1;
+        } else {
+            A = h->xfer[level].devR();
+        }
+        if (flags & 1) A.tiles = nullptr;
+        const Transfer *xf = which == 0 ? nullptr : &h->xfer[level];
+        const bool by_tile = xf && xf->ft.ready && !(flags & 1) && r >= 8;
+        if (which == 2) {                                           // Y = B + P X; B and Y the same array: in place.  A masked chunk keeps what Y held
+            const cplx *src = (const void *)B == (const void *)Y ? yi.p : bi.p;
+            if (by_tile) launch_prolong_tiles(xf->ft.dev, xi.p, src, yi.p, r, st, cmask ? cm.p : nullptr);
+            else launch_prolong_add(xf->p_ptr.p, xf->p_col.p, xf->p_val.p, xf->nf, xi.p, src, yi.p, r, st, cmask ? cm.p : nullptr);
+        } else
+        launch_spmv(A, which == 0 ? pcd.p : h->one_dev.p, cps, xi.p, yi.p, (mode == MODE_AX || mode == MODE_AX_DS) ? nullptr : bi.p, jac_w, r, mode, st,
+                    cmask ? cm.p : nullptr);
+        launch_inter_to_colmajor(yi.p, r, n_out, r, yc.p, st, perm);
+        HIP_CHECK(hipMemcpyAsync(Y, yc.p, cout * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        if (mode == MODE_AX_J0) {
+            HIP_CHECK(hipStreamSynchronize(st));
+            launch_inter_to_colmajor(bi.p, r, n_out, r, yc.p, st, perm);
+            HIP_CHECK(hipMemcpyAsync(B2, yc.p, cout * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        return WAE_OK;
+    });
+}
+
+// ONE launch of a prolongation kernel with its norm output (include/waehip.h)
+int wae_debug_prolong(wae_family *h, int32_t level, const double *X, const double *B, double *Y, double *norms, int32_t r, const uint8_t *cmask,
+                      int32_t flags) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && X && B && Y && norms, "bad argument");
+        require_solver(h);
+        WAE_REQUIRE(level >= 0 && level < (int)h->xfer.size(), "no such level");
+        WAE_REQUIRE(r >= 1 && r <= 256, "bad argument (1 <= r <= 256)");
+        WAE_REQUIRE(flags >= 0 && flags < 4, "unknown flag");
+        const Transfer *xf = &h->xfer[level];
+        const int64_t nc = xf->nc, nf = xf->nf;
+        HIP_CHECK(hipSetDevice(h->device));
+        hipStream_t st = h->stream;
+        const int *perm = level == 0 ? h->perm() : nullptr;       // level 0 is in the caller's row numbering
+        const size_t cin = (size_t)nc * r, cout = (size_t)nf * r;
+        const bool by_tile = xf->ft.ready && !(flags & 1) && r >= 8;
+        DevBuf<cplx> xc, yc, xi, yi, bi, part, nrm;
+        DevBuf<unsigned char> cm;
+        xc.alloc(cin); yc.alloc(cout); xi.alloc(cin); yi.alloc(cout); bi.alloc(cout); nrm.alloc((size_t)r);
+        part.alloc((size_t)(by_tile ? xf->ft.dev.ntiles : PROLONG_NORM_BLOCKS) * r);
+        HIP_CHECK(hipMemcpyAsync(xc.p, X, cin * sizeof(cplx), hipMemcpyHostToDevice, st));
+        launch_colmajor_to_inter(xc.p, nc, r, xi.p, r, st, nullptr);
+        HIP_CHECK(hipMemcpyAsync(yc.p, Y, cout * sizeof(cplx), hipMemcpyHostToDevice, st));
+        launch_colmajor_to_inter(yc.p, nf, r, yi.p, r, st, perm);
+        HIP_CHECK(hipStreamSynchronize(st));                       // (yc is staged twice)
+        HIP_CHECK(hipMemcpyAsync(yc.p, B, cout * sizeof(cplx), hipMemcpyHostToDevice, st));
+        launch_colmajor_to_inter(yc.p, nf, r, bi.p, r, st, perm);
+        if (cmask) cm.upload(cmask, (size_t)(r + 7) / 8, st);
+        cplx *const dst = (flags & 2) ? nullptr : yi.p;
+        if (by_tile) launch_prolong_tiles(xf->ft.dev, xi.p, bi.p, dst, r, st, cmask ? cm.p : nullptr, part.p, nrm.p);
+        else launch_prolong_add(xf->p_ptr.p, xf->p_col.p, xf->p_val.p, nf, xi.p, bi.p, dst, r, st, cmask ? cm.p : nullptr, part.p, nrm.p);
+        launch_inter_to_colmajor(yi.p, r, nf, r, yc.p, st, perm);
+        HIP_CHECK(hipMemcpyAsync(Y, yc.p, cout * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        std::vector<cplx> hn((size_t)r);
+        HIP_CHECK(hipMemcpyAsync(hn.data(), nrm.p, (size_t)r * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (int b = 0; b < r; ++b) norms[b] = hn[(size_t)b].x;
+        return WAE_OK;
+    });
+}
+
+// ONE application of vcycle() -- the solver's own, not a copy -- from `level` down, on the handle's workspaces (include/waehip.h)
+int wae_debug_vcycle(wae_family *h, int32_t level, const double *coeffs, int32_t ncoef, const double *B, double *Y, int32_t r, int32_t op,
+                     int32_t flags, const uint8_t *cmask) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && coeffs && B && Y, "bad argument");
+        require_solver(h);
+        const int L = (int)h->ops.size() - 1;
+        WAE_REQUIRE(level >= 0 && level <= L, "no such level");
+        WAE_REQUIRE(r >= 1 && r <= h->NB, "r must be in 1..NB (opts[6] of wae_solver_setup)");
+        WAE_REQUIRE(ncoef == 1 || ncoef == r, "ncoef must be 1 or r");
+        WAE_REQUIRE(op >= 0 && op <= 2, "bad op");
+        WAE_REQUIRE(flags >= 0 && flags < 8, "unknown flag");
+        WAE_REQUIRE(!(flags & 4) || level == 0, "flags bit 2 (Y = M^-1 A V) needs level 0");
+        HIP_CHECK(hipSetDevice(h->device));
+        hipStream_t st = h->stream;
+        struct LightRestore { bool &on; bool was; ~LightRestore() { on = was; } } light_restore{h->vc_light, h->vc_light};
+        h->vc_light = (flags & 1) != 0;
+        const Batch bt = ncoef == 1 ? Batch::one_system(r, op) : Batch::per_column(r, op);   // the batch and the plane tables as wae_solve_guess builds them
+        std::vector<std::vector<zc>> pcs((size_t)bt.nsys);
+        for (int s = 0; s < bt.nsys; ++s) plane_coeffs(h, coeffs + (size_t)s * 2 * h->T, op, pcs[(size_t)s]);
+        upload_pc(h, pcs);
+        dense_setup(h, bt);
+        const int64_t n = h->ops[level].n;
+        const size_t cnt = (size_t)n * r;
+        const int *perm = level == 0 ? h->perm() : nullptr;       // level 0 is in the caller's row numbering
+        DevBuf<cplx> col, vin, fout;
+        DevBuf<unsigned char> cm;
+        col.alloc(cnt);
+        if (cmask) cm.upload(cmask, (size_t)(r + 7) / 8, st);
+        const unsigned char *mk = (cmask && r >= 8) ? cm.p : nullptr;   // (narrower batches run unmasked in the solver)
+        // what a masked chunk holds on return is what every buffer the cycle may return held before it: the caller's Y
+        cplx *x = h->lx[level].p;
+        HIP_CHECK(hipMemcpyAsync(col.p, Y, cnt * sizeof(cplx), hipMemcpyHostToDevice, st));
+        launch_colmajor_to_inter(col.p, n, r, x, r, st, perm);
+        launch_copy(x, h->lt[level].p, cnt, st);
+        if (flags & 2) { fout.alloc(cnt); launch_copy(x, fout.p, cnt, st); }
+        cplx *b = level == 0 ? h->W.p : h->lb[level].p;            // the right-hand side where the solver keeps it
+        HIP_CHECK(hipMemcpyAsync(col.p, B, cnt * sizeof(cplx), hipMemcpyHostToDevice, st));
+        bool have_x0 = false;
+        if (flags & 4) {                                            // one Krylov step's product and cycle: B is V, b = A V
+            vin.alloc(cnt);
+            launch_colmajor_to_inter(col.p, n, r, vin.p, r, st, perm);
+            have_x0 = L > 0;
+            launch_spmv(h->ops[0].dev(op), pc_level(h, 0), bt.cps, vin.p, b, have_x0 ? x : nullptr, have_x0 ? pre_weight(h) : 0.0, r,
+                        have_x0 ? MODE_AX_J0 : MODE_AX, st, mk);
+        } else {
+            launch_colmajor_to_inter(col.p, n, r, b, r, st, perm);
+        }
+        const cplx *res = vcycle(h, bt, level, b, mk, have_x0, (flags & 2) ? fout.p : nullptr);
+        launch_inter_to_colmajor(res, r, n, r, col.p, st, perm);
+        HIP_CHECK(hipMemcpyAsync(Y, col.p, cnt * sizeof(cplx), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return WAE_OK;
+    });
+}
+
+int wae_bench_spmv_level(wae_family *h, const double *coeffs, int32_t which, int32_t level, int32_t r, int32_t reps, double *ms_out,
+                         int64_t *bytes_out) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && coeffs && which >= 0 && which <= 2 && level >= 0 && r > 0 && r <= 256 && reps > 0 && ms_out, "bad argument");
+        require_solver(h);
+        WAE_REQUIRE(which == 0 ? (level == 0 || level < (int)h->ops.size() - 1) : level < (int)h->xfer.size(), "no such level");
+        HIP_CHECK(hipSetDevice(h->device));
+        hipStream_t st = h->stream;
+        const int64_t n_in = which == 0 ? h->ops[level].n : (which == 1 ? h->xfer[level].nf : h->xfer[level].nc);
+        const int64_t n_out = which == 0 ? h->ops[level].n : (which == 1 ? h->xfer[level].nc : h->xfer[level].nf);
+        DevBuf<cplx> x, y, pcd;
+        x.alloc((size_t)n_in * r); y.alloc((size_t)n_out * r);
+        std::vector<cplx> hx((size_t)n_in * r);
+        fill_xorshift(hx);
+        HIP_CHECK(hipMemcpyAsync(x.p, hx.data(), hx.size() * sizeof(cplx), hipMemcpyHostToDevice, st));
+        OpDev A;
+        const cplx *pcp = h->one_dev.p;
+        int64_t bytes = 2;
+        if (which == 0) {
+            std::vector<zc> pc;
+            plane_coeffs(h, coeffs, WAE_OP_N, pc);
+            std::vector<cplx> tab(h->nplanes);
+            slot_coeffs(h, h->slot_plane[level], pc, tab.data());
+            pcd.upload(tab.data(), tab.size(), st);
+            pcp = pcd.p;
+            A = h->ops[level].dev(WAE_OP_N);
+            bytes = 0;
+            for (size_t g = 0; g < h->ops[level].groups.size(); ++g) {
+                const GroupHost &G = h->ops[level].groups[g];
+                for (int q = 0; q < G.nplanes; ++q)
+                    if (tab[G.plane0 + q].x != 0.0 || tab[G.plane0 + q].y != 0.0) bytes += G.nnz * 20 + (n_out + 1) * 4;
+            }
+        } else {
+            A = h->xfer[level].devR();
+            bytes = (int64_t)h->xfer[level].r_col.n * 12 + (n_out + 1) * 4;       // real values: 8 + 4 bytes per entry
+        }
+        bytes += (int64_t)r * (n_in + n_out) * 16;
+        if (which == 2) bytes += (int64_t)r * n_out * 16;          // (the prolongation updates the fine vector in place: read + write)
+        if (bytes_out) *bytes_out = bytes;
+        const Transfer *xf = which == 0 ? nullptr : &h->xfer[level];
+        const bool by_tile = xf && xf->ft.ready && r >= 8 && xfer_tiles_on();
+        auto one = [&]() {
+            if (which == 2) {
+                if (by_tile) launch_prolong_tiles(xf->ft.dev, x.p, y.p, y.p, r, st);
+                else launch_prolong_add(xf->p_ptr.p, xf->p_col.p, xf->p_val.p, xf->nf, x.p, y.p, y.p, r, st, nullptr);
+            } else launch_spmv(A, pcp, 1 << 30, x.p, y.p, nullptr, 0.0, r, MODE_AX, st);
+        };
+        if (which == 2) HIP_CHECK(hipMemsetAsync(y.p, 0, (size_t)n_out * r * sizeof(cplx), st));
+        *ms_out = mean_ms(st, reps, one);
+        return WAE_OK;
+    });
+}
+
+int wae_bench_triad(int32_t device, int64_t n, int32_t reps, double *gbs_out) {
+    return guarded([&]() {
+        WAE_REQUIRE(n > 0 && reps > 0 && gbs_out, "bad argument");
+        HIP_CHECK(hipSetDevice(device));
+        DevBuf<double> a, b, c;
+        a.alloc(n); b.alloc(n); c.alloc(n);
+        HIP_CHECK(hipMemset(b.p, 0, n * sizeof(double)));
+        HIP_CHECK(hipMemset(c.p, 0, n * sizeof(double)));
+        hipStream_t st;
+        HIP_CHECK(hipStreamCreate(&st));
+        // The rate depends on the shape of the launch (measured, round 4: 4.6 ... 5.7 TB/s between 256 and 65 536 workgroups on one
+        // box; the 8 192 this probe used until then sits at the low end): the best of five grid sizes is what the device attains.
+        hipEvent_t e0, e1;
+        HIP_CHECK(hipEventCreate(&e0));
+        HIP_CHECK(hipEventCreate(&e1));
+        double best = 0.0;
+        for (unsigned cap : {512u, 1024u, 4096u, 8192u, 65536u}) {
+            for (int i = 0; i < 2; ++i) launch_triad(a.p, b.p, c.p, 1.5, n, st, cap);
+            HIP_CHECK(hipEventRecord(e0, st));
+            for (int i = 0; i < reps; ++i) launch_triad(a.p, b.p, c.p, 1.5, n, st, cap);
+            HIP_CHECK(hipEventRecord(e1, st));
+            HIP_CHECK(hipEventSynchronize(e1));
+            float ms = 0.f;
+            HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+            best = std::max(best, 3.0 * n * sizeof(double) * reps / (ms * 1e-3) / 1e9);
+        }
+        *gbs_out = best;
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        (void)hipStreamDestroy(st);
+        return WAE_OK;
+    });
+}
+
+}   // extern "C"

@@ -1,5 +1,6 @@
-// The family handle and the few helpers that lib.hip (solvers, C ABI) and setup.hip (construction of the handle and of the
-// multigrid hierarchy) share.  Private to those two files: mgpu.hip goes through the C ABI and wae_internal_device / _stream.
+// The family handle and the few helpers that setup.hip (construction of the handle and of the multigrid hierarchy), lib.hip (operator
+// products, C ABI) and the solver units (solver.h) share.  Private to those files: mgpu.hip goes through the C ABI and
+// wae_internal_device / _stream.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -58,7 +59,7 @@ struct wae_family {
     RbState rb;                      // the snapshot basis and its projected terms
     DevBuf<int> plane_col_dev;
     DevBuf<unsigned char> cmask;     // one byte per 8-column chunk of the current batch (0 = converged)
-    // device-resident recurrence of the wide-batch GMRES (gmres_wide)
+    // device-resident recurrence of the wide-batch GMRES (Gmres::run_device)
     DevBuf<cplx> gs_R, gs_sn, gs_g, gs_rescale, gs_Hraw, gs_pair;
     DevBuf<double> gs_sub;
     DevBuf<double> gs_cs, gs_sv, gs_relres, gs_bnorm, gs_hist;
@@ -98,6 +99,8 @@ struct Batch {
     int cps;    // columns per system
     int nsys;
     int op;
+    static Batch one_system(int nb, int op) { return Batch{nb, nb, 1, op}; }       // one coefficient set for all columns
+    static Batch per_column(int nb, int op) { return Batch{nb, 1, nb, op}; }       // one system (coefficient set) per column
 };
 
 // ----------------------------------------------------------------------------------------------------
@@ -116,6 +119,10 @@ static void plane_coeffs(const wae_family *h, const double *coeffs, int op, std:
     for (int k = 0; k < h->T; ++k) pc[h->term_plane[k]] += h->term_scale[k] * zc(coeffs[2 * k], coeffs[2 * k + 1]);
     if (op == WAE_OP_C)
         for (auto &c : pc) c = std::conj(c);
+}
+// dst[q] = pc[slot_plane[q]]: the nplanes coefficients of one system in the slot order of a level (h->slot_plane[level]) or of a penalty block
+static void slot_coeffs(const wae_family *h, const std::vector<int> &slot_plane, const std::vector<zc> &pc, cplx *dst) {
+    for (int q = 0; q < h->nplanes; ++q) dst[q] = cplx{pc[slot_plane[q]].real(), pc[slot_plane[q]].imag()};
 }
 
 template <class F> static int guarded(F &&f) {

@@ -1537,7 +1537,7 @@ void launch_prolong_tiles(const XferTilesDev &T, const cplx *Xc, const cplx *X, 
     launch_reduce_partials(partial, T.ntiles, nb, norms, 1, st);
 }
 
-// compact <-> full row sets (penalty-block polish, lib.hip): out[i][b] = X[rows[i]][b];  X[rows[i]][b] += D[i][b]
+// compact <-> full row sets (penalty-block polish, gmres.hip): out[i][b] = X[rows[i]][b];  X[rows[i]][b] += D[i][b]
 __global__ __launch_bounds__(256) void gather_rows_kernel(const cplx *__restrict__ X, const int *__restrict__ rows, size_t total, int nb,
                                                           cplx *__restrict__ out) {
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {

@@ -1,6 +1,6 @@
 // libwaehip.so -- construction: the family handle from the caller's term matrices (wae_family_create_opts) and the multigrid
 // hierarchy with its work spaces (wae_solver_setup, and wae_solver_setup_nested from prolongators the caller supplies).  Host code and
-// uploads only, but for the Galerkin products of the supplied levels (galerkin.hip); the solvers that use what is built here are in lib.hip.
+// uploads only, but for the Galerkin products of the supplied levels (galerkin.hip); the solvers that use what is built here: solver.h.
 #include <atomic>
 #include <cmath>
 #include <exception>

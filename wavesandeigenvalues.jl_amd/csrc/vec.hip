@@ -142,7 +142,7 @@ static void dots_impl(const cplx *V, size_t stride, int nv, const cplx *W, int64
     }
 }
 // block version: partial[blk][i*nw + j][b] = sum over this block's rows of conj(V_i[row][b]) W_j[row][b], j < nw <= NW.
-// Reads V once for NW right-hand vectors (the projected-operator build of the snapshot basis, lib.hip rb_append, is a
+// Reads V once for NW right-hand vectors (the projected-operator build of the snapshot basis, beyn.hip rb_append, is a
 // tall-skinny Gram product: with one w per launch it re-read the whole basis for every new column).
 template <int MAXV, int NW>
 __global__ __launch_bounds__(256) void dots_multi_kernel(const cplx *__restrict__ V, size_t sv, int nv, const cplx *__restrict__ W, size_t sw, int nw,
@@ -325,7 +325,7 @@ void launch_axpy_neg(const cplx *V, size_t stride, int nv, const cplx *h, cplx *
     axpy_impl(V, stride, nv, h, W, n, nb, -1.0, W, st, cmask);
 }
 // W_j -= sum_i h[i][j] V_i for CNT vectors W_j (stride wstride) in ONE reading of V_0..nv-1: the block Gram-Schmidt update of the
-// snapshot basis (lib.hip rb_append_block), whose four new vectors used to read the basis once each.  h[(i*CNT + j)*nb + b], the
+// snapshot basis (beyn.hip rb_append_block), whose four new vectors used to read the basis once each.  h[(i*CNT + j)*nb + b], the
 // layout dots_multi writes.
 template <int CNT>
 __global__ __launch_bounds__(256) void axpy_neg_multi_kernel(const cplx *__restrict__ V, size_t stride, int nv, const cplx *__restrict__ h, cplx *W,
@@ -373,7 +373,7 @@ void launch_axpy_neg_multi(const cplx *V, size_t stride, int nv, const cplx *h, 
 }
 // w -= V h and norms[b] = ||w[:,b]|| in one pass over w (falls back to two kernels when the coefficients do not fit one launch)
 // base (optional): W = base - V h instead of the in-place update; inv_out (optional): 1/||W[:,b]||^2 beside the norms.  Both are
-// what a Krylov basis kept UNNORMALISED needs (lib.hip gmres): the new vector goes straight into its basis slot.
+// what a Krylov basis kept UNNORMALISED needs (gmres.hip gmres): the new vector goes straight into its basis slot.
 void launch_axpy_neg_norm(const cplx *V, size_t stride, int nv, const cplx *h, cplx *W, int64_t n, int nb, cplx *partial, cplx *norms,
                           hipStream_t st, const unsigned char *cmask, const cplx *base, cplx *inv_out) {
     if (!n || nb < 1) return;
@@ -392,7 +392,7 @@ void launch_axpy_neg_norm(const cplx *V, size_t stride, int nv, const cplx *h, c
     launch_reduce_partials(partial, (int)grid, nb, norms, 1, st, nullptr, inv_out);
 }
 // ---------------------------------------------------------------------------------------------------
-// Two Arnoldi steps per pass over the basis (lib.hip gmres_wide, "pair" steps).  With w1 = Op v_j and w2 = Op w1 -- the operator
+// Two Arnoldi steps per pass over the basis (gmres.hip Gmres::run_device, "pair" steps).  With w1 = Op v_j and w2 = Op w1 -- the operator
 // applied to the vector BEFORE it is orthogonalised -- both new basis vectors come out of ONE reading of V_0..j for the inner
 // products and ONE for the update, where two single steps read it four times: the Gram-Schmidt traffic of a long recurrence, the
 // largest stream of a from-zero solve, halves.
@@ -568,7 +568,7 @@ void launch_lincomb_add(const cplx *V, size_t stride, int nv, const cplx *y, cpl
 }
 
 // ---------------------------------------------------------------------------------------------------
-// snapshot-basis helpers (Galerkin initial guesses for the shifted systems of a contour, lib.hip: beyn_moments_rb)
+// snapshot-basis helpers (Galerkin initial guesses for the shifted systems of a contour, beyn.hip: beyn_moments_rb)
 // ---------------------------------------------------------------------------------------------------
 // out[row][c] = X[row][off + c], c < l   (one system's l columns out of a lock-step batch of nb columns)
 __global__ __launch_bounds__(256) void extract_cols_kernel(const cplx *__restrict__ X, int nb, int off, int l, cplx *__restrict__ out, size_t total) {
@@ -855,7 +855,7 @@ void launch_beyn_accum(const cplx *Xi, int nb, int64_t d, int l, int nsys, const
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The small-matrix half of the lock-step GMRES on the device (lib.hip gmres_wide): one thread per column keeps that column's
+// The small-matrix half of the lock-step GMRES on the device (gmres.hip Gmres::run_device): one thread per column keeps that column's
 // Hessenberg column, Givens rotations, residual estimate and convergence flags in HBM, so that no iteration ends in a
 // device-to-host copy + stream synchronisation (round 1: 51 us of host turnaround per lock-step iteration).  The arithmetic is
 // the host loop's, statement for statement (same rotations, same tests), hence the same iterates.
@@ -887,7 +887,7 @@ __global__ __launch_bounds__(256) void gmres_init_kernel(GmresDev S, const cplx 
 }
 
 // after Arnoldi step j: hd[i][b], i <= j: s_i^2-scaled dots of the new vector against the unnormalised basis; hd[j+1][b].x: norm of
-// the orthogonalised vector (lib.hip: "lazy" basis).  Produces the Hessenberg column of the normalised recurrence, rotates it,
+// the orthogonalised vector (gmres.hip: "lazy" basis).  Produces the Hessenberg column of the normalised recurrence, rotates it,
 // updates g, the residual estimate and the flags; marks vectors whose running scale left [1/lim, lim] for renormalisation.
 __global__ __launch_bounds__(256) void gmres_step_kernel(GmresDev S, const cplx *__restrict__ hd, int j, double tol, double lim, int use_mask,
                                                          const cplx *__restrict__ rn) {
@@ -1092,7 +1092,7 @@ void launch_triad(double *a, const double *b, const double *c, double s_, int64_
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Batched adjoint perturbation (lib.hip perturb_batch_core): nb eigenpairs expanded in lock-step.  Every vector of the batch is
+// Batched adjoint perturbation (perturb.hip perturb_batch_core): nb eigenpairs expanded in lock-step.  Every vector of the batch is
 // interleaved [row][system] like the solver's multivectors; the input columns of the regrouped recurrence are U[row][t][system].
 // ---------------------------------------------------------------------------------------------------
 // U[row][t0 + t][b] (+)= sum_{i<k} G[i][t0 + t][b] * V_i[row][b],  t < tn <= TMAX;  V_i = V + i*stride, G: [k][T][nb].

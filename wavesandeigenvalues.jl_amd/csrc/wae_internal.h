@@ -149,6 +149,7 @@ template <class T> struct DevBuf {
         n = count;
         if (count) HIP_CHECK(hipMalloc((void **)&p, count * sizeof(T)));
     }
+    void reserve(size_t count) { if (n < count) alloc(count); }      // grows only; the contents are not kept
     void upload(const T *h, size_t count, hipStream_t s) {
         if (count > n) alloc(count);
         if (count) HIP_CHECK(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s));
