@@ -428,6 +428,11 @@ int wae_p2_connectivity(int32_t device, int64_t npoints, int64_t ntets, const in
 int wae_p2_connectivity_info(const void *handle, int64_t *nedges, int64_t *ntets, int64_t *ntris);
 int wae_p2_connectivity_get(const void *handle, int32_t *edges, int32_t *tets10, int32_t *tris6);
 int wae_p2_connectivity_free(void *handle);
+/* The embedding of the P1 space of the mesh into its P2 space (a P1 function at the P2 nodes; the coarse space of p-coarsening, a
+ * prolongator wae_solver_setup_nested takes) as a CSR matrix, built by a kernel from the handle's edge list: npoints + nedges rows,
+ * npoints columns, npoints + 2 nedges entries (ptr: rows + 1; 0-based); the row of point a holds (a, 1.0), the row of edge (a, b), a < b,
+ * holds (a, 0.5) (b, 0.5).  WAE_ERR_INVALID, nothing written: a NULL pointer, or npoints other than the handle's. */
+int wae_p2_embedding(const void *handle, int64_t npoints, int32_t *ptr, int32_t *col, double *val);
 /* The three operators on the P2 space, basis phi_i = l_i (2 l_i - 1) on the points and phi_ij = 4 l_i l_j on the edges (l:
  * barycentric coordinates), node order and numbering as above.  Each entry takes the plain mesh, numbers the edges itself and
  * returns the handle type of the P1 entries (wae_p1_info / wae_p1_get / wae_p1_free) with npoints + nedges rows; same pipeline:
@@ -446,7 +451,7 @@ int wae_p2_assemble_boundary(int32_t device, int64_t npoints, const double *poin
 int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t nflame,
                           const int32_t *flame_tets, int32_t ref_tet, const double *x_ref, const double *n_ref, double nglobal_scaled, void **out,
                           double *volume_out);
-/* -- uniform mesh refinement on the device: `octosplit(mesh)` with the nested P1 prolongation ---------------------------
+/* -- uniform mesh refinement on the device: `octosplit(mesh)` with the nested P1 and P2 prolongations ------------------
  * Every tetrahedron is split into 8 and every boundary triangle into 4 (src/Meshutils.jl:589-747); the handle keeps `levels`
  * successive refinements in HBM, level 0 being the input.  points: 3 doubles per point, tets: 4 point indices (0-based) per
  * tetrahedron, tris: 3 per boundary triangle (ntris may be 0, tris NULL).  One level, index for index what the reference returns:
@@ -483,8 +488,25 @@ int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points,
  * WAE_ERR_INVALID, nothing returned and nothing truncated: an index outside 0..npoints-1, a triangle edge that is no tetrahedron's
  * edge, two equal children after the sort (a simplex listed twice or repeating a point), levels < 1, or a level whose point,
  * tetrahedron or triangle count passes a 32-bit index.
+ * P2 prolongation.  The P2 unknowns of a level are those of wae_p2_assemble on its mesh: the points, then the edges ascending by (smaller
+ * point, larger point).  The step level -> level + 1 evaluates the coarse basis (l_i (2 l_i - 1), 4 l_i l_j) at the fine unknowns: a real
+ * CSR matrix with ndof(level + 1) rows and ndof(level) columns, five kinds of row with exact weights, every row summing to 1:
+ *      old point a                                 (a, 1)
+ *      new point, midpoint of the coarse edge AB   (edge AB, 1)
+ *      fine edge (A, AB)                           (A, 3/8) (B, -1/8) (edge AB, 3/4)
+ *      fine edge (AB, AC)                          (B, -1/8) (C, -1/8) (edge AB, 1/2) (edge AC, 1/2) (edge BC, 1/4)
+ *      fine edge (AB, CD), an inner diagonal       the four points -1/8, the six edges among them 1/4
+ * columns ascending.  The first of the three P2 entries called on a handle numbers the edges of every level on the device (keys, sort and
+ * unique pass of wae_p2_connectivity) and builds every step in HBM (row lengths by kind, an exclusive scan, one thread per row; binary
+ * searches in the coarse edge list, no atomics); a handle that never sees one pays nothing.
+ * wae_octosplit_p2_info: nedges and ndof = npoints + nedges of a level, prolongator_nnz of the step level -> level + 1 (0 for the last
+ * level); any pointer may be NULL.  wae_octosplit_prolongator_p2 copies the step from_level -> from_level + 1 out (ptr: ndof(from_level +
+ * 1) + 1, col and val: prolongator_nnz; 0-based), in the form wae_solver_setup_nested takes.  wae_octosplit_prolong_p2 applies the same
+ * arrays, level by level, to ncols complex columns (X: ndof(from_level) x ncols column-major, interleaved re/im; Y: ndof(to_level) x
+ * ncols); one kernel per level, the intermediate levels stay in HBM.  WAE_ERR_INVALID, nothing written: a level out of range, from_level
+ * >= to_level, ncols < 1, a NULL pointer, or a level whose unknowns or whose step's entries pass a 32-bit index.
  * Out of scope: meshes with a degree of symmetry (the point classes of a Bloch unit cell do not survive appended points; the reference
- * drops `dos` too), interior-triangle lists (a TODO in the reference, Meshutils.jl:656-668), and P2 or Hermite prolongation. */
+ * drops `dos` too), interior-triangle lists (a TODO in the reference, Meshutils.jl:656-668), and Hermite prolongation. */
 int wae_octosplit(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris,
                   int32_t levels, void **out);
 int wae_octosplit_info(const void *handle, int32_t level, int64_t *npoints, int64_t *ntets, int64_t *ntris);
@@ -492,6 +514,9 @@ int wae_octosplit_get(const void *handle, int32_t level, double *points, int32_t
                       int32_t *tri_labels);
 int wae_octosplit_prolong(const void *handle, int32_t from_level, int32_t to_level, int32_t ncols, const double *X, double *Y);
 int wae_octosplit_prolongator(const void *handle, int32_t from_level, int32_t *ptr, int32_t *col, double *val);
+int wae_octosplit_p2_info(void *handle, int32_t level, int64_t *nedges, int64_t *ndof, int64_t *prolongator_nnz);
+int wae_octosplit_prolongator_p2(void *handle, int32_t from_level, int32_t *ptr, int32_t *col, double *val);
+int wae_octosplit_prolong_p2(void *handle, int32_t from_level, int32_t to_level, int32_t ncols, const double *X, double *Y);
 int wae_octosplit_free(void *handle);
 /* -- Bloch unit cells with P1 or P2 elements: cell numbering and operator fold on the device ------------------------
  * `discretize(mesh, dscrp, C; order, b=:b)` on a mesh with a degree of symmetry: blochify (src/Bloch.jl:4-112), the dimension of

@@ -1438,10 +1438,10 @@ function assemble_p1_flame(points::Matrix{Float64}, tets::AbstractMatrix{<:Integ
     return _take_p1(h[], false), vol[]
 end
 
-# Uniform mesh refinement on the device: `octosplit(mesh)` (Meshutils.jl:589-747) and the nested P1 prolongation between its levels
-# (include/waehip.h, wae_octosplit*).  Out of scope, as there: meshes with a degree of symmetry, interior-triangle lists, P2 or Hermite
-# prolongation.  `prolongator` returns a step of the prolongation as a sparse matrix, `solver_setup_nested` builds a family's multigrid
-# hierarchy from such matrices.
+# Uniform mesh refinement on the device: `octosplit(mesh)` (Meshutils.jl:589-747) and the nested P1 and P2 prolongations between its levels
+# (include/waehip.h, wae_octosplit*; `order=:quad` selects the P2 space of assemble_p2).  Out of scope, as there: meshes with a degree of
+# symmetry, interior-triangle lists, Hermite prolongation.  `prolongator` returns a step of the prolongation as a sparse matrix,
+# `p2_embedding` the P1 -> P2 embedding of one mesh, `solver_setup_nested` builds a family's multigrid hierarchy from such matrices.
 "the levels 0..levels of one `octosplit_device` call, kept in HBM (level 0 = the input); `npoints[l + 1]` points on level l"
 mutable struct Refinement
     handle::Ptr{Cvoid}
@@ -1510,30 +1510,83 @@ function octosplit_device(mesh; levels::Integer=1, device::Integer=0)
     return new_mesh, ref
 end
 
-"Y = prolong(ref, X; from=0, to=ref.levels): the nested P1 embedding of level `from` into level `to` on the device -- old points keep their
-value, a new point gets the mean of the two ends of its edge, level by level.  X: a vector or a matrix with one row per point of level
+"ndof(ref, level; order=:lin): the unknowns of a level -- its points (:lin), or its points and edges (:quad, the size of assemble_p2)"
+function ndof(ref::Refinement, level::Integer; order::Symbol=:lin)
+    order in (:lin, :quad) || throw(ArgumentError("order must be :lin or :quad, got $order"))
+    0 <= level <= ref.levels || throw(ArgumentError("level outside 0..$(ref.levels)"))
+    order == :lin && return ref.npoints[level + 1]
+    return _p2_info(ref, level)[2]
+end
+
+"(nedges, ndof, prolongator_nnz) of a level's P2 space (wae_octosplit_p2_info)"
+function _p2_info(ref::Refinement, level::Integer)
+    ne = Ref{Int64}(0); nd = Ref{Int64}(0); nz = Ref{Int64}(0)
+    check(ccall((:wae_octosplit_p2_info, libwaehip), Cint, (Ptr{Cvoid}, Int32, Ref{Int64}, Ref{Int64}, Ref{Int64}), ref.handle, level, ne, nd, nz))
+    return Int(ne[]), Int(nd[]), Int(nz[])
+end
+
+"Y = prolong(ref, X; from=0, to=ref.levels, order=:lin): the nested embedding of level `from` into level `to` on the device, level by
+level.  order=:lin: old points keep their value, a new point gets the mean of the two ends of its edge.  order=:quad: the P2 function with
+the coefficients X in the P2 basis of level `to` (wae_octosplit_prolong_p2).  X: a vector or a matrix with one row per unknown of level
 `from`, real or complex; Y has the shape and the realness of X."
-function prolong(ref::Refinement, X::AbstractVecOrMat{<:Number}; from::Integer=0, to::Integer=ref.levels)
+function prolong(ref::Refinement, X::AbstractVecOrMat{<:Number}; from::Integer=0, to::Integer=ref.levels, order::Symbol=:lin)
+    order in (:lin, :quad) || throw(ArgumentError("order must be :lin or :quad, got $order"))
     0 <= from < to <= ref.levels || throw(ArgumentError("prolong needs 0 <= from < to <= $(ref.levels), got $from and $to"))
-    size(X, 1) == ref.npoints[from + 1] || throw(ArgumentError("X has $(size(X, 1)) rows, level $from has $(ref.npoints[from + 1]) points"))
+    nin, nout = ndof(ref, from; order=order), ndof(ref, to; order=order)
+    size(X, 1) == nin || throw(ArgumentError("X has $(size(X, 1)) rows, level $from has $nin unknowns"))
     Xc = Matrix{ComplexF64}(reshape(X, size(X, 1), :))
-    Y = zeros(ComplexF64, ref.npoints[to + 1], size(Xc, 2))
-    check(ccall((:wae_octosplit_prolong, libwaehip), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}),
-                ref.handle, from, to, size(Xc, 2), Xc, Y))
+    Y = zeros(ComplexF64, nout, size(Xc, 2))
+    if order == :quad
+        check(ccall((:wae_octosplit_prolong_p2, libwaehip), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                    ref.handle, from, to, size(Xc, 2), Xc, Y))
+    else
+        check(ccall((:wae_octosplit_prolong, libwaehip), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                    ref.handle, from, to, size(Xc, 2), Xc, Y))
+    end
     Yr = eltype(X) <: Real ? real.(Y) : Y
     return X isa AbstractVector ? vec(Yr) : Yr
 end
 
-"P = prolongator(ref; from=0): the step `from` -> `from + 1` of the nested P1 embedding as a SparseMatrixCSC (points of level from + 1 x
-points of level from), built on the device from the parents table: an old point's row holds 1, a new point's row 0.5 at its two parents."
-function prolongator(ref::Refinement; from::Integer=0)
+"P = prolongator(ref; from=0, order=:lin): the step `from` -> `from + 1` of the nested embedding as a SparseMatrixCSC (unknowns of level
+from + 1 x unknowns of level from), built on the device.  order=:lin: an old point's row holds 1, a new point's row 0.5 at its two parents.
+order=:quad: the coarse P2 basis at the fine unknowns, rows of 1, 3, 5 or 10 fixed weights (include/waehip.h)."
+function prolongator(ref::Refinement; from::Integer=0, order::Symbol=:lin)
+    order in (:lin, :quad) || throw(ArgumentError("order must be :lin or :quad, got $order"))
     0 <= from < ref.levels || throw(ArgumentError("prolongator needs 0 <= from < $(ref.levels), got $from"))
-    nf, nc = ref.npoints[from + 2], ref.npoints[from + 1]
-    ptr = zeros(Int32, nf + 1); col = zeros(Int32, 2nf - nc); val = zeros(Float64, 2nf - nc)
-    check(ccall((:wae_octosplit_prolongator, libwaehip), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
-                ref.handle, from, ptr, col, val))
+    if order == :quad
+        _, nc, nnz = _p2_info(ref, from)
+        nf = ndof(ref, from + 1; order=:quad)
+        ptr = zeros(Int32, nf + 1); col = zeros(Int32, nnz); val = zeros(Float64, nnz)
+        check(ccall((:wae_octosplit_prolongator_p2, libwaehip), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                    ref.handle, from, ptr, col, val))
+    else
+        nf, nc = ref.npoints[from + 2], ref.npoints[from + 1]
+        ptr = zeros(Int32, nf + 1); col = zeros(Int32, 2nf - nc); val = zeros(Float64, 2nf - nc)
+        check(ccall((:wae_octosplit_prolongator, libwaehip), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                    ref.handle, from, ptr, col, val))
+    end
     # the CSR arrays of P are the CSC arrays of its transpose
     return sparse(transpose(SparseMatrixCSC(nc, nf, Int.(ptr) .+ 1, Int.(col) .+ 1, val)))
+end
+
+"E = p2_embedding(npoints, tets; device=0): the embedding of the P1 space of a mesh into its P2 space as a SparseMatrixCSC (npoints + nedges
+x npoints), built on the device from the edge list of the connectivity (wae_p2_embedding): a point's row holds 1, the row of edge (a, b) 0.5
+at a and b.  With the P1 steps behind it, the p-hierarchy of a P2 family for `solver_setup_nested`:
+[p2_embedding(n, tets); [prolongator(ref; from=l) for l in ref.levels-1:-1:0]]."
+function p2_embedding(npoints::Integer, tets::AbstractMatrix{<:Integer}; device::Integer=0)
+    t0 = _zero_based(tets); h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:wae_p2_connectivity, libwaehip), Cint, (Int32, Int64, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ref{Ptr{Cvoid}}),
+                device, npoints, size(t0, 2), t0, 0, C_NULL, h))
+    try
+        ne = Ref{Int64}(0); nt = Ref{Int64}(0); ns = Ref{Int64}(0)
+        check(ccall((:wae_p2_connectivity_info, libwaehip), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], ne, nt, ns))
+        n, nnz = Int(npoints + ne[]), Int(npoints + 2ne[])
+        ptr = zeros(Int32, n + 1); col = zeros(Int32, nnz); val = zeros(Float64, nnz)
+        check(ccall((:wae_p2_embedding, libwaehip), Cint, (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}), h[], npoints, ptr, col, val))
+        return sparse(transpose(SparseMatrixCSC(Int(npoints), n, Int.(ptr) .+ 1, Int.(col) .+ 1, val)))
+    finally
+        ccall((:wae_p2_connectivity_free, libwaehip), Cint, (Ptr{Cvoid},), h[])
+    end
 end
 
 "solver_setup_nested(fam, coeffs, Ps; opts=Float64[]): the multigrid set-up of `fam` from the prolongators Ps (finest first: size(Ps[1], 1)

@@ -46,6 +46,7 @@ EXPORTS = [
     "wae_bloch_numbering", "wae_bloch_numbering_info", "wae_bloch_numbering_get", "wae_bloch_numbering_free", "wae_bloch_fold",
     "wae_octosplit", "wae_octosplit_info", "wae_octosplit_get", "wae_octosplit_prolong", "wae_octosplit_free",
     "wae_octosplit_prolongator", "wae_solver_setup_nested",
+    "wae_octosplit_p2_info", "wae_octosplit_prolongator_p2", "wae_octosplit_prolong_p2", "wae_p2_embedding",
 ]
 BLOCH_IMAGE, BLOCH_AXIS = 1, 2      # WAE_BLOCH_* flag bits
 TALL_MAXCOLS = 64           # WAE_TALL_MAXCOLS
@@ -167,6 +168,10 @@ def lib():
     L.wae_octosplit_prolong.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, dp, dp]
     L.wae_octosplit_free.argtypes = [C.c_void_p]
     L.wae_octosplit_prolongator.argtypes = [C.c_void_p, C.c_int32, i32p, i32p, dp]
+    L.wae_octosplit_p2_info.argtypes = [C.c_void_p, C.c_int32, i64p, i64p, i64p]
+    L.wae_octosplit_prolongator_p2.argtypes = [C.c_void_p, C.c_int32, i32p, i32p, dp]
+    L.wae_octosplit_prolong_p2.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, dp, dp]
+    L.wae_p2_embedding.argtypes = [C.c_void_p, C.c_int64, i32p, i32p, dp]
     L.wae_solver_setup_nested.argtypes = [C.c_void_p, dp, dp, C.c_int32, C.c_int32, i64p, i64p, vpp, vpp, vpp]
     L.wae_bench_spmv.argtypes = [C.c_void_p, dp, C.c_int32, C.c_int32, dp]
     L.wae_bench_triad.argtypes = [C.c_int32, C.c_int64, C.c_int32, dp]

@@ -252,6 +252,24 @@ __global__ __launch_bounds__(256) void p2_edge_pairs_kernel(const u64 *__restric
     edges[e * 2 + 1] = (int)(k - lo * np);
 }
 
+// the embedding of the P1 space into the P2 space of the same mesh as CSR (np + ne rows, np columns): the row of point a holds (a, 1), the
+// row of edge (a, b), a < b, holds (a, 1/2) (b, 1/2) -- a P1 function at the P2 nodes; one thread per row, and one for ptr[np + ne]
+__global__ __launch_bounds__(256) void p2_embedding_kernel(int64_t np, const int *__restrict__ edges, int64_t ne, int *__restrict__ ptr,
+                                                           int *__restrict__ col, double *__restrict__ val) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > np + ne) return;
+    const int64_t p = i < np ? i : np + 2 * (i - np);
+    ptr[i] = (int)p;
+    if (i == np + ne) return;
+    if (i < np) {
+        col[p] = (int)i;
+        val[p] = 1.0;
+    } else {
+        col[p] = edges[(i - np) * 2]; col[p + 1] = edges[(i - np) * 2 + 1];
+        val[p] = 0.5; val[p + 1] = 0.5;
+    }
+}
+
 // ---- element kernels -------------------------------------------------------------------------------------------------------------
 // row a of the local matrices of tetrahedron t:  M_ab = |det J| int phi_a phi_b,   K_ab = -c^2 |det J| int grad phi_a . grad phi_b  with
 // int l_k l_l = (1 + delta_kl)/120:   K_ab = -c^2 |det J|/120 (s_a . s_b + sum_k w_a[k] . w_b[k])
@@ -841,6 +859,7 @@ __global__ __launch_bounds__(64) void p2_shape_ref_kernel(const double *__restri
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 struct P2Conn {
+    int device = 0;
     int64_t npoints = 0, nedges = 0, ntets = 0, ntris = 0;
     std::vector<int> edges, tets10, tris6;
 };
@@ -934,7 +953,7 @@ int wae_p2_connectivity(int32_t device, int64_t npoints, int64_t ntets, const in
         HIP_CHECK(hipSetDevice(device));
         P2Mesh m(npoints, nullptr, ntets, tets, ntris, tris);
         std::unique_ptr<P2Conn> H(new P2Conn);
-        H->npoints = npoints; H->nedges = m.nedges; H->ntets = ntets; H->ntris = ntris;
+        H->device = device; H->npoints = npoints; H->nedges = m.nedges; H->ntets = ntets; H->ntris = ntris;
         H->edges.resize((size_t)m.nedges * 2); H->tets10.resize((size_t)ntets * 10); H->tris6.resize((size_t)ntris * 6);
         Dev<int> de((size_t)m.nedges * 2);
         hipLaunchKernelGGL(p2_edge_pairs_kernel, dim3((unsigned)((m.nedges + 255) / 256)), dim3(256), 0, 0, m.ek.p, m.nedges, (u64)npoints, de.p);
@@ -972,6 +991,27 @@ int wae_p2_connectivity_get(const void *handle, int32_t *edges, int32_t *tets10,
 int wae_p2_connectivity_free(void *handle) {
     delete (P2Conn *)handle;
     return WAE_OK;
+}
+
+int wae_p2_embedding(const void *handle, int64_t npoints, int32_t *ptr, int32_t *col, double *val) {
+    return wae_guarded([&]() {
+        if (!handle) throw WaeError(WAE_ERR_INVALID, "null handle");
+        const P2Conn *H = (const P2Conn *)handle;
+        if (npoints != H->npoints) throw WaeError(WAE_ERR_INVALID, "npoints is not the point count the connectivity was numbered with");
+        if (!(ptr && col && val)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        const int64_t np = H->npoints, ne = H->nedges, nnz = np + 2 * ne;
+        if (nnz > INT_MAX) throw WaeError(WAE_ERR_INVALID, "the embedding's entries do not fit a 32-bit index");
+        HIP_CHECK(hipSetDevice(H->device));
+        Dev<int> de((size_t)ne * 2), dptr((size_t)(np + ne + 1)), dcol((size_t)nnz);
+        Dev<double> dval((size_t)nnz);
+        HIP_CHECK(hipMemcpy(de.p, H->edges.data(), (size_t)ne * 2 * sizeof(int), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(p2_embedding_kernel, dim3((unsigned)((np + ne + 1 + 255) / 256)), dim3(256), 0, 0, np, de.p, ne, dptr.p, dcol.p, dval.p);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(ptr, dptr.p, (size_t)(np + ne + 1) * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(col, dcol.p, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(val, dval.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
+        return WAE_OK;
+    });
 }
 
 // c: per tetrahedron (NULL = 1), or per mesh point (nodal; required)

@@ -24,6 +24,10 @@
 //      descending, 31 bits each: two stable 64-bit radix sorts of (key, child number), low pair first.  The inverse permutation gives
 //      tet_labels (8 per parent) and tri_labels (4 per parent): the positions of a parent's children, in the order listed above.
 // No atomics, the same bits on every call.  Only the edge count and three flags of a level come back to the host before the next level starts.
+//
+// The P2 prolongation between the levels ("P2 prolongation between two levels" below): the first P2 entry called on a handle numbers the
+// P2 edges of every level and builds every step as a CSR matrix in HBM; wae_octosplit_prolong_p2 applies it, wae_octosplit_prolongator_p2
+// copies it out.
 #include <hipcub/hipcub.hpp>
 
 #include <climits>
@@ -229,6 +233,134 @@ __global__ __launch_bounds__(256) void octo_prolongator_kernel(int64_t nold, con
     }
 }
 
+// ---- P2 prolongation between two levels ------------------------------------------------------------------------------------------------
+// The P2 unknowns of a level are its points, then its edges ascending by (smaller point, larger point) (p2_edge_key: the numbering of
+// wae_p2_assemble).  A row of the prolongator is the coarse basis -- l_i (2 l_i - 1) on the points, 4 l_i l_j on the edges -- at the place of
+// the fine unknown.  nc / nf: points of the coarse / fine level; fine point nc + k is the midpoint of parents[k] = (larger, smaller).
+//   fine unknown                                   entries
+//   old point a < nc                               (a, 1)
+//   new point, midpoint of the coarse edge AB      (edge AB, 1)
+//   fine edge (A, AB)                              (A, 3/8) (B, -1/8) (edge AB, 3/4)
+//   fine edge (AB, AC)                             (B, -1/8) (C, -1/8) (edge AB, 1/2) (edge AC, 1/2) (edge BC, 1/4); A has weight 0: not stored
+//   fine edge (AB, CD), an inner diagonal          the four points -1/8, the six edges among them 1/4
+// Only the two ends of the fine edge, the parents table and binary searches in the coarse edge list are read; one thread per row, every
+// entry written once, columns ascending (points before edges, either kind sorted).
+
+// entries of the fine row i (0 for a row that no refinement produces: flagged by the fill kernel)
+__device__ inline int octo_p2_row_length(int64_t i, int64_t nc, int64_t nf, const u64 *__restrict__ ekf, const int *__restrict__ parents) {
+    if (i < nf) return 1;
+    const u64 k = ekf[i - nf], u = k / (u64)nf, v = k - u * (u64)nf;          // u < v
+    if (v < (u64)nc) return 0;
+    if (u < (u64)nc) return 3;
+    const int a1 = parents[(u - nc) * 2], b1 = parents[(u - nc) * 2 + 1], a2 = parents[(v - nc) * 2], b2 = parents[(v - nc) * 2 + 1];
+    return (a1 == a2 || a1 == b2 || b1 == a2 || b1 == b2) ? 5 : 10;
+}
+
+// len[i] for the ndof rows, len[ndof] = 0: the exclusive scan of ndof + 1 values ends with the entry count
+__global__ __launch_bounds__(256) void octo_p2_count_kernel(int64_t nc, int64_t nf, int64_t ndof, const u64 *__restrict__ ekf,
+                                                            const int *__restrict__ parents, long long *__restrict__ len) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > ndof) return;
+    len[i] = i < ndof ? octo_p2_row_length(i, nc, nf, ekf, parents) : 0;
+}
+
+// M distinct columns with their weights, written in ascending column order (position = number of smaller columns)
+template <int M> __device__ inline void octo_p2_put(int *__restrict__ col, double *__restrict__ val, const int (&c)[M], const double (&w)[M]) {
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        int r = 0;
+#pragma unroll
+        for (int k = 0; k < M; ++k) r += c[k] < c[j];
+        col[r] = c[j];
+        val[r] = w[j];
+    }
+}
+
+// bad[0]: a pair of points that is no coarse edge, or a fine edge that no refinement produces (the row is then filled with column 0)
+__global__ __launch_bounds__(256) void octo_p2_fill_kernel(int64_t nc, int64_t nf, int64_t ndof, const u64 *__restrict__ ekc, int64_t nec,
+                                                           const u64 *__restrict__ ekf, const int *__restrict__ parents,
+                                                           const long long *__restrict__ ptr64, int *__restrict__ ptr, int *__restrict__ col,
+                                                           double *__restrict__ val, int *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i > ndof) return;
+    const long long p = ptr64[i];
+    ptr[i] = (int)p;
+    if (i == ndof) return;
+    int *cp = col + p;
+    double *vp = val + p;
+    auto edge = [&](int a, int b) {                     // the coarse unknown of edge (a, b)
+        int e = p2_find_edge(ekc, nec, (u64)nc, a, b);
+        if (e < 0) { bad[0] = 1; e = -(int)nc; }
+        return (int)nc + e;
+    };
+    if (i < nc) {
+        cp[0] = (int)i; vp[0] = 1.0;
+        return;
+    }
+    if (i < nf) {
+        cp[0] = edge(parents[(i - nc) * 2], parents[(i - nc) * 2 + 1]); vp[0] = 1.0;
+        return;
+    }
+    const u64 k = ekf[i - nf], uu = k / (u64)nf, vv = k - uu * (u64)nf;
+    if (vv < (u64)nc) { bad[0] = 1; return; }           // (its length is 0)
+    const int a2 = parents[(vv - nc) * 2], b2 = parents[(vv - nc) * 2 + 1];
+    if (uu < (u64)nc) {
+        const int A = (int)uu, B = a2 == A ? b2 : a2;
+        if (a2 != A && b2 != A) bad[0] = 1;
+        const int c[3] = {A, B, edge(a2, b2)};
+        const double w[3] = {0.375, -0.125, 0.75};
+        octo_p2_put<3>(cp, vp, c, w);
+        return;
+    }
+    const int a1 = parents[(uu - nc) * 2], b1 = parents[(uu - nc) * 2 + 1];
+    if (a1 == a2 || a1 == b2 || b1 == a2 || b1 == b2) {
+        const int A = (a1 == a2 || a1 == b2) ? a1 : b1, B = a1 + b1 - A, Cc = a2 + b2 - A;
+        const int c[5] = {B, Cc, edge(A, B), edge(A, Cc), edge(B, Cc)};
+        const double w[5] = {-0.125, -0.125, 0.5, 0.5, 0.25};
+        octo_p2_put<5>(cp, vp, c, w);
+        return;
+    }
+    const int c[10] = {a1, b1, a2, b2, edge(a1, b1), edge(a1, a2), edge(a1, b2), edge(b1, a2), edge(b1, b2), edge(a2, b2)};
+    const double w[10] = {-0.125, -0.125, -0.125, -0.125, 0.25, 0.25, 0.25, 0.25, 0.25, 0.25};
+    octo_p2_put<10>(cp, vp, c, w);
+}
+
+// Y = P X on column-major multivectors, P the real CSR step above (rows of 1, 3, 5 or 10 entries): one thread per fine row, the lanes
+// of a wave on consecutive rows, so that the col / val reads and the store of a column coalesce; a thread reads its row once into
+// registers and loops over the columns, gathering 16-byte values of X (the coarse vector is 1/8 of the fine one and stays in L2).
+// Rows longer than 10 entries (no octosplit step has one) finish from memory.
+constexpr int OCTO_P2_ROW = 10;
+__global__ __launch_bounds__(256) void octo_p2_apply_kernel(const int *__restrict__ ptr, const int *__restrict__ col, const double *__restrict__ val,
+                                                            int64_t nrow, int64_t nin, int ncols, const cplx *__restrict__ X, cplx *__restrict__ Y) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nrow) return;
+    const int p0 = ptr[i], len = ptr[i + 1] - p0;
+    int cj[OCTO_P2_ROW];
+    double vj[OCTO_P2_ROW];
+#pragma unroll
+    for (int k = 0; k < OCTO_P2_ROW; ++k) {
+        cj[k] = k < len ? col[p0 + k] : 0;
+        vj[k] = k < len ? val[p0 + k] : 0.0;
+    }
+    for (int c = 0; c < ncols; ++c) {
+        const cplx *x = X + (size_t)c * nin;
+        double re = 0.0, im = 0.0;
+#pragma unroll
+        for (int k = 0; k < OCTO_P2_ROW; ++k)
+            if (k < len) {
+                const cplx xv = x[cj[k]];
+                re = fma(vj[k], xv.x, re);
+                im = fma(vj[k], xv.y, im);
+            }
+        for (int k = OCTO_P2_ROW; k < len; ++k) {
+            const cplx xv = x[col[p0 + k]];
+            re = fma(val[p0 + k], xv.x, re);
+            im = fma(val[p0 + k], xv.y, im);
+        }
+        Y[(size_t)c * nrow + i] = cplx{re, im};
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 struct OctoLevel {
     int64_t np = 0, nt = 0, ns = 0;
@@ -236,9 +368,17 @@ struct OctoLevel {
     DevBuf<int> tets, tris;
     DevBuf<int> parents, tet_labels, tri_labels;     // empty on level 0
 };
+// the P2 space of a level and the prolongator to the next one, made by the first P2 call on the handle (octo_p2_build)
+struct OctoP2Level {
+    int64_t ne = 0, ndof = 0, nnz = 0;               // edges; points + edges; entries of the step level -> level + 1 (0 on the last level)
+    DevBuf<u64> ek;                                  // the edges: sorted keys smaller * npoints + larger
+    DevBuf<int> ptr, col;                            // the step as CSR, ndof(level + 1) rows
+    DevBuf<double> val;
+};
 struct Octo {
     int device = 0;
     std::vector<OctoLevel> lv;
+    std::vector<OctoP2Level> p2;                     // empty until a P2 entry is called
 };
 
 int octo_bits(u64 x) {          // bits that hold every value below x
@@ -327,9 +467,113 @@ template <class T> void octo_copy_out(T *dst, const DevBuf<T> &src, size_t count
     if (dst && count) HIP_CHECK(hipMemcpy(dst, src.p, count * sizeof(T), hipMemcpyDeviceToHost));
 }
 
+// the step l -> l + 1: row lengths by kind, an exclusive scan, one thread per row to fill it
+void octo_p2_step(const OctoLevel &F, const OctoLevel &T, const OctoP2Level &cf, const OctoP2Level &ct, OctoP2Level &out, int level) {
+    const std::string at = " (P2 prolongator of level " + std::to_string(level) + ")";
+    const int64_t nd = ct.ndof;
+    if (nd + 1 > INT_MAX) throw WaeError(WAE_ERR_INVALID, "npoints + nedges + 1 does not fit a 32-bit index" + at);
+    DevBuf<long long> len, ptr64;
+    len.alloc((size_t)nd + 1); ptr64.alloc((size_t)nd + 1);
+    hipLaunchKernelGGL(octo_p2_count_kernel, octo_grid(nd + 1), dim3(256), 0, 0, F.np, T.np, nd, ct.ek.p, T.parents.p, len.p);
+    HIP_CHECK(hipGetLastError());
+    size_t tb = 0;
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, len.p, ptr64.p, (int)(nd + 1)));
+    Dev<char> tmp(tb);
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, len.p, ptr64.p, (int)(nd + 1)));
+    long long nnz = 0;
+    HIP_CHECK(hipMemcpy(&nnz, ptr64.p + nd, sizeof(long long), hipMemcpyDeviceToHost));
+    if (nnz < nd || nnz > 10 * nd) throw WaeError(WAE_ERR_HIP, "P2 prolongator: the scan returned an impossible entry count" + at);
+    if (nnz > INT_MAX) throw WaeError(WAE_ERR_INVALID, "the prolongator's entries do not fit a 32-bit index" + at);
+    out.nnz = nnz;
+    out.ptr.alloc((size_t)nd + 1); out.col.alloc((size_t)nnz); out.val.alloc((size_t)nnz);
+    Dev<int> bad(1);
+    HIP_CHECK(hipMemset(bad.p, 0, sizeof(int)));
+    hipLaunchKernelGGL(octo_p2_fill_kernel, octo_grid(nd + 1), dim3(256), 0, 0, F.np, T.np, nd, cf.ek.p, cf.ne, ct.ek.p, T.parents.p, ptr64.p,
+                       out.ptr.p, out.col.p, out.val.p, bad.p);
+    HIP_CHECK(hipGetLastError());
+    int hbad = 0;
+    HIP_CHECK(hipMemcpy(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (hbad) throw WaeError(WAE_ERR_HIP, "P2 prolongator: an edge of the finer level does not come from the coarser one" + at);
+}
+
+// The first P2 call on a handle: the edges of every level (keys, sort and unique pass of wae_p2_connectivity: p2_edge_list) and every
+// step's prolongator, kept in HBM.  Nothing is kept if a level is refused.
+const std::vector<OctoP2Level> &octo_p2(Octo *H) {
+    if (!H->p2.empty()) return H->p2;
+    const size_t nl = H->lv.size();
+    std::vector<OctoP2Level> p2(nl);
+    for (size_t l = 0; l < nl; ++l) {
+        const OctoLevel &L = H->lv[l];
+        if (L.nt > INT_MAX / 6) throw WaeError(WAE_ERR_INVALID, "6*ntets does not fit a 32-bit index (P2 edges of level " + std::to_string(l) + ")");
+        Dev<u64> ek((size_t)L.nt * 6);
+        p2[l].ne = p2_edge_list(L.np, L.nt, L.tets.p, ek);          // (refuses npoints + nedges beyond a 32-bit index)
+        p2[l].ndof = L.np + p2[l].ne;
+        p2[l].ek.alloc((size_t)p2[l].ne);
+        HIP_CHECK(hipMemcpy(p2[l].ek.p, ek.p, (size_t)p2[l].ne * sizeof(u64), hipMemcpyDeviceToDevice));
+    }
+    for (size_t l = 0; l + 1 < nl; ++l) octo_p2_step(H->lv[l], H->lv[l + 1], p2[l], p2[l + 1], p2[l], (int)l);
+    H->p2 = std::move(p2);
+    return H->p2;
+}
+
 }  // namespace
 
 extern "C" {
+
+int wae_octosplit_p2_info(void *h, int32_t level, int64_t *nedges, int64_t *ndof, int64_t *prolongator_nnz) {
+    return wae_guarded([&]() {
+        (void)octo_level(h, level);
+        Octo *H = (Octo *)h;
+        HIP_CHECK(hipSetDevice(H->device));
+        const OctoP2Level &P = octo_p2(H)[(size_t)level];
+        if (nedges) *nedges = P.ne;
+        if (ndof) *ndof = P.ndof;
+        if (prolongator_nnz) *prolongator_nnz = P.nnz;
+        return WAE_OK;
+    });
+}
+
+int wae_octosplit_prolongator_p2(void *h, int32_t from_level, int32_t *ptr, int32_t *col, double *val) {
+    return wae_guarded([&]() {
+        (void)octo_level(h, from_level);
+        Octo *H = (Octo *)h;
+        if (from_level + 1 >= (int32_t)H->lv.size()) throw WaeError(WAE_ERR_INVALID, "from_level must be below the last level");
+        if (!(ptr && col && val)) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        HIP_CHECK(hipSetDevice(H->device));
+        const std::vector<OctoP2Level> &p2 = octo_p2(H);
+        const OctoP2Level &P = p2[(size_t)from_level];
+        octo_copy_out(ptr, P.ptr, (size_t)p2[(size_t)from_level + 1].ndof + 1);
+        octo_copy_out(col, P.col, (size_t)P.nnz);
+        octo_copy_out(val, P.val, (size_t)P.nnz);
+        return WAE_OK;
+    });
+}
+
+int wae_octosplit_prolong_p2(void *h, int32_t from_level, int32_t to_level, int32_t ncols, const double *X, double *Y) {
+    return wae_guarded([&]() {
+        (void)octo_level(h, from_level);
+        (void)octo_level(h, to_level);
+        if (from_level >= to_level) throw WaeError(WAE_ERR_INVALID, "prolongation needs from_level < to_level");
+        if (!(X && Y) || ncols < 1) throw WaeError(WAE_ERR_INVALID, "bad argument");
+        Octo *H = (Octo *)h;
+        HIP_CHECK(hipSetDevice(H->device));
+        const std::vector<OctoP2Level> &p2 = octo_p2(H);
+        DevBuf<cplx> a, b;                                  // the intermediate levels stay here
+        const size_t nin = (size_t)p2[(size_t)from_level].ndof * (size_t)ncols;
+        a.alloc(nin);
+        HIP_CHECK(hipMemcpy(a.p, X, nin * sizeof(cplx), hipMemcpyHostToDevice));
+        for (int32_t l = from_level; l < to_level; ++l) {
+            const OctoP2Level &P = p2[(size_t)l];
+            const int64_t nrow = p2[(size_t)l + 1].ndof;
+            b.alloc((size_t)nrow * (size_t)ncols);
+            hipLaunchKernelGGL(octo_p2_apply_kernel, octo_grid(nrow), dim3(256), 0, 0, P.ptr.p, P.col.p, P.val.p, nrow, P.ndof, (int)ncols, a.p, b.p);
+            HIP_CHECK(hipGetLastError());
+            std::swap(a, b);
+        }
+        HIP_CHECK(hipMemcpy(Y, a.p, (size_t)p2[(size_t)to_level].ndof * (size_t)ncols * sizeof(cplx), hipMemcpyDeviceToHost));
+        return WAE_OK;
+    });
+}
 
 int wae_octosplit(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris,
                   int32_t levels, void **out) {

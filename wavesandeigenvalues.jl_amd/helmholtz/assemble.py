@@ -149,6 +149,39 @@ def p2_connectivity(points, tets, tris=None, device=0):
     return edges, t10, t6
 
 
+def p2_embedding_host(npoints, edges):
+    """the P1 -> P2 embedding of one mesh formed on the host: the row of point a holds (a, 1), the row of edge (a, b), a < b, holds
+    (a, 1/2) (b, 1/2) -- a P1 function's values at the P2 nodes, which are its P2 coefficients"""
+    e = np.asarray(edges, dtype=np.int32).reshape(-1, 2)
+    n, ne = int(npoints), len(e)
+    ptr = np.concatenate([np.arange(n, dtype=np.int32), n + 2 * np.arange(ne + 1, dtype=np.int32)])
+    col = np.concatenate([np.arange(n, dtype=np.int32), e.ravel()])
+    val = np.concatenate([np.ones(n), np.full(2 * ne, 0.5)])
+    return sp.csr_matrix((val, col, ptr), shape=(n + ne, n))
+
+
+def p2_embedding(points, tets, device=0):
+    """The embedding of the P1 space of a mesh into its P2 space as a ``csr_matrix`` (npoints + nedges rows, npoints columns,
+    npoints + 2 nedges entries, columns ascending), built by a kernel from the edge list of ``wae_p2_connectivity``
+    (wae_p2_embedding): the coarse space of p-coarsening, a prolongator ``DeviceFamily.setup_solver(prolongators=...)`` takes.
+    ``points``: the (npoints, 3) array or just npoints."""
+    npoints = int(points) if np.ndim(points) == 0 else np.asarray(points).reshape(-1, 3).shape[0]
+    _, tt, _ = _mesh_args(np.zeros((0, 3)), tets)
+    L = _lib.lib()
+    ip = C.POINTER(C.c_int32)
+    h = C.c_void_p()
+    _lib.check(L.wae_p2_connectivity(int(device), npoints, tt.shape[0], tt.ctypes.data_as(ip), 0, None, C.byref(h)))
+    try:
+        ne = C.c_int64(0)
+        _lib.check(L.wae_p2_connectivity_info(h, C.byref(ne), None, None))
+        n, nnz = npoints + ne.value, npoints + 2 * ne.value
+        ptr, col, val = np.zeros(n + 1, dtype=np.int32), np.zeros(nnz, dtype=np.int32), np.zeros(nnz)
+        _lib.check(L.wae_p2_embedding(h, npoints, ptr.ctypes.data_as(ip), col.ctypes.data_as(ip), val.ctypes.data_as(C.POINTER(C.c_double))))
+    finally:
+        L.wae_p2_connectivity_free(h)
+    return sp.csr_matrix((val, col, ptr), shape=(n, npoints))
+
+
 def assemble_p2(points, tets, c_tet=None, device=0, dtype=np.complex128, c_point=None):
     """P2 mass and stiffness matrices on the device (wae_p2_assemble, wae_p2_assemble_cpoint; src/Helmholtz.jl:120-149,405-441 with
     order=:quad), arguments as ``assemble_p1``.  Returns (M, K) as scipy CSR matrices of size npoints + nedges sharing one pattern."""
