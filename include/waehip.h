@@ -518,6 +518,48 @@ int wae_octosplit_p2_info(void *handle, int32_t level, int64_t *nedges, int64_t 
 int wae_octosplit_prolongator_p2(void *handle, int32_t from_level, int32_t *ptr, int32_t *col, double *val);
 int wae_octosplit_prolong_p2(void *handle, int32_t from_level, int32_t to_level, int32_t ncols, const double *X, double *Y);
 int wae_octosplit_free(void *handle);
+/* -- point location in a tetrahedral mesh and sampling of P1 / P2 vectors there, on the device --------------------------
+ * find_tetrahedron_containing_point (src/Meshutils.jl:800-815) and get_p / get_n_grad_p (src/FEM/helmholtz_getters.jl:7-45) for many
+ * points at once.  wae_locator_create keeps the mesh (points: 3 doubles per point, tets: 4 point indices per tetrahedron, 0-based) and a
+ * uniform cell grid over it in HBM; every pointer of these entries is a host pointer.
+ *  - containment: the barycentric coordinates of x by Cramer's rule on J = [p1-p4, p2-p4, p3-p4], the fourth 1 - sum, every operation
+ *    rounded on its own in double (a float64 host restatement gets the same bits), independent of the sign of det J.  A tetrahedron
+ *    contains x if all four are >= -tol, 0 <= tol <= 1e-6 (tol = 0: the reference's all(0 .<= xi .<= 1)); wae_locator_find returns the
+ *    LOWEST such index in list order in tet[q], -1 if there is none, and in lambda (4 per point, may be NULL) the coordinates that
+ *    decided, NaN for -1.
+ *  - cells: the bounding box of the points (block reduction), a grid of about ntets / cell_target cells over it (cell_target = 0: 8), as
+ *    cubical as the box allows, at most 1024 per axis and 8 ntets in all (every dim is halved until that holds).  Every tetrahedron is listed in the cells that its bounding box, grown per axis by
+ *    (4e-6 + 2^-30) times the extent of the mesh, overlaps; a point's cell and a box corner's cell come from the same expression
+ *    clamp(floor((x - lo) * (dim / (hi - lo))), 0, dim - 1), which is monotone in x under rounding, so the list of a point's cell holds
+ *    every tetrahedron the rule can accept.  Count, exclusive scan, stable radix sort by cell (hipCUB): the tetrahedra ascend within a
+ *    cell, a query stops at its first hit.  More than 32 ntets pairs: every dim is halved and the pairs recounted, down to one cell.  No
+ *    atomics; the same input gives the same indices and bits on every call.  A point outside the box grown by the same amount (no
+ *    tetrahedron can accept it) is -1 without a look at the cells; a point in the rim between the two boxes or on an upper face of
+ *    the box belongs to the first or last cell of the axis.
+ * wae_locator_info: the sizes, dims[3], nrefs = the (cell, tet) pairs, max_per_cell = the longest list; any pointer may be NULL.
+ * wae_locator_set_p2: the P2 unknowns of every tetrahedron (tets10: 10 per tetrahedron as wae_p2_connectivity_get gives them: the 4
+ * points, then the edges (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)), ndof = npoints + nedges; needed before any call with order 2.
+ * wae_locator_weights: the rows of the point functionals, idx / val with 4 (order 1) or 10 (order 2) entries per point: kind 0, p(x) =
+ * sum val v[idx]: l_i on the points (order 1), l_i (2 l_i - 1) on the points and 4 l_i l_j on the edges (order 2); kind 1, n . grad p(x):
+ * the derivative of those weights along n (3 per point).  tet: the tetrahedron of every point (from wae_locator_find); a row with tet ==
+ * -1 has idx 0 and val 0.
+ * wae_locator_sample: out[q, c] = sum_i val[q, i] V[idx[q, i], c] in one gather kernel, i ascending, without the weights leaving the
+ * device.  V: d x ncols complex column-major (interleaved re/im), d = npoints (order 1) or ndof (order 2); out: nq x ncols complex
+ * column-major; a row with tet == -1 is NaN.
+ * WAE_ERR_INVALID, nothing launched: a negative count, a tetrahedron index outside 0..npoints-1, a point or query coordinate that is
+ * not finite, tol outside [0, 1e-6], a tet outside -1..ntets-1, order 2 before wae_locator_set_p2, d different from npoints / ndof, an
+ * entry of tets10 outside 0..ndof-1, kind 1 with n == NULL, npoints or 32 ntets beyond a 32-bit index.  nq == 0 returns WAE_OK and
+ * touches nothing.  Out of scope: Hermite elements, nearest-tetrahedron answers outside the mesh, curved geometry, Bloch-expanded fields. */
+int wae_locator_create(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t cell_target,
+                       void **out);
+int wae_locator_info(const void *handle, int64_t *npoints, int64_t *ntets, int64_t *dims, int64_t *nrefs, int64_t *max_per_cell);
+int wae_locator_find(const void *handle, int64_t nq, const double *x, double tol, int32_t *tet, double *lambda);
+int wae_locator_set_p2(void *handle, int64_t ndof, const int32_t *tets10);
+int wae_locator_weights(const void *handle, int32_t order, int32_t kind, int64_t nq, const double *x, const int32_t *tet, const double *n,
+                        int32_t *idx, double *val);
+int wae_locator_sample(const void *handle, int32_t order, int32_t kind, int64_t nq, const double *x, const int32_t *tet, const double *n,
+                       int64_t d, int32_t ncols, const double *V, double *out);
+int wae_locator_free(void *handle);
 /* -- Bloch unit cells with P1 or P2 elements: cell numbering and operator fold on the device ------------------------
  * `discretize(mesh, dscrp, C; order, b=:b)` on a mesh with a degree of symmetry: blochify (src/Bloch.jl:4-112), the dimension of
  * Helmholtz.jl:107-113.  The mesh is the EXTENDED unit cell: points < naxis lie on the symmetry axis, points >= nsector are image

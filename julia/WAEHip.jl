@@ -1518,6 +1518,110 @@ function ndof(ref::Refinement, level::Integer; order::Symbol=:lin)
     return _p2_info(ref, level)[2]
 end
 
+# Point location and sampling on the device (include/waehip.h, wae_locator_*): find_tetrahedron_containing_point (Meshutils.jl:800-815) and
+# get_p / get_n_grad_p (FEM/helmholtz_getters.jl:7-45) for many points at once.  Points are the columns of X (3 x nq); indices are 1-based
+# here, 0 = the point lies in no tetrahedron.
+"the mesh and a uniform cell grid over it, kept in HBM; `dims`, `nrefs`, `max_per_cell` describe the grid"
+mutable struct PointLocator
+    handle::Ptr{Cvoid}
+    npoints::Int
+    ntets::Int
+    dims::NTuple{3,Int}
+    nrefs::Int
+    max_per_cell::Int
+    tets::Matrix{Int32}
+    ndof::Int                      # of the P2 space, 0 until an order=:quad call
+    device::Int
+end
+
+"release the device arrays of a PointLocator (the finalizer is only the safety net).  Idempotent."
+function free!(loc::PointLocator)
+    loc.handle != C_NULL && ccall((:wae_locator_free, libwaehip), Cint, (Ptr{Cvoid},), loc.handle)
+    loc.handle = C_NULL
+    return nothing
+end
+
+"loc = locator(mesh; cell_target=0, device=0): the locator of the package's `Mesh` (cell_target tetrahedra per grid cell, 0: about 8)"
+function locator(mesh; cell_target::Integer=0, device::Integer=0)
+    points = Matrix{Float64}(mesh.points)
+    t0 = _zero_based(hcat(mesh.tetrahedra...))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:wae_locator_create, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ref{Ptr{Cvoid}}),
+                device, size(points, 2), points, size(t0, 2), t0, cell_target, h))
+    loc = PointLocator(h[], size(points, 2), size(t0, 2), (0, 0, 0), 0, 0, t0, 0, Int(device))
+    finalizer(free!, loc)                      # attached before anything else can throw, so the handle cannot leak
+    np = Ref{Int64}(0); nt = Ref{Int64}(0); nr = Ref{Int64}(0); mx = Ref{Int64}(0); dims = zeros(Int64, 3)
+    check(ccall((:wae_locator_info, libwaehip), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ref{Int64}, Ref{Int64}), h[], np, nt, dims, nr, mx))
+    loc.npoints, loc.ntets, loc.nrefs, loc.max_per_cell = Int(np[]), Int(nt[]), Int(nr[]), Int(mx[])
+    loc.dims = (Int(dims[1]), Int(dims[2]), Int(dims[3]))
+    return loc
+end
+
+"find_tetrahedra(loc, X; tol=0): per column of X (3 x nq) the first tetrahedron in list order whose barycentric coordinates are all >= -tol
+(1-based; 0: none), 0 <= tol <= 1e-6"
+function find_tetrahedra(loc::PointLocator, X::Matrix{Float64}; tol::Real=0)
+    size(X, 1) == 3 || throw(ArgumentError("X must be 3 x nq"))
+    tet = fill(Int32(-1), size(X, 2))
+    check(ccall((:wae_locator_find, libwaehip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Float64, Ptr{Int32}, Ptr{Float64}),
+                loc.handle, size(X, 2), X, Float64(tol), tet, C_NULL))
+    return Int.(tet) .+ 1
+end
+
+function _locator_p2!(loc::PointLocator)
+    loc.ndof > 0 && return
+    # loc.tets is 0-based (what the library holds); p2_connectivity takes and returns 1-based indices, wae_locator_set_p2 wants 0-based
+    edges, t10, _ = p2_connectivity(loc.npoints, loc.tets .+ Int32(1); device=loc.device)
+    ndof = loc.npoints + size(edges, 2)
+    t10_0 = t10 .- Int32(1)
+    check(ccall((:wae_locator_set_p2, libwaehip), Cint, (Ptr{Cvoid}, Int64, Ptr{Int32}), loc.handle, ndof, t10_0))
+    loc.ndof = ndof
+    return
+end
+
+function _locator_sample(loc::PointLocator, V::AbstractVecOrMat{<:Number}, X::Matrix{Float64}, n, order::Symbol)
+    order in (:lin, :quad) || throw(ArgumentError("order must be :lin or :quad, got $order"))
+    size(X, 1) == 3 || throw(ArgumentError("X must be 3 x nq"))
+    order == :quad && _locator_p2!(loc)
+    nq = size(X, 2)
+    tet = fill(Int32(-1), nq)
+    check(ccall((:wae_locator_find, libwaehip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Float64, Ptr{Int32}, Ptr{Float64}),
+                loc.handle, nq, X, 0.0, tet, C_NULL))
+    Vc = Matrix{ComplexF64}(reshape(V, size(V, 1), :))
+    out = zeros(ComplexF64, nq, size(Vc, 2))
+    check(ccall((:wae_locator_sample, libwaehip), Cint,
+                (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Int64, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                loc.handle, order == :lin ? 1 : 2, n === nothing ? 0 : 1, nq, X, tet, n === nothing ? C_NULL : n, size(Vc, 1), size(Vc, 2), Vc, out))
+    return V isa AbstractVector ? out[:, 1] : out
+end
+
+"get_p(loc, V, X; order=:lin): the pressure of every column of V at every column of X (NaN where the point lies in no tetrahedron)"
+get_p(loc::PointLocator, V::AbstractVecOrMat{<:Number}, X::Matrix{Float64}; order::Symbol=:lin) = _locator_sample(loc, V, X, nothing, order)
+
+"get_n_grad_p(loc, V, X, n; order=:lin): n . grad p there; n is one direction (3) or one per point (3 x nq)"
+function get_n_grad_p(loc::PointLocator, V::AbstractVecOrMat{<:Number}, X::Matrix{Float64}, n::AbstractVecOrMat{<:Real}; order::Symbol=:lin)
+    N = n isa AbstractVector ? repeat(Float64.(n), 1, size(X, 2)) : Matrix{Float64}(n)
+    size(N) == size(X) || throw(ArgumentError("n must have 3 entries or the shape of X"))
+    return _locator_sample(loc, V, X, N, order)
+end
+
+"idx, val = locator_weights(loc, X, tet; order=:lin, n=nothing): the rows of the point functionals (wae_locator_weights), 1-based unknowns,
+4 (:lin) or 10 (:quad) per point; tet as find_tetrahedra returns it"
+function locator_weights(loc::PointLocator, X::Matrix{Float64}, tet::AbstractVector{<:Integer}; order::Symbol=:lin, n=nothing)
+    order in (:lin, :quad) || throw(ArgumentError("order must be :lin or :quad, got $order"))
+    size(X, 1) == 3 || throw(ArgumentError("X must be 3 x nq"))
+    nq = size(X, 2); nw = order == :lin ? 4 : 10
+    length(tet) == nq || throw(ArgumentError("tet must have one entry per column of X ($nq), got $(length(tet))"))
+    N = n === nothing ? nothing : Matrix{Float64}(n)
+    N === nothing || size(N) == size(X) || throw(ArgumentError("n must have the shape of X"))
+    order == :quad && _locator_p2!(loc)
+    t0 = Int32.(tet) .- Int32(1)
+    idx = zeros(Int32, nw, nq); val = zeros(Float64, nw, nq)
+    check(ccall((:wae_locator_weights, libwaehip), Cint,
+                (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                loc.handle, order == :lin ? 1 : 2, N === nothing ? 0 : 1, nq, X, t0, N === nothing ? C_NULL : N, idx, val))
+    return Int.(idx) .+ 1, val
+end
+
 "(nedges, ndof, prolongator_nnz) of a level's P2 space (wae_octosplit_p2_info)"
 function _p2_info(ref::Refinement, level::Integer)
     ne = Ref{Int64}(0); nd = Ref{Int64}(0); nz = Ref{Int64}(0)

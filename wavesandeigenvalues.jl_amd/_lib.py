@@ -47,6 +47,8 @@ EXPORTS = [
     "wae_octosplit", "wae_octosplit_info", "wae_octosplit_get", "wae_octosplit_prolong", "wae_octosplit_free",
     "wae_octosplit_prolongator", "wae_solver_setup_nested",
     "wae_octosplit_p2_info", "wae_octosplit_prolongator_p2", "wae_octosplit_prolong_p2", "wae_p2_embedding",
+    "wae_locator_create", "wae_locator_info", "wae_locator_find", "wae_locator_set_p2", "wae_locator_weights", "wae_locator_sample",
+    "wae_locator_free",
 ]
 BLOCH_IMAGE, BLOCH_AXIS = 1, 2      # WAE_BLOCH_* flag bits
 TALL_MAXCOLS = 64           # WAE_TALL_MAXCOLS
@@ -172,6 +174,13 @@ def lib():
     L.wae_octosplit_prolongator_p2.argtypes = [C.c_void_p, C.c_int32, i32p, i32p, dp]
     L.wae_octosplit_prolong_p2.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, dp, dp]
     L.wae_p2_embedding.argtypes = [C.c_void_p, C.c_int64, i32p, i32p, dp]
+    L.wae_locator_create.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, C.POINTER(C.c_void_p)]
+    L.wae_locator_info.argtypes = [C.c_void_p, i64p, i64p, i64p, i64p, i64p]
+    L.wae_locator_find.argtypes = [C.c_void_p, C.c_int64, dp, C.c_double, i32p, dp]
+    L.wae_locator_set_p2.argtypes = [C.c_void_p, C.c_int64, i32p]
+    L.wae_locator_weights.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, i32p, dp, i32p, dp]
+    L.wae_locator_sample.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, i32p, dp, C.c_int64, C.c_int32, dp, dp]
+    L.wae_locator_free.argtypes = [C.c_void_p]
     L.wae_solver_setup_nested.argtypes = [C.c_void_p, dp, dp, C.c_int32, C.c_int32, i64p, i64p, vpp, vpp, vpp]
     L.wae_bench_spmv.argtypes = [C.c_void_p, dp, C.c_int32, C.c_int32, dp]
     L.wae_bench_triad.argtypes = [C.c_int32, C.c_int64, C.c_int32, dp]
