@@ -9,28 +9,14 @@
 //      deterministic (no atomics);
 //   3. reduce-by-key (hipCUB) of both value streams, and the CSR row pointer from the unique keys.
 // The result is what Julia's sparse(I, J, V) returns for the same triplets, up to the order of the additions.
-#include <hipcub/hipcub.hpp>
-
 #include <cstring>
 #include <memory>
 #include <vector>
 
-#include "wae_internal.h"
+#include "mesh_host.h"
 #include "../../include/waehip.h"
 
 namespace {
-
-template <class F> int wae_guarded(F &&f) {
-    try {
-        return f();
-    } catch (const WaeError &e) {
-        wae_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        wae_set_error(e.what());
-        return WAE_ERR_INVALID;
-    }
-}
 
 // local P1 matrices of one tetrahedron with corner coordinates X: M_ab = |det J|/120 (1+delta_ab), K_ab = -c^2 |det J|/6 grad_a.grad_b
 __device__ inline void p1_local(const double X[4][3], double c, double M[16], double K[16]) {
@@ -262,25 +248,24 @@ void triplets_to_csr_dev(int64_t npoints, size_t ne, Dev<unsigned long long> &k0
     Dev<int> dnum(1);
     Dev<unsigned long long> k1(ne), ku0(ne);
     Dev<unsigned int> i0(ne), i1(ne);
-    const unsigned g = (unsigned)std::min<size_t>((ne + 255) / 256, 8192);
-    hipLaunchKernelGGL(iota_kernel, dim3(g), dim3(256), 0, 0, i0.p, ne);
-    int bits = 1;
-    while (bits < 64 && ((unsigned long long)npoints * (unsigned long long)npoints) >> bits) ++bits;
-    size_t tmp_bytes = 0;
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, k0.p, k1.p, i0.p, i1.p, (int)ne, 0, bits));
-    Dev<char> tmp(tmp_bytes);
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, k0.p, k1.p, i0.p, i1.p, (int)ne, 0, bits));
-    hipLaunchKernelGGL(gather_d_kernel, dim3(g), dim3(256), 0, 0, mv.p, i1.p, ms.p, ne);
-    if (kv) hipLaunchKernelGGL(gather_d_kernel, dim3(g), dim3(256), 0, 0, kv->p, i1.p, ks.p, ne);
-    size_t tb2 = 0;
-    HIP_CHECK(hipcub::DeviceReduce::ReduceByKey(nullptr, tb2, k1.p, ku0.p, ms.p, mu.p, dnum.p, hipcub::Sum(), (int)ne));
-    Dev<char> tmp2(tb2);
-    HIP_CHECK(hipcub::DeviceReduce::ReduceByKey(tmp2.p, tb2, k1.p, ku0.p, ms.p, mu.p, dnum.p, hipcub::Sum(), (int)ne));
-    if (kv) HIP_CHECK(hipcub::DeviceReduce::ReduceByKey(tmp2.p, tb2, k1.p, ku0.p, ks.p, ku.p, dnum.p, hipcub::Sum(), (int)ne));
+    const dim3 g = grid_for(ne, GRID_STRIDE_CAP);
+    hipLaunchKernelGGL(iota_kernel, g, dim3(256), 0, 0, i0.p, ne);
+    const int bits = key_bits((unsigned long long)npoints * (unsigned long long)npoints);
+    auto sort = [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0.p, k1.p, i0.p, i1.p, (int)ne, 0, bits); };
+    auto reduce = [&](double *in, double *out) {
+        return [&, in, out](void *t, size_t &b) { return hipcub::DeviceReduce::ReduceByKey(t, b, k1.p, ku0.p, in, out, dnum.p, hipcub::Sum(), (int)ne); };
+    };
+    DevBuf<char> tmp;
+    cub_reserve(tmp, sort, reduce(ms.p, mu.p));
+    cub_run(sort, tmp);
+    hipLaunchKernelGGL(gather_d_kernel, g, dim3(256), 0, 0, mv.p, i1.p, ms.p, ne);
+    if (kv) hipLaunchKernelGGL(gather_d_kernel, g, dim3(256), 0, 0, kv->p, i1.p, ks.p, ne);
+    cub_run(reduce(ms.p, mu.p), tmp);
+    if (kv) cub_run(reduce(ks.p, ku.p), tmp);
     int nnz = 0;
-    HIP_CHECK(hipMemcpy(&nnz, dnum.p, sizeof(int), hipMemcpyDeviceToHost));
+    dnum.to_host(&nnz, 1);
     HIP_CHECK(hipMemset(drow.p, 0xff, ((size_t)npoints + 1) * sizeof(int)));          // -1 = row without entries
-    hipLaunchKernelGGL(split_keys_kernel, dim3(g), dim3(256), 0, 0, ku0.p, (size_t)nnz, (unsigned long long)npoints, dcol.p, drow.p);
+    hipLaunchKernelGGL(split_keys_kernel, g, dim3(256), 0, 0, ku0.p, (size_t)nnz, (unsigned long long)npoints, dcol.p, drow.p);
     HIP_CHECK(hipGetLastError());
     out.np = npoints; out.nnz = nnz;
 }
@@ -292,14 +277,21 @@ P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k
     std::unique_ptr<P1Handle> H(new P1Handle);
     H->np = npoints; H->nnz = nnz;
     H->rowptr.resize((size_t)npoints + 1); H->col.resize(nnz); H->m.resize(nnz); H->k.assign(nnz, 0.0);
-    HIP_CHECK(hipMemcpy(H->rowptr.data(), D.rowptr.p, ((size_t)npoints + 1) * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(H->col.data(), D.col.p, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(H->m.data(), D.m.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
-    if (kv) HIP_CHECK(hipMemcpy(H->k.data(), D.k.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
+    D.rowptr.to_host(H->rowptr.data(), (size_t)npoints + 1);
+    D.col.to_host(H->col.data(), (size_t)nnz);
+    D.m.to_host(H->m.data(), (size_t)nnz);
+    if (kv) D.k.to_host(H->k.data(), (size_t)nnz);
     H->rowptr[npoints] = nnz;
     for (int64_t r = npoints - 1; r >= 0; --r)
         if (H->rowptr[r] < 0) H->rowptr[r] = H->rowptr[r + 1];
     return H.release();
+}
+
+// (declared in mesh_host.h: assemble_p2.hip sums its flame with it too)
+double flame_volume(const Dev<double> &adet, int64_t nflame) {
+    const double volume = device_sum(adet.p, (int)nflame) / 6.0;
+    if (!(volume > 0.0)) throw WaeError(WAE_ERR_INVALID, "flame domain has no volume");
+    return volume;
 }
 
 void pairs_to_dense(int64_t n, size_t ne, Dev<unsigned long long> &k0, Dev<double> &v, double *out) {
@@ -501,6 +493,24 @@ __global__ void shape_ref_kernel(const double *__restrict__ pts, const int *__re
     if (e < npair * 6) g_pm[e] = acc; else *g0 = acc;
 }
 
+namespace {
+
+// One half of wae_p1_shape_sensitivity (tetrahedra with omega, triangles with omega Y): the simplices, their speed of sound (nc values, NULL = 1)
+// and the (point, simplex) pairs go up, `kernel` runs over the 3 npair (pair, coordinate) items, out receives their 3 npair complex numbers.
+typedef void (*ShapeKernel)(const double *, const int *, const double *, int64_t, const int *, const int *, double, double, const cplx *, const cplx *,
+                            double, cplx *);
+void shape_half(ShapeKernel kernel, const Dev<double> &dpts, const int32_t *simplices, size_t nints, const double *c, size_t nc, int64_t npair,
+                const int32_t *pair_pt, const int32_t *pair_simplex, const double *w, const Dev<cplx> &dv, const Dev<cplx> &dva, double h, double *out) {
+    Dev<int> dt(simplices, nints), dpp(pair_pt, (size_t)npair), dps(pair_simplex, (size_t)npair);
+    Dev<double> dc(c, c ? nc : 0);
+    Dev<cplx> dout((size_t)npair * 3);
+    hipLaunchKernelGGL(kernel, grid_for(npair * 3), dim3(256), 0, 0, dpts.p, dt.p, c ? dc.p : nullptr, npair, dpp.p, dps.p, w[0], w[1], dv.p, dva.p, h, dout.p);
+    HIP_CHECK(hipGetLastError());
+    dout.to_host((cplx *)out, (size_t)npair * 3);
+}
+
+}  // namespace
+
 extern "C" {
 
 // c: per triangle (NULL = 1), or per mesh point (nodal; required)
@@ -509,19 +519,14 @@ static int p1_assemble_boundary(int32_t device, int64_t npoints, const double *p
     return wae_guarded([&]() {
         if (!(npoints > 0 && ntris > 0 && points && tris && out)) throw WaeError(WAE_ERR_INVALID, "bad argument");
         if (nodal) check_c_point(npoints, c);
-        for (int64_t i = 0; i < ntris * 3; ++i)
-            if (tris[i] < 0 || tris[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "triangle refers to a point outside 0..npoints-1");
+        check_tris(tris, ntris, npoints);
         HIP_CHECK(hipSetDevice(device));
-        const size_t ne = (size_t)ntris * 9, nc = (size_t)(nodal ? npoints : ntris);
-        Dev<double> dpts((size_t)npoints * 3), dc(c ? nc : 1), bv(ne);
-        Dev<int> dt((size_t)ntris * 3);
+        const size_t ne = (size_t)ntris * 9;
+        Dev<double> dpts(points, (size_t)npoints * 3), dc(c, c ? (size_t)(nodal ? npoints : ntris) : 0), bv(ne);
+        Dev<int> dt(tris, (size_t)ntris * 3);
         Dev<unsigned long long> k0(ne);
-        HIP_CHECK(hipMemcpy(dpts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dt.p, tris, (size_t)ntris * 3 * sizeof(int), hipMemcpyHostToDevice));
-        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
-        const dim3 grid((unsigned)((ntris + 255) / 256));
-        if (nodal) hipLaunchKernelGGL(p1_boundary_cpoint_kernel, grid, dim3(256), 0, 0, dpts.p, dt.p, dc.p, ntris, npoints, k0.p, bv.p);
-        else hipLaunchKernelGGL(p1_boundary_kernel, grid, dim3(256), 0, 0, dpts.p, dt.p, c ? dc.p : nullptr, ntris, npoints, k0.p, bv.p);
+        if (nodal) hipLaunchKernelGGL(p1_boundary_cpoint_kernel, grid_for(ntris), dim3(256), 0, 0, dpts.p, dt.p, dc.p, ntris, npoints, k0.p, bv.p);
+        else hipLaunchKernelGGL(p1_boundary_kernel, grid_for(ntris), dim3(256), 0, 0, dpts.p, dt.p, c ? dc.p : nullptr, ntris, npoints, k0.p, bv.p);
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(npoints, ne, k0, bv, nullptr);
         return WAE_OK;
@@ -544,22 +549,17 @@ static int p1_assemble_source(int32_t device, int64_t npoints, const double *poi
         if (!(npoints > 0 && ntris >= 0 && points && (ntris == 0 || tris) && out)) throw WaeError(WAE_ERR_INVALID, "bad argument");
         if (nodal) check_c_point(npoints, c);
         if ((size_t)ntris * 3 >= 0x7fffffffull) throw WaeError(WAE_ERR_INVALID, "too many triangles for a 32-bit pair count");
-        for (int64_t i = 0; i < ntris * 3; ++i)
-            if (tris[i] < 0 || tris[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "triangle refers to a point outside 0..npoints-1");
+        check_tris(tris, ntris, npoints);
         if (ntris == 0) {                                                     // an empty speaker domain: the zero vector
             std::fill(out, out + npoints, 0.0);
             return WAE_OK;
         }
         HIP_CHECK(hipSetDevice(device));
-        const size_t ne = (size_t)ntris * 3, nc = (size_t)(nodal ? npoints : ntris);
-        Dev<double> dpts((size_t)npoints * 3), dc(c ? nc : 1), sv(ne);
-        Dev<int> dt((size_t)ntris * 3);
+        const size_t ne = (size_t)ntris * 3;
+        Dev<double> dpts(points, (size_t)npoints * 3), dc(c, c ? (size_t)(nodal ? npoints : ntris) : 0), sv(ne);
+        Dev<int> dt(tris, (size_t)ntris * 3);
         Dev<unsigned long long> k0(ne);
-        HIP_CHECK(hipMemcpy(dpts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dt.p, tris, (size_t)ntris * 3 * sizeof(int), hipMemcpyHostToDevice));
-        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(p1_source_kernel, dim3((unsigned)((ntris + 255) / 256)), dim3(256), 0, 0, dpts.p, dt.p, c ? dc.p : nullptr, nodal ? 1 : 0, ntris,
-                           npoints, k0.p, sv.p);
+        hipLaunchKernelGGL(p1_source_kernel, grid_for(ntris), dim3(256), 0, 0, dpts.p, dt.p, c ? dc.p : nullptr, nodal ? 1 : 0, ntris, npoints, k0.p, sv.p);
         HIP_CHECK(hipGetLastError());
         pairs_to_dense(npoints, ne, k0, sv, out);
         return WAE_OK;
@@ -580,30 +580,16 @@ int wae_p1_assemble_flame(int32_t device, int64_t npoints, const double *points,
     return wae_guarded([&]() {
         if (!(npoints > 0 && ntets > 0 && nflame > 0 && points && tets && flame_tets && n_ref && out)) throw WaeError(WAE_ERR_INVALID, "bad argument");
         if (ref_tet < 0 || ref_tet >= ntets) throw WaeError(WAE_ERR_INVALID, "reference tetrahedron out of range");
-        for (int64_t i = 0; i < nflame; ++i)
-            if (flame_tets[i] < 0 || flame_tets[i] >= ntets) throw WaeError(WAE_ERR_INVALID, "flame tetrahedron out of range");
-        for (int64_t i = 0; i < ntets * 4; ++i)
-            if (tets[i] < 0 || tets[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "tetrahedron refers to a point outside 0..npoints-1");
+        check_indices(flame_tets, nflame, ntets, "flame tetrahedron out of range");
+        check_tets(tets, ntets, npoints);
         HIP_CHECK(hipSetDevice(device));
         const size_t ne = (size_t)nflame * 16;
-        Dev<double> dpts((size_t)npoints * 3), adet((size_t)nflame), vol(1), qv(ne);
-        Dev<int> dt((size_t)ntets * 4), dl((size_t)nflame);
+        Dev<double> dpts(points, (size_t)npoints * 3), adet((size_t)nflame), qv(ne);
+        Dev<int> dt(tets, (size_t)ntets * 4), dl(flame_tets, (size_t)nflame);
         Dev<unsigned long long> k0(ne);
-        HIP_CHECK(hipMemcpy(dpts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dt.p, tets, (size_t)ntets * 4 * sizeof(int), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, flame_tets, (size_t)nflame * sizeof(int), hipMemcpyHostToDevice));
-        const unsigned gb = (unsigned)((nflame + 255) / 256);
-        hipLaunchKernelGGL(p1_det_kernel, dim3(gb), dim3(256), 0, 0, dpts.p, dt.p, dl.p, nflame, adet.p);
+        hipLaunchKernelGGL(p1_det_kernel, grid_for(nflame), dim3(256), 0, 0, dpts.p, dt.p, dl.p, nflame, adet.p);
         HIP_CHECK(hipGetLastError());
-        // flame volume = sum |det J| / 6 (Meshutils.jl:757-767), summed in a fixed tree order on the device
-        size_t tb = 0;
-        HIP_CHECK(hipcub::DeviceReduce::Sum(nullptr, tb, adet.p, vol.p, (int)nflame));
-        Dev<char> tmp(tb);
-        HIP_CHECK(hipcub::DeviceReduce::Sum(tmp.p, tb, adet.p, vol.p, (int)nflame));
-        double det_sum = 0.0;
-        HIP_CHECK(hipMemcpy(&det_sum, vol.p, sizeof(double), hipMemcpyDeviceToHost));
-        const double volume = det_sum / 6.0;
-        if (!(volume > 0.0)) throw WaeError(WAE_ERR_INVALID, "flame domain has no volume");
+        const double volume = flame_volume(adet, nflame);
         if (volume_out) *volume_out = volume;
         const double nlocal = nglobal_scaled / volume;                                 // Helmholtz.jl:325
         // g_b = -nlocal grad(phi_b) . n_ref on the reference tetrahedron (FEM.jl:2442-2448, Helmholtz.jl:482): 4 numbers, on the host
@@ -627,7 +613,7 @@ int wae_p1_assemble_flame(int32_t device, int64_t npoints, const double *points,
         for (int k = 0; k < 3; ++k) G[3][k] = -(G[0][k] + G[1][k] + G[2][k]);
         double g[4];
         for (int b = 0; b < 4; ++b) g[b] = -nlocal * (G[b][0] * n_ref[0] + G[b][1] * n_ref[1] + G[b][2] * n_ref[2]);
-        hipLaunchKernelGGL(p1_flame_kernel, dim3(gb), dim3(256), 0, 0, dt.p, dl.p, nflame, adet.p, rn[0], rn[1], rn[2], rn[3], g[0], g[1], g[2], g[3], npoints,
+        hipLaunchKernelGGL(p1_flame_kernel, grid_for(nflame), dim3(256), 0, 0, dt.p, dl.p, nflame, adet.p, rn[0], rn[1], rn[2], rn[3], g[0], g[1], g[2], g[3], npoints,
                            k0.p, qv.p);
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(npoints, ne, k0, qv, nullptr);
@@ -641,19 +627,14 @@ static int p1_assemble_interior(int32_t device, int64_t npoints, const double *p
         if (!(npoints > 0 && ntets > 0 && points && tets && out)) throw WaeError(WAE_ERR_INVALID, "bad argument");
         if (nodal) check_c_point(npoints, c);
         if ((size_t)ntets * 16 >= 0xffffffffull) throw WaeError(WAE_ERR_INVALID, "too many tetrahedra for 32-bit triplet indices");
-        for (int64_t i = 0; i < ntets * 4; ++i)
-            if (tets[i] < 0 || tets[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "tetrahedron refers to a point outside 0..npoints-1");
+        check_tets(tets, ntets, npoints);
         HIP_CHECK(hipSetDevice(device));
-        const size_t ne = (size_t)ntets * 16, nc = (size_t)(nodal ? npoints : ntets);
-        Dev<double> dpts((size_t)npoints * 3), dc(c ? nc : 1), mv(ne), kv(ne);
-        Dev<int> dt((size_t)ntets * 4);
+        const size_t ne = (size_t)ntets * 16;
+        Dev<double> dpts(points, (size_t)npoints * 3), dc(c, c ? (size_t)(nodal ? npoints : ntets) : 0), mv(ne), kv(ne);
+        Dev<int> dt(tets, (size_t)ntets * 4);
         Dev<unsigned long long> k0(ne);
-        HIP_CHECK(hipMemcpy(dpts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dt.p, tets, (size_t)ntets * 4 * sizeof(int), hipMemcpyHostToDevice));
-        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
-        const dim3 grid((unsigned)((ntets + 255) / 256));
-        if (nodal) hipLaunchKernelGGL(p1_local_cpoint_kernel, grid, dim3(256), 0, 0, dpts.p, dt.p, dc.p, ntets, npoints, k0.p, mv.p, kv.p);
-        else hipLaunchKernelGGL(p1_local_kernel, grid, dim3(256), 0, 0, dpts.p, dt.p, c ? dc.p : nullptr, ntets, npoints, k0.p, mv.p, kv.p);
+        if (nodal) hipLaunchKernelGGL(p1_local_cpoint_kernel, grid_for(ntets), dim3(256), 0, 0, dpts.p, dt.p, dc.p, ntets, npoints, k0.p, mv.p, kv.p);
+        else hipLaunchKernelGGL(p1_local_kernel, grid_for(ntets), dim3(256), 0, 0, dpts.p, dt.p, c ? dc.p : nullptr, ntets, npoints, k0.p, mv.p, kv.p);
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(npoints, ne, k0, mv, &kv);
         return WAE_OK;
@@ -682,54 +663,21 @@ static int p1_shape_sensitivity(int32_t device, int64_t npoints, const double *p
         }
         if (npair_t > 0 && !(tets && pair_pt_t && pair_tet && out_t && ntets > 0)) throw WaeError(WAE_ERR_INVALID, "bad tetrahedron pair arguments");
         if (npair_s > 0 && !(tris && c_tri && pair_pt_s && pair_tri && out_s && omegaY && ntris > 0)) throw WaeError(WAE_ERR_INVALID, "bad triangle pair arguments");
-        for (int64_t i = 0; i < npair_t; ++i)
-            if (pair_tet[i] < 0 || pair_tet[i] >= ntets || pair_pt_t[i] < 0 || pair_pt_t[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
-        for (int64_t i = 0; i < npair_s; ++i)
-            if (pair_tri[i] < 0 || pair_tri[i] >= ntris || pair_pt_s[i] < 0 || pair_pt_s[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
-        for (int64_t i = 0; i < ntets * 4 && npair_t > 0; ++i)
-            if (tets[i] < 0 || tets[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "tetrahedron refers to a point outside 0..npoints-1");
-        for (int64_t i = 0; i < ntris * 3 && npair_s > 0; ++i)
-            if (tris[i] < 0 || tris[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "triangle refers to a point outside 0..npoints-1");
+        check_indices(pair_tet, npair_t, ntets, "pair index out of range");
+        check_indices(pair_pt_t, npair_t, npoints, "pair index out of range");
+        check_indices(pair_tri, npair_s, ntris, "pair index out of range");
+        check_indices(pair_pt_s, npair_s, npoints, "pair index out of range");
+        if (npair_t > 0) check_tets(tets, ntets, npoints);
+        if (npair_s > 0) check_tris(tris, ntris, npoints);
         HIP_CHECK(hipSetDevice(device));
-        Dev<double> dpts((size_t)npoints * 3);
-        Dev<cplx> dv((size_t)npoints), dva((size_t)npoints);
-        HIP_CHECK(hipMemcpy(dpts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dv.p, v, (size_t)npoints * sizeof(cplx), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dva.p, v_adj, (size_t)npoints * sizeof(cplx), hipMemcpyHostToDevice));
-        if (npair_t > 0) {
-            Dev<int> dt((size_t)ntets * 4), dpp((size_t)npair_t), dpt((size_t)npair_t);
-            const size_t nc = (size_t)(nodal ? npoints : ntets);
-            Dev<double> dc(c_tet ? nc : 1);
-            Dev<cplx> dout((size_t)npair_t * 3);
-            HIP_CHECK(hipMemcpy(dt.p, tets, (size_t)ntets * 4 * sizeof(int), hipMemcpyHostToDevice));
-            if (c_tet) HIP_CHECK(hipMemcpy(dc.p, c_tet, nc * sizeof(double), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dpp.p, pair_pt_t, (size_t)npair_t * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dpt.p, pair_tet, (size_t)npair_t * sizeof(int), hipMemcpyHostToDevice));
-            const dim3 grid((unsigned)((npair_t * 3 + 255) / 256));
-            if (nodal) hipLaunchKernelGGL(shape_tet_kernel<true>, grid, dim3(256), 0, 0, dpts.p, dt.p, dc.p, npair_t, dpp.p, dpt.p, omega[0], omega[1], dv.p,
-                                          dva.p, h, dout.p);
-            else hipLaunchKernelGGL(shape_tet_kernel<false>, grid, dim3(256), 0, 0, dpts.p, dt.p, c_tet ? dc.p : nullptr, npair_t, dpp.p, dpt.p, omega[0],
-                                    omega[1], dv.p, dva.p, h, dout.p);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpy(out_t, dout.p, (size_t)npair_t * 3 * sizeof(cplx), hipMemcpyDeviceToHost));
-        }
-        if (npair_s > 0) {
-            Dev<int> dt((size_t)ntris * 3), dpp((size_t)npair_s), dpt((size_t)npair_s);
-            const size_t nc = (size_t)(nodal ? npoints : ntris);
-            Dev<double> dc(nc);
-            Dev<cplx> dout((size_t)npair_s * 3);
-            HIP_CHECK(hipMemcpy(dt.p, tris, (size_t)ntris * 3 * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dc.p, c_tri, nc * sizeof(double), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dpp.p, pair_pt_s, (size_t)npair_s * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dpt.p, pair_tri, (size_t)npair_s * sizeof(int), hipMemcpyHostToDevice));
-            const dim3 grid((unsigned)((npair_s * 3 + 255) / 256));
-            if (nodal) hipLaunchKernelGGL(shape_tri_kernel<true>, grid, dim3(256), 0, 0, dpts.p, dt.p, dc.p, npair_s, dpp.p, dpt.p, omegaY[0], omegaY[1], dv.p,
-                                          dva.p, h, dout.p);
-            else hipLaunchKernelGGL(shape_tri_kernel<false>, grid, dim3(256), 0, 0, dpts.p, dt.p, dc.p, npair_s, dpp.p, dpt.p, omegaY[0], omegaY[1], dv.p,
-                                    dva.p, h, dout.p);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpy(out_s, dout.p, (size_t)npair_s * 3 * sizeof(cplx), hipMemcpyDeviceToHost));
-        }
+        Dev<double> dpts(points, (size_t)npoints * 3);
+        Dev<cplx> dv((const cplx *)v, (size_t)npoints), dva((const cplx *)v_adj, (size_t)npoints);
+        if (npair_t > 0)
+            shape_half(nodal ? shape_tet_kernel<true> : shape_tet_kernel<false>, dpts, tets, (size_t)ntets * 4, c_tet, (size_t)(nodal ? npoints : ntets),
+                       npair_t, pair_pt_t, pair_tet, omega, dv, dva, h, out_t);
+        if (npair_s > 0)
+            shape_half(nodal ? shape_tri_kernel<true> : shape_tri_kernel<false>, dpts, tris, (size_t)ntris * 3, c_tri, (size_t)(nodal ? npoints : ntris),
+                       npair_s, pair_pt_s, pair_tri, omegaY, dv, dva, h, out_s);
         return WAE_OK;
     });
 }
@@ -759,43 +707,31 @@ int wae_p1_shape_sensitivity_flame(int32_t device, int64_t npoints, const double
         if (npair > 0 && !(pair_pt && pair_tet && det_pm && ssum)) throw WaeError(WAE_ERR_INVALID, "bad flame pair arguments");
         if (npair_r > 0 && !(pair_pt_r && g_pm)) throw WaeError(WAE_ERR_INVALID, "bad reference pair arguments");
         if (ref_tet < 0 || ref_tet >= ntets) throw WaeError(WAE_ERR_INVALID, "reference tetrahedron out of range");
-        for (int64_t i = 0; i < npair; ++i)
-            if (pair_tet[i] < 0 || pair_tet[i] >= ntets || pair_pt[i] < 0 || pair_pt[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
-        for (int64_t i = 0; i < npair_r; ++i)
-            if (pair_pt_r[i] < 0 || pair_pt_r[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
-        for (int64_t i = 0; i < ntets * 4; ++i)
-            if (tets[i] < 0 || tets[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "tetrahedron refers to a point outside 0..npoints-1");
+        check_indices(pair_tet, npair, ntets, "pair index out of range");
+        check_indices(pair_pt, npair, npoints, "pair index out of range");
+        check_indices(pair_pt_r, npair_r, npoints, "pair index out of range");
+        check_tets(tets, ntets, npoints);
         HIP_CHECK(hipSetDevice(device));
-        Dev<double> dpts((size_t)npoints * 3);
-        Dev<cplx> dv((size_t)npoints), dva((size_t)npoints);
-        Dev<int> dt((size_t)ntets * 4);
-        HIP_CHECK(hipMemcpy(dpts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dv.p, v, (size_t)npoints * sizeof(cplx), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dva.p, v_adj, (size_t)npoints * sizeof(cplx), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dt.p, tets, (size_t)ntets * 4 * sizeof(int), hipMemcpyHostToDevice));
+        Dev<double> dpts(points, (size_t)npoints * 3);
+        Dev<cplx> dv((const cplx *)v, (size_t)npoints), dva((const cplx *)v_adj, (size_t)npoints);
+        Dev<int> dt(tets, (size_t)ntets * 4);
         if (npair > 0) {
-            Dev<int> dpp((size_t)npair), dpt((size_t)npair);
+            Dev<int> dpp(pair_pt, (size_t)npair), dpt(pair_tet, (size_t)npair);
             Dev<double> ddet((size_t)npair * 6);
             Dev<cplx> dss((size_t)npair);
-            HIP_CHECK(hipMemcpy(dpp.p, pair_pt, (size_t)npair * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dpt.p, pair_tet, (size_t)npair * sizeof(int), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(shape_flame_kernel, dim3((unsigned)((npair * 3 + 255) / 256)), dim3(256), 0, 0, dpts.p, dt.p, npair, dpp.p, dpt.p, dva.p, h,
-                               ddet.p, dss.p);
+            hipLaunchKernelGGL(shape_flame_kernel, grid_for(npair * 3), dim3(256), 0, 0, dpts.p, dt.p, npair, dpp.p, dpt.p, dva.p, h, ddet.p, dss.p);
             HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpy(det_pm, ddet.p, (size_t)npair * 6 * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(ssum, dss.p, (size_t)npair * sizeof(cplx), hipMemcpyDeviceToHost));
+            ddet.to_host(det_pm, (size_t)npair * 6);
+            dss.to_host((cplx *)ssum, (size_t)npair);
         }
-        {
-            Dev<int> dpr((size_t)std::max<int64_t>(npair_r, 1));
-            Dev<cplx> dg((size_t)npair_r * 6 + 1);
-            if (npair_r > 0) HIP_CHECK(hipMemcpy(dpr.p, pair_pt_r, (size_t)npair_r * sizeof(int), hipMemcpyHostToDevice));
-            const int64_t nthr = npair_r * 6 + 1;
-            hipLaunchKernelGGL(shape_ref_kernel, dim3((unsigned)((nthr + 63) / 64)), dim3(64), 0, 0, dpts.p, dt.p, ref_tet, npair_r, dpr.p, n_ref[0], n_ref[1],
-                               n_ref[2], dv.p, h, dg.p, dg.p + (size_t)npair_r * 6);
-            HIP_CHECK(hipGetLastError());
-            if (npair_r > 0) HIP_CHECK(hipMemcpy(g_pm, dg.p, (size_t)npair_r * 6 * sizeof(cplx), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(g0, dg.p + (size_t)npair_r * 6, sizeof(cplx), hipMemcpyDeviceToHost));
-        }
+        const size_t nr = (size_t)npair_r;
+        Dev<int> dpr(pair_pt_r, nr);
+        Dev<cplx> dg(nr * 6 + 1);
+        hipLaunchKernelGGL(shape_ref_kernel, dim3((unsigned)((nr * 6 + 1 + 63) / 64)), dim3(64), 0, 0, dpts.p, dt.p, ref_tet, npair_r, dpr.p, n_ref[0], n_ref[1],
+                           n_ref[2], dv.p, h, dg.p, dg.p + nr * 6);
+        HIP_CHECK(hipGetLastError());
+        dg.to_host((cplx *)g_pm, nr * 6);
+        dg.to_host((cplx *)g0, 1, nr * 6);
         return WAE_OK;
     });
 }

@@ -14,31 +14,17 @@
 // a homogeneous quadratic form  phi_a = 1/2 sum_kl q2[a][k][l] l_k l_l  with integer q2, and the monomial formula
 //     int l^alpha = |det J| prod(alpha_i!) / (|alpha| + n - 1)!
 // gives every local matrix exactly: the tables below are made from it at compile time, none is copied from anywhere.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <climits>
 #include <memory>
 #include <vector>
 
 #include "edge_keys.h"
-#include "wae_internal.h"
+#include "mesh_host.h"
 
 namespace {
 
 typedef unsigned long long u64;
-
-template <class F> int wae_guarded(F &&f) {
-    try {
-        return f();
-    } catch (const WaeError &e) {
-        wae_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        wae_set_error(e.what());
-        return WAE_ERR_INVALID;
-    }
-}
 
 template <int NV> struct P2Basis {
     static constexpr int NN = NV + NV * (NV - 1) / 2;
@@ -868,38 +854,26 @@ void p2_check_mesh(int64_t npoints, int64_t ntets, const int32_t *tets, int64_t 
     if (!(npoints > 0 && ntets > 0 && tets && ntris >= 0 && (ntris == 0 || tris))) throw WaeError(WAE_ERR_INVALID, "bad argument");
     if (npoints > INT_MAX || ntets > INT_MAX / 100 || ntris > INT_MAX / 36)
         throw WaeError(WAE_ERR_INVALID, "mesh too large: 100*ntets and 36*ntris triplets must fit a 32-bit count");
-    for (int64_t i = 0; i < ntets * 4; ++i)
-        if (tets[i] < 0 || tets[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "tetrahedron refers to a point outside 0..npoints-1");
-    for (int64_t i = 0; i < ntris * 3; ++i)
-        if (tris[i] < 0 || tris[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "triangle refers to a point outside 0..npoints-1");
+    check_tets(tets, ntets, npoints);
+    check_tris(tris, ntris, npoints);
 }
 
 // Edge list and connectivities of a mesh whose 4-node tetrahedra (and 3-node triangles, ns may be 0) are on the device.
 // ek: room for 6*nt keys, on return the nedges sorted unique keys; t10: 10*nt; s6: 6*ns.  Returns nedges.
 int64_t p2_connect(int64_t npoints, int64_t nt, const int *dtets, int64_t ns, const int *dtris, Dev<u64> &ek, Dev<int> &t10, Dev<int> &s6) {
     const int nk = (int)(nt * 6);
-    Dev<u64> k0((size_t)nk), k1((size_t)nk);
-    Dev<int> dnum(1), bad(2);
-    hipLaunchKernelGGL(p2_edge_keys_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, 0, dtets, nt, (u64)npoints, k0.p);
+    Dev<u64> k0((size_t)nk);
+    Dev<int> bad(2);
+    hipLaunchKernelGGL(p2_edge_keys_kernel, grid_for(nt), dim3(256), 0, 0, dtets, nt, (u64)npoints, k0.p);
     HIP_CHECK(hipGetLastError());
-    int bits = 1;
-    while (bits < 64 && ((u64)npoints * (u64)npoints) >> bits) ++bits;
-    size_t tb = 0, tb2 = 0;
-    HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, k0.p, k1.p, nk, 0, bits));
-    HIP_CHECK(hipcub::DeviceSelect::Unique(nullptr, tb2, k1.p, ek.p, dnum.p, nk));
-    Dev<char> tmp(std::max(tb, tb2));
-    HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(tmp.p, tb, k0.p, k1.p, nk, 0, bits));
-    HIP_CHECK(hipcub::DeviceSelect::Unique(tmp.p, tb2, k1.p, ek.p, dnum.p, nk));
-    int ne = 0;
-    HIP_CHECK(hipMemcpy(&ne, dnum.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (ne <= 0 || ne > nk) throw WaeError(WAE_ERR_HIP, "edge list: unique pass returned an impossible count");
+    const int ne = sorted_unique_keys(k0, nk, key_bits((u64)npoints * (u64)npoints), ek);
     if (npoints + (int64_t)ne > INT_MAX) throw WaeError(WAE_ERR_INVALID, "npoints + nedges does not fit a 32-bit index");
     HIP_CHECK(hipMemset(bad.p, 0, 2 * sizeof(int)));
-    hipLaunchKernelGGL(p2_connect_kernel, dim3((unsigned)((nt + ns + 255) / 256)), dim3(256), 0, 0, dtets, nt, dtris, ns, ek.p, (int64_t)ne, (u64)npoints,
+    hipLaunchKernelGGL(p2_connect_kernel, grid_for(nt + ns), dim3(256), 0, 0, dtets, nt, dtris, ns, ek.p, (int64_t)ne, (u64)npoints,
                        t10.p, s6.p, bad.p);
     HIP_CHECK(hipGetLastError());
     int hbad[2] = {0, 0};
-    HIP_CHECK(hipMemcpy(hbad, bad.p, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    bad.to_host(hbad, 2);
     if (hbad[0]) throw WaeError(WAE_ERR_HIP, "edge list: an edge of a tetrahedron was not found");
     if (hbad[1]) throw WaeError(WAE_ERR_INVALID, "a boundary triangle has an edge that is no tetrahedron's edge");
     return ne;
@@ -926,16 +900,46 @@ struct P2Mesh {
     Dev<u64> ek;
     int64_t nedges = 0, dim = 0;
     P2Mesh(int64_t npoints, const double *points, int64_t nt, const int32_t *htets, int64_t ns, const int32_t *htris)
-        : pts(points ? (size_t)npoints * 3 : 1), tets((size_t)nt * 4), tris((size_t)ns * 3), t10((size_t)nt * 10), s6((size_t)ns * 6), ek((size_t)nt * 6) {
-        if (points) HIP_CHECK(hipMemcpy(pts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(tets.p, htets, (size_t)nt * 4 * sizeof(int), hipMemcpyHostToDevice));
-        if (ns) HIP_CHECK(hipMemcpy(tris.p, htris, (size_t)ns * 3 * sizeof(int), hipMemcpyHostToDevice));
+        : pts(points, points ? (size_t)npoints * 3 : 0), tets(htets, (size_t)nt * 4), tris(htris, (size_t)ns * 3), t10((size_t)nt * 10), s6((size_t)ns * 6),
+          ek((size_t)nt * 6) {
         nedges = p2_connect(npoints, nt, tets.p, ns, tris.p, ek, t10, s6);
         dim = npoints + nedges;
     }
 };
 
+// One half of wae_p2_shape_sensitivity (10-node tetrahedra with omega, 6-node triangles with omega Y) on the mesh in HBM: the (point, simplex) pairs
+// and, unless the nodal field c_nodal is on the device already, the speed of sound per simplex (c: nc values, NULL = 1) go up, `kernel` runs
+// with a thread per pair, out receives the 3 npair complex numbers.
+typedef void (*P2ShapeKernel)(const double *, const int *, const double *, int64_t, const int *, const int *, double, double, const cplx *, const cplx *,
+                              double, cplx *);
+void p2_shape_half(P2ShapeKernel kernel, const Dev<double> &pts, const Dev<int> &nodes, const double *c_nodal, const double *c, size_t nc, int64_t npair,
+                   const int32_t *pair_pt, const int32_t *pair_simplex, const double *w, const Dev<cplx> &dv, const Dev<cplx> &dva, double h, double *out) {
+    Dev<int> dpp(pair_pt, (size_t)npair), dps(pair_simplex, (size_t)npair);
+    Dev<double> dc(c, !c_nodal && c ? nc : 0);
+    Dev<cplx> dout((size_t)npair * 3);
+    hipLaunchKernelGGL(kernel, grid_for(npair), dim3(256), 0, 0, pts.p, nodes.p, c_nodal ? c_nodal : c ? dc.p : nullptr, npair, dpp.p, dps.p, w[0], w[1], dv.p,
+                       dva.p, h, dout.p);
+    HIP_CHECK(hipGetLastError());
+    dout.to_host((cplx *)out, (size_t)npair * 3);
+}
+
 }  // namespace
+
+// (declared in mesh_host.h: octosplit.hip numbers the new points of a level with it)
+int sorted_unique_keys(Dev<unsigned long long> &k0, int nk, int bits, Dev<unsigned long long> &ek) {
+    Dev<unsigned long long> k1((size_t)nk);
+    Dev<int> dnum(1);
+    auto sort = [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortKeys(t, b, k0.p, k1.p, nk, 0, bits); };
+    auto unique = [&](void *t, size_t &b) { return hipcub::DeviceSelect::Unique(t, b, k1.p, ek.p, dnum.p, nk); };
+    DevBuf<char> tmp;
+    cub_reserve(tmp, sort, unique);
+    cub_run(sort, tmp);
+    cub_run(unique, tmp);
+    int ne = 0;
+    dnum.to_host(&ne, 1);
+    if (ne <= 0 || ne > nk) throw WaeError(WAE_ERR_HIP, "edge list: unique pass returned an impossible count");
+    return ne;
+}
 
 // the sorted unique edge keys of a mesh whose tetrahedra are on the device (declared in wae_internal.h: bloch.hip numbers unit cells with them)
 int64_t p2_edge_list(int64_t npoints, int64_t nt, const int *dtets, Dev<unsigned long long> &ek) {
@@ -956,11 +960,11 @@ int wae_p2_connectivity(int32_t device, int64_t npoints, int64_t ntets, const in
         H->device = device; H->npoints = npoints; H->nedges = m.nedges; H->ntets = ntets; H->ntris = ntris;
         H->edges.resize((size_t)m.nedges * 2); H->tets10.resize((size_t)ntets * 10); H->tris6.resize((size_t)ntris * 6);
         Dev<int> de((size_t)m.nedges * 2);
-        hipLaunchKernelGGL(p2_edge_pairs_kernel, dim3((unsigned)((m.nedges + 255) / 256)), dim3(256), 0, 0, m.ek.p, m.nedges, (u64)npoints, de.p);
+        hipLaunchKernelGGL(p2_edge_pairs_kernel, grid_for(m.nedges), dim3(256), 0, 0, m.ek.p, m.nedges, (u64)npoints, de.p);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(H->edges.data(), de.p, H->edges.size() * sizeof(int), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(H->tets10.data(), m.t10.p, H->tets10.size() * sizeof(int), hipMemcpyDeviceToHost));
-        if (ntris) HIP_CHECK(hipMemcpy(H->tris6.data(), m.s6.p, H->tris6.size() * sizeof(int), hipMemcpyDeviceToHost));
+        de.to_host(H->edges.data(), H->edges.size());
+        m.t10.to_host(H->tets10.data(), H->tets10.size());
+        m.s6.to_host(H->tris6.data(), H->tris6.size());
         *out = H.release();
         return WAE_OK;
     });
@@ -1002,14 +1006,13 @@ int wae_p2_embedding(const void *handle, int64_t npoints, int32_t *ptr, int32_t 
         const int64_t np = H->npoints, ne = H->nedges, nnz = np + 2 * ne;
         if (nnz > INT_MAX) throw WaeError(WAE_ERR_INVALID, "the embedding's entries do not fit a 32-bit index");
         HIP_CHECK(hipSetDevice(H->device));
-        Dev<int> de((size_t)ne * 2), dptr((size_t)(np + ne + 1)), dcol((size_t)nnz);
+        Dev<int> de(H->edges.data(), (size_t)ne * 2), dptr((size_t)(np + ne + 1)), dcol((size_t)nnz);
         Dev<double> dval((size_t)nnz);
-        HIP_CHECK(hipMemcpy(de.p, H->edges.data(), (size_t)ne * 2 * sizeof(int), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(p2_embedding_kernel, dim3((unsigned)((np + ne + 1 + 255) / 256)), dim3(256), 0, 0, np, de.p, ne, dptr.p, dcol.p, dval.p);
+        hipLaunchKernelGGL(p2_embedding_kernel, grid_for(np + ne + 1), dim3(256), 0, 0, np, de.p, ne, dptr.p, dcol.p, dval.p);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(ptr, dptr.p, (size_t)(np + ne + 1) * sizeof(int), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(col, dcol.p, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(val, dval.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
+        dptr.to_host(ptr, (size_t)(np + ne + 1));
+        dcol.to_host(col, (size_t)nnz);
+        dval.to_host(val, (size_t)nnz);
         return WAE_OK;
     });
 }
@@ -1023,11 +1026,10 @@ static int p2_assemble_interior(int32_t device, int64_t npoints, const double *p
         if (nodal) check_c_point(npoints, c);
         HIP_CHECK(hipSetDevice(device));
         P2Mesh m(npoints, points, ntets, tets, 0, nullptr);
-        const size_t ne = (size_t)ntets * 100, nc = (size_t)(nodal ? npoints : ntets);
-        Dev<double> dc(c ? nc : 1), mv(ne), kv(ne);
+        const size_t ne = (size_t)ntets * 100;
+        Dev<double> dc(c, c ? (size_t)(nodal ? npoints : ntets) : 0), mv(ne), kv(ne);
         Dev<u64> k0(ne);
-        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
-        const dim3 grid((unsigned)((ntets * 10 + 255) / 256));
+        const dim3 grid = grid_for(ntets * 10);
         if (nodal) hipLaunchKernelGGL(p2_local_cpoint_kernel, grid, dim3(256), 0, 0, m.pts.p, m.t10.p, dc.p, ntets, (u64)m.dim, k0.p, mv.p, kv.p);
         else hipLaunchKernelGGL(p2_local_kernel, grid, dim3(256), 0, 0, m.pts.p, m.t10.p, c ? dc.p : nullptr, ntets, (u64)m.dim, k0.p, mv.p, kv.p);
         HIP_CHECK(hipGetLastError());
@@ -1044,11 +1046,10 @@ static int p2_assemble_boundary(int32_t device, int64_t npoints, const double *p
         if (nodal) check_c_point(npoints, c);
         HIP_CHECK(hipSetDevice(device));
         P2Mesh m(npoints, points, ntets, tets, ntris, tris);
-        const size_t ne = (size_t)ntris * 36, nc = (size_t)(nodal ? npoints : ntris);
-        Dev<double> dc(c ? nc : 1), bv(ne);
+        const size_t ne = (size_t)ntris * 36;
+        Dev<double> dc(c, c ? (size_t)(nodal ? npoints : ntris) : 0), bv(ne);
         Dev<u64> k0(ne);
-        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
-        const dim3 grid((unsigned)((ntris * 6 + 255) / 256));
+        const dim3 grid = grid_for(ntris * 6);
         if (nodal) hipLaunchKernelGGL(p2_boundary_cpoint_kernel, grid, dim3(256), 0, 0, m.pts.p, m.s6.p, dc.p, ntris, (u64)m.dim, k0.p, bv.p);
         else hipLaunchKernelGGL(p2_boundary_kernel, grid, dim3(256), 0, 0, m.pts.p, m.s6.p, c ? dc.p : nullptr, ntris, (u64)m.dim, k0.p, bv.p);
         HIP_CHECK(hipGetLastError());
@@ -1072,12 +1073,11 @@ static int p2_assemble_source(int32_t device, int64_t npoints, const double *poi
             std::fill(out, out + nout, 0.0);
             return WAE_OK;
         }
-        const size_t ne = (size_t)ntris * 6, nc = (size_t)(nodal ? npoints : ntris);
-        Dev<double> dc(c ? nc : 1), sv(ne);
+        const size_t ne = (size_t)ntris * 6;
+        Dev<double> dc(c, c ? (size_t)(nodal ? npoints : ntris) : 0), sv(ne);
         Dev<u64> k0(ne);
-        if (c) HIP_CHECK(hipMemcpy(dc.p, c, nc * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(p2_source_kernel, dim3((unsigned)((ntris * 6 + 255) / 256)), dim3(256), 0, 0, m.pts.p, m.s6.p, c ? dc.p : nullptr, nodal ? 1 : 0,
-                           ntris, (u64)m.dim, k0.p, sv.p);
+        hipLaunchKernelGGL(p2_source_kernel, grid_for(ntris * 6), dim3(256), 0, 0, m.pts.p, m.s6.p, c ? dc.p : nullptr, nodal ? 1 : 0, ntris, (u64)m.dim, k0.p,
+                           sv.p);
         HIP_CHECK(hipGetLastError());
         pairs_to_dense(m.dim, ne, k0, sv, out);
         return WAE_OK;
@@ -1120,26 +1120,16 @@ int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points,
         p2_check_mesh(npoints, ntets, tets, 0, nullptr);
         if (nflame > INT_MAX / 100) throw WaeError(WAE_ERR_INVALID, "too many flame tetrahedra: 100*nflame triplets must fit a 32-bit count");
         if (ref_tet < 0 || ref_tet >= ntets) throw WaeError(WAE_ERR_INVALID, "reference tetrahedron out of range");
-        for (int64_t i = 0; i < nflame; ++i)
-            if (flame_tets[i] < 0 || flame_tets[i] >= ntets) throw WaeError(WAE_ERR_INVALID, "flame tetrahedron out of range");
+        check_indices(flame_tets, nflame, ntets, "flame tetrahedron out of range");
         HIP_CHECK(hipSetDevice(device));
         P2Mesh m(npoints, points, ntets, tets, 0, nullptr);
         const size_t ne = (size_t)nflame * 100;
-        Dev<double> adet((size_t)nflame), vol(1), qv(ne), dg(10);
-        Dev<int> dl((size_t)nflame);
+        Dev<double> adet((size_t)nflame), qv(ne);
+        Dev<int> dl(flame_tets, (size_t)nflame);
         Dev<u64> k0(ne);
-        HIP_CHECK(hipMemcpy(dl.p, flame_tets, (size_t)nflame * sizeof(int), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(p2_det_kernel, dim3((unsigned)((nflame + 255) / 256)), dim3(256), 0, 0, m.pts.p, m.t10.p, dl.p, nflame, adet.p);
+        hipLaunchKernelGGL(p2_det_kernel, grid_for(nflame), dim3(256), 0, 0, m.pts.p, m.t10.p, dl.p, nflame, adet.p);
         HIP_CHECK(hipGetLastError());
-        // flame volume = sum |det J| / 6 (Meshutils.jl:757-767), summed in a fixed tree order on the device
-        size_t tb = 0;
-        HIP_CHECK(hipcub::DeviceReduce::Sum(nullptr, tb, adet.p, vol.p, (int)nflame));
-        Dev<char> tmp(tb);
-        HIP_CHECK(hipcub::DeviceReduce::Sum(tmp.p, tb, adet.p, vol.p, (int)nflame));
-        double det_sum = 0.0;
-        HIP_CHECK(hipMemcpy(&det_sum, vol.p, sizeof(double), hipMemcpyDeviceToHost));
-        const double volume = det_sum / 6.0;
-        if (!(volume > 0.0)) throw WaeError(WAE_ERR_INVALID, "flame domain has no volume");
+        const double volume = flame_volume(adet, nflame);
         if (volume_out) *volume_out = volume;
         const double nlocal = nglobal_scaled / volume;                                 // Helmholtz.jl:325
         // g_b = -nlocal grad(phi_b)(x_ref) . n_ref on the 10 nodes of the reference tetrahedron (Helmholtz.jl:477-482): 10 numbers, on the host
@@ -1160,8 +1150,8 @@ int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points,
             for (int k = 0; k < 4; ++k) acc += lam[k] * (w[k][0] * n_ref[0] + w[k][1] * n_ref[1] + w[k][2] * n_ref[2]);
             g[b] = -nlocal * acc;
         }
-        HIP_CHECK(hipMemcpy(dg.p, g, sizeof(g), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(p2_flame_kernel, dim3((unsigned)((nflame * 10 + 255) / 256)), dim3(256), 0, 0, m.t10.p, dl.p, nflame, adet.p, ref_tet, dg.p,
+        Dev<double> dg(g, 10);
+        hipLaunchKernelGGL(p2_flame_kernel, grid_for(nflame * 10), dim3(256), 0, 0, m.t10.p, dl.p, nflame, adet.p, ref_tet, dg.p,
                            (u64)m.dim, k0.p, qv.p);
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(m.dim, ne, k0, qv, nullptr);
@@ -1183,10 +1173,10 @@ static int p2_shape_sensitivity(int32_t device, int64_t npoints, const double *p
         p2_check_mesh(npoints, ntets, tets, ns, tris);
         if (npair_t > INT_MAX / 3 || npair_s > INT_MAX / 3) throw WaeError(WAE_ERR_INVALID, "too many pairs: 3*npair must fit a 32-bit count");
         if (nodal) check_c_point(npoints, c_t);
-        for (int64_t i = 0; i < npair_t; ++i)
-            if (pair_tet[i] < 0 || pair_tet[i] >= ntets || pair_pt_t[i] < 0 || pair_pt_t[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
-        for (int64_t i = 0; i < npair_s; ++i)
-            if (pair_tri[i] < 0 || pair_tri[i] >= ntris || pair_pt_s[i] < 0 || pair_pt_s[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
+        check_indices(pair_tet, npair_t, ntets, "pair index out of range");
+        check_indices(pair_pt_t, npair_t, npoints, "pair index out of range");
+        check_indices(pair_tri, npair_s, ntris, "pair index out of range");
+        check_indices(pair_pt_s, npair_s, npoints, "pair index out of range");
         if (npair_t == 0 && npair_s == 0) {                                  // empty lists: nothing is launched, nv is checked against a host count
             if (nv != npoints + p2_host_edge_count(npoints, ntets, tets)) throw WaeError(WAE_ERR_INVALID, "nv is not npoints + nedges");
             return (int)WAE_OK;
@@ -1194,41 +1184,14 @@ static int p2_shape_sensitivity(int32_t device, int64_t npoints, const double *p
         HIP_CHECK(hipSetDevice(device));
         P2Mesh m(npoints, points, ntets, tets, ns, tris);
         if (nv != m.dim) throw WaeError(WAE_ERR_INVALID, "nv is not npoints + nedges");
-        Dev<cplx> dv((size_t)nv), dva((size_t)nv);
-        HIP_CHECK(hipMemcpy(dv.p, v, (size_t)nv * sizeof(cplx), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dva.p, v_adj, (size_t)nv * sizeof(cplx), hipMemcpyHostToDevice));
-        Dev<double> dcp(nodal ? (size_t)npoints : 1);
-        if (nodal) HIP_CHECK(hipMemcpy(dcp.p, c_t, (size_t)npoints * sizeof(double), hipMemcpyHostToDevice));
-        if (npair_t > 0) {
-            Dev<int> dpp((size_t)npair_t), dpt((size_t)npair_t);
-            Dev<double> dc(!nodal && c_t ? (size_t)ntets : 1);
-            Dev<cplx> dout((size_t)npair_t * 3);
-            if (!nodal && c_t) HIP_CHECK(hipMemcpy(dc.p, c_t, (size_t)ntets * sizeof(double), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dpp.p, pair_pt_t, (size_t)npair_t * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dpt.p, pair_tet, (size_t)npair_t * sizeof(int), hipMemcpyHostToDevice));
-            const dim3 grid((unsigned)((npair_t + 255) / 256));
-            if (nodal) hipLaunchKernelGGL(p2_shape_tet_kernel<true>, grid, dim3(256), 0, 0, m.pts.p, m.t10.p, dcp.p, npair_t, dpp.p, dpt.p, omega[0], omega[1],
-                                          dv.p, dva.p, h, dout.p);
-            else hipLaunchKernelGGL(p2_shape_tet_kernel<false>, grid, dim3(256), 0, 0, m.pts.p, m.t10.p, c_t ? dc.p : nullptr, npair_t, dpp.p, dpt.p, omega[0],
-                                    omega[1], dv.p, dva.p, h, dout.p);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpy(out_t, dout.p, (size_t)npair_t * 3 * sizeof(cplx), hipMemcpyDeviceToHost));
-        }
-        if (npair_s > 0) {
-            Dev<int> dpp((size_t)npair_s), dpt((size_t)npair_s);
-            Dev<double> dc(!nodal && c_s ? (size_t)ntris : 1);
-            Dev<cplx> dout((size_t)npair_s * 3);
-            if (!nodal && c_s) HIP_CHECK(hipMemcpy(dc.p, c_s, (size_t)ntris * sizeof(double), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dpp.p, pair_pt_s, (size_t)npair_s * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dpt.p, pair_tri, (size_t)npair_s * sizeof(int), hipMemcpyHostToDevice));
-            const dim3 grid((unsigned)((npair_s + 255) / 256));
-            if (nodal) hipLaunchKernelGGL(p2_shape_tri_kernel<true>, grid, dim3(256), 0, 0, m.pts.p, m.s6.p, dcp.p, npair_s, dpp.p, dpt.p, omegaY[0], omegaY[1],
-                                          dv.p, dva.p, h, dout.p);
-            else hipLaunchKernelGGL(p2_shape_tri_kernel<false>, grid, dim3(256), 0, 0, m.pts.p, m.s6.p, c_s ? dc.p : nullptr, npair_s, dpp.p, dpt.p, omegaY[0],
-                                    omegaY[1], dv.p, dva.p, h, dout.p);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpy(out_s, dout.p, (size_t)npair_s * 3 * sizeof(cplx), hipMemcpyDeviceToHost));
-        }
+        Dev<cplx> dv((const cplx *)v, (size_t)nv), dva((const cplx *)v_adj, (size_t)nv);
+        Dev<double> dcp(c_t, nodal ? (size_t)npoints : 0);                   // the nodal field serves both halves
+        if (npair_t > 0)
+            p2_shape_half(nodal ? p2_shape_tet_kernel<true> : p2_shape_tet_kernel<false>, m.pts, m.t10, nodal ? dcp.p : nullptr, c_t, (size_t)ntets, npair_t,
+                          pair_pt_t, pair_tet, omega, dv, dva, h, out_t);
+        if (npair_s > 0)
+            p2_shape_half(nodal ? p2_shape_tri_kernel<true> : p2_shape_tri_kernel<false>, m.pts, m.s6, nodal ? dcp.p : nullptr, c_s, (size_t)ntris, npair_s,
+                          pair_pt_s, pair_tri, omegaY, dv, dva, h, out_s);
         return (int)WAE_OK;
     });
 }
@@ -1265,36 +1228,28 @@ int wae_p2_shape_sensitivity_flame(int32_t device, int64_t npoints, const double
             if (pair_tet[i] < 0 || pair_tet[i] >= ntets) throw WaeError(WAE_ERR_INVALID, "flame tetrahedron out of range");
             if (pair_pt[i] < 0 || pair_pt[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
         }
-        for (int64_t i = 0; i < npair_r; ++i)
-            if (pair_pt_r[i] < 0 || pair_pt_r[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "pair index out of range");
+        check_indices(pair_pt_r, npair_r, npoints, "pair index out of range");
         HIP_CHECK(hipSetDevice(device));
         P2Mesh m(npoints, points, ntets, tets, 0, nullptr);
         if (nv != m.dim) throw WaeError(WAE_ERR_INVALID, "nv is not npoints + nedges");
-        Dev<cplx> dv((size_t)nv), dva((size_t)nv);
-        HIP_CHECK(hipMemcpy(dv.p, v, (size_t)nv * sizeof(cplx), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dva.p, v_adj, (size_t)nv * sizeof(cplx), hipMemcpyHostToDevice));
+        Dev<cplx> dv((const cplx *)v, (size_t)nv), dva((const cplx *)v_adj, (size_t)nv);
         if (npair > 0) {
-            Dev<int> dpp((size_t)npair), dpt((size_t)npair);
+            Dev<int> dpp(pair_pt, (size_t)npair), dpt(pair_tet, (size_t)npair);
             Dev<double> ddet((size_t)npair * 6);
             Dev<cplx> dss((size_t)npair);
-            HIP_CHECK(hipMemcpy(dpp.p, pair_pt, (size_t)npair * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dpt.p, pair_tet, (size_t)npair * sizeof(int), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(p2_shape_flame_kernel, dim3((unsigned)((npair + 255) / 256)), dim3(256), 0, 0, m.pts.p, m.t10.p, npair, dpp.p, dpt.p, dva.p, h,
-                               ddet.p, dss.p);
+            hipLaunchKernelGGL(p2_shape_flame_kernel, grid_for(npair), dim3(256), 0, 0, m.pts.p, m.t10.p, npair, dpp.p, dpt.p, dva.p, h, ddet.p, dss.p);
             HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpy(det_pm, ddet.p, (size_t)npair * 6 * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(ssum, dss.p, (size_t)npair * sizeof(cplx), hipMemcpyDeviceToHost));
+            ddet.to_host(det_pm, (size_t)npair * 6);
+            dss.to_host((cplx *)ssum, (size_t)npair);
         }
-        {
-            Dev<int> dpr((size_t)std::max<int64_t>(npair_r, 1));
-            Dev<cplx> dg((size_t)npair_r * 6 + 1);
-            if (npair_r > 0) HIP_CHECK(hipMemcpy(dpr.p, pair_pt_r, (size_t)npair_r * sizeof(int), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(p2_shape_ref_kernel, dim3((unsigned)((npair_r + 1 + 63) / 64)), dim3(64), 0, 0, m.pts.p, m.t10.p, ref_tet, npair_r, dpr.p,
-                               x_ref[0], x_ref[1], x_ref[2], n_ref[0], n_ref[1], n_ref[2], dv.p, h, dg.p, dg.p + (size_t)npair_r * 6);
-            HIP_CHECK(hipGetLastError());
-            if (npair_r > 0) HIP_CHECK(hipMemcpy(g_pm, dg.p, (size_t)npair_r * 6 * sizeof(cplx), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(g0, dg.p + (size_t)npair_r * 6, sizeof(cplx), hipMemcpyDeviceToHost));
-        }
+        const size_t nr = (size_t)npair_r;
+        Dev<int> dpr(pair_pt_r, nr);
+        Dev<cplx> dg(nr * 6 + 1);
+        hipLaunchKernelGGL(p2_shape_ref_kernel, dim3((unsigned)((nr + 1 + 63) / 64)), dim3(64), 0, 0, m.pts.p, m.t10.p, ref_tet, npair_r, dpr.p, x_ref[0], x_ref[1],
+                           x_ref[2], n_ref[0], n_ref[1], n_ref[2], dv.p, h, dg.p, dg.p + nr * 6);
+        HIP_CHECK(hipGetLastError());
+        dg.to_host((cplx *)g_pm, nr * 6);
+        dg.to_host((cplx *)g0, 1, nr * 6);
         return (int)WAE_OK;
     });
 }

@@ -12,30 +12,16 @@
 //      triplets_to_csr (assemble.hip) sorts all parts at once (stable radix sort), sums the duplicates that folding creates in input
 //      order (reduce-by-key) -- no atomics, the same bits on every call -- and returns one CSR of nparts * dim rows, which the host cuts
 //      into the parts.
-#include <hipcub/hipcub.hpp>
-
 #include <climits>
 #include <memory>
 #include <vector>
 
 #include "edge_keys.h"
-#include "wae_internal.h"
+#include "mesh_host.h"
 
 namespace {
 
 typedef unsigned long long u64;
-
-template <class F> int wae_guarded(F &&f) {
-    try {
-        return f();
-    } catch (const WaeError &e) {
-        wae_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        wae_set_error(e.what());
-        return WAE_ERR_INVALID;
-    }
-}
 
 struct BlochNumbering {
     int64_t npoints = 0, ndof = 0, dim = 0, nedges = 0, nimage_edges = 0, naxis_edges = 0;
@@ -111,19 +97,6 @@ __global__ __launch_bounds__(256) void bloch_fold_keys_kernel(const int *__restr
     }
 }
 
-int sum_ints(const int *d, int n) {
-    Dev<int> out(1);
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceReduce::Sum(nullptr, tb, d, out.p, n));
-    Dev<char> tmp(tb);
-    HIP_CHECK(hipcub::DeviceReduce::Sum(tmp.p, tb, d, out.p, n));
-    int h = 0;
-    HIP_CHECK(hipMemcpy(&h, out.p, sizeof(int), hipMemcpyDeviceToHost));
-    return h;
-}
-
-unsigned grid_for(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 8192)); }
-
 }  // namespace
 
 extern "C" {
@@ -141,11 +114,10 @@ int wae_bloch_numbering(int32_t device, int64_t npoints, int64_t ntets, const in
         HIP_CHECK(hipSetDevice(device));
         std::unique_ptr<BlochNumbering> H(new BlochNumbering);
         H->npoints = npoints;
-        Dev<int> dtets((size_t)ntets * 4);
+        Dev<int> dtets(tets, order == 2 ? (size_t)ntets * 4 : 0);
         Dev<u64> ek((size_t)ntets * 6);
         int64_t ne = 0;
         if (order == 2) {
-            HIP_CHECK(hipMemcpy(dtets.p, tets, (size_t)ntets * 4 * sizeof(int), hipMemcpyHostToDevice));
             ne = p2_edge_list(npoints, ntets, dtets.p, ek);                 // (checks npoints + nedges <= INT_MAX)
         }
         const int64_t ndof = npoints + ne;
@@ -153,28 +125,26 @@ int wae_bloch_numbering(int32_t device, int64_t npoints, int64_t ntets, const in
         Dev<int> cell((size_t)ndof), flags((size_t)ndof);
         int nkeep = 0;
         if (ne > 0) {
-            hipLaunchKernelGGL(bloch_edge_kernel, dim3(grid_for((size_t)ne)), dim3(256), 0, 0, ek.p, ne, (u64)npoints, (int)nsector, (int)naxis, edges.p,
+            hipLaunchKernelGGL(bloch_edge_kernel, grid_for((size_t)ne, GRID_STRIDE_CAP), dim3(256), 0, 0, ek.p, ne, (u64)npoints, (int)nsector, (int)naxis, edges.p,
                                keep.p, twin.p, eflags.p, cnt.p, cnt.p + ne, cnt.p + 2 * ne);
             HIP_CHECK(hipGetLastError());
-            const int nmissing = sum_ints(cnt.p, (int)ne), nimgtwin = sum_ints(cnt.p + ne, (int)ne);
+            const int nmissing = device_sum(cnt.p, (int)ne), nimgtwin = device_sum(cnt.p + ne, (int)ne);
             if (nmissing)
                 throw WaeError(WAE_ERR_INVALID, "the cell is not periodic: " + std::to_string(nmissing) + " image edge(s) whose twin is no edge of the mesh");
             if (nimgtwin) throw WaeError(WAE_ERR_INVALID, std::to_string(nimgtwin) + " image edge(s) whose twin is an image edge itself");
-            H->naxis_edges = sum_ints(cnt.p + 2 * ne, (int)ne);
-            size_t tb = 0;
-            HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep.p, rank.p, (int)ne));
-            Dev<char> tmp(tb);
-            HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, keep.p, rank.p, (int)ne));
-            nkeep = sum_ints(keep.p, (int)ne);
+            H->naxis_edges = device_sum(cnt.p + 2 * ne, (int)ne);
+            DevBuf<char> tmp;
+            exclusive_sum(keep.p, rank.p, (int)ne, tmp);
+            nkeep = device_sum(keep.p, (int)ne);
         }
-        hipLaunchKernelGGL(bloch_number_kernel, dim3(grid_for((size_t)ndof)), dim3(256), 0, 0, npoints, ne, (int)nsector, (int)naxis, rank.p, twin.p,
+        hipLaunchKernelGGL(bloch_number_kernel, grid_for((size_t)ndof, GRID_STRIDE_CAP), dim3(256), 0, 0, npoints, ne, (int)nsector, (int)naxis, rank.p, twin.p,
                            eflags.p, cell.p, flags.p);
         HIP_CHECK(hipGetLastError());
         H->ndof = ndof; H->nedges = ne; H->nimage_edges = ne - nkeep; H->dim = nsector + nkeep;
         H->cell_dof.resize((size_t)ndof); H->flags.resize((size_t)ndof); H->edges.resize((size_t)ne * 2);
-        HIP_CHECK(hipMemcpy(H->cell_dof.data(), cell.p, (size_t)ndof * sizeof(int), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(H->flags.data(), flags.p, (size_t)ndof * sizeof(int), hipMemcpyDeviceToHost));
-        if (ne) HIP_CHECK(hipMemcpy(H->edges.data(), edges.p, (size_t)ne * 2 * sizeof(int), hipMemcpyDeviceToHost));
+        cell.to_host(H->cell_dof.data(), (size_t)ndof);
+        flags.to_host(H->flags.data(), (size_t)ndof);
+        edges.to_host(H->edges.data(), (size_t)ne * 2);
         *out = H.release();
         return WAE_OK;
     });
@@ -221,8 +191,7 @@ int wae_bloch_fold(int32_t device, int64_t n, const int32_t *rowptr, const int32
             if (rowptr[r + 1] < rowptr[r]) throw WaeError(WAE_ERR_INVALID, "rowptr decreases");
         const size_t nnz = (size_t)rowptr[n];
         if (nnz && !col) throw WaeError(WAE_ERR_INVALID, "bad argument");
-        for (size_t e = 0; e < nnz; ++e)
-            if (col[e] < 0 || col[e] >= n) throw WaeError(WAE_ERR_INVALID, "column index outside 0..n-1");
+        check_indices(col, (int64_t)nnz, n, "column index outside 0..n-1");
         for (int64_t d = 0; d < n; ++d) {
             if (cell_dof[d] < 0 || cell_dof[d] >= dim) throw WaeError(WAE_ERR_INVALID, "cell_dof holds an index outside 0..dim-1");
             if (flags[d] & ~(WAE_BLOCH_IMAGE | WAE_BLOCH_AXIS)) throw WaeError(WAE_ERR_INVALID, "flags holds an unknown bit");
@@ -235,17 +204,11 @@ int wae_bloch_fold(int32_t device, int64_t n, const int32_t *rowptr, const int32
         }
         if (nnz) {
             HIP_CHECK(hipSetDevice(device));
-            Dev<int> drow((size_t)n + 1), dcol(nnz), didx(nnz), dcell((size_t)n), dflags((size_t)n);
-            Dev<double> a(nnz), b(v1 ? nnz : 1);
+            Dev<int> drow(rowptr, (size_t)n + 1), dcol(col, nnz), didx(nnz), dcell(cell_dof, (size_t)n), dflags(flags, (size_t)n);
+            Dev<double> a(v0, nnz), b(v1, v1 ? nnz : 0);
             Dev<u64> keys(nnz);
-            HIP_CHECK(hipMemcpy(drow.p, rowptr, ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dcol.p, col, nnz * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dcell.p, cell_dof, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dflags.p, flags, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(a.p, v0, nnz * sizeof(double), hipMemcpyHostToDevice));
-            if (v1) HIP_CHECK(hipMemcpy(b.p, v1, nnz * sizeof(double), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(bloch_expand_rows_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, 0, drow.p, n, didx.p);
-            hipLaunchKernelGGL(bloch_fold_keys_kernel, dim3(grid_for(nnz)), dim3(256), 0, 0, didx.p, dcol.p, nnz, dcell.p, dflags.p, (u64)dim, (int)nparts,
+            hipLaunchKernelGGL(bloch_expand_rows_kernel, grid_for((size_t)n, GRID_STRIDE_CAP), dim3(256), 0, 0, drow.p, n, didx.p);
+            hipLaunchKernelGGL(bloch_fold_keys_kernel, grid_for(nnz, GRID_STRIDE_CAP), dim3(256), 0, 0, didx.p, dcol.p, nnz, dcell.p, dflags.p, (u64)dim, (int)nparts,
                                keys.p);
             HIP_CHECK(hipGetLastError());
             std::unique_ptr<P1Handle> all(triplets_to_csr(dim * nparts, nnz, keys, a, v1 ? &b : nullptr));

@@ -125,17 +125,4 @@ static void slot_coeffs(const wae_family *h, const std::vector<int> &slot_plane,
     for (int q = 0; q < h->nplanes; ++q) dst[q] = cplx{pc[slot_plane[q]].real(), pc[slot_plane[q]].imag()};
 }
 
-template <class F> static int guarded(F &&f) {
-    try {
-        return f();
-    } catch (const WaeError &e) {
-        wae_set_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        wae_set_error("out of host memory");
-        return WAE_ERR_INVALID;
-    } catch (const std::exception &e) {
-        wae_set_error(e.what());
-        return WAE_ERR_INVALID;
-    }
-}
+template <class F> static int guarded(F &&f) { return wae_guarded(f); }       // the one definition: wae_internal.h

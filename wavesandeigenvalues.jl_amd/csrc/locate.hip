@@ -25,26 +25,12 @@
 // average), the points outside the box leave at once, and a million points fill the device without any sharing of a point among lanes;
 // the lanes of a wavefront that fall into the same cell read the same candidates (one fetch).  A wavefront per point with a ballot over 64
 // candidates would test the whole list every time and idle most lanes on lists shorter than 64.
-#include <hipcub/hipcub.hpp>
-
 #include <climits>
 #include <memory>
 
-#include "wae_internal.h"
+#include "mesh_host.h"
 
 namespace {
-
-template <class F> int wae_guarded(F &&f) {
-    try {
-        return f();
-    } catch (const WaeError &e) {
-        wae_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        wae_set_error(e.what());
-        return WAE_ERR_INVALID;
-    }
-}
 
 constexpr double LOC_TOL_MAX = 1e-6;
 constexpr double LOC_PAD = 4.0 * LOC_TOL_MAX + 9.313225746154785e-10;          // 4 tol_max + 2^-30
@@ -56,8 +42,6 @@ struct LocGrid {
     double lo[3], hi[3], inv[3], pad[3];
     int dims[3];
 };
-
-inline dim3 loc_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 __device__ inline int loc_axis_cell(double x, double lo, double inv, int dim) {
 #pragma clang fp contract(off)
@@ -353,7 +337,7 @@ void loc_build(Locator &H, int64_t cell_target) {
         hipLaunchKernelGGL(loc_box_final_kernel, dim3(1), dim3(64), 0, 0, partial.p, nblk, box.p);
         HIP_CHECK(hipGetLastError());
         double hb[6];
-        HIP_CHECK(hipMemcpy(hb, box.p, sizeof(hb), hipMemcpyDeviceToHost));
+        box.to_host(hb, 6);
         for (int k = 0; k < 3; ++k) {
             H.G.lo[k] = hb[k];
             H.G.hi[k] = hb[3 + k];
@@ -367,16 +351,14 @@ void loc_build(Locator &H, int64_t cell_target) {
     while ((int64_t)dims[0] * dims[1] * dims[2] > LOC_CELLS_PER_TET * nt)
         for (int k = 0; k < 3; ++k) dims[k] = (dims[k] + 1) / 2;
     Dev<long long> len((size_t)nt + 1), off((size_t)nt + 1);
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, len.p, off.p, (int)(nt + 1)));
-    Dev<char> tmp(tb);
+    DevBuf<char> tmp;                                                // (allocated by the first scan, kept for the others)
     long long nrefs = 0;
     for (;;) {
         loc_set_dims(H.G, dims);
-        hipLaunchKernelGGL(loc_count_kernel, loc_grid(nt + 1), dim3(256), 0, 0, H.G, H.pts.p, H.tets.p, nt, len.p);
+        hipLaunchKernelGGL(loc_count_kernel, grid_for(nt + 1), dim3(256), 0, 0, H.G, H.pts.p, H.tets.p, nt, len.p);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, len.p, off.p, (int)(nt + 1)));
-        HIP_CHECK(hipMemcpy(&nrefs, off.p + nt, sizeof(long long), hipMemcpyDeviceToHost));
+        exclusive_sum(len.p, off.p, (int)(nt + 1), tmp);
+        off.to_host(&nrefs, 1, (size_t)nt);
         if (nrefs < nt) throw WaeError(WAE_ERR_HIP, "locator: the scan returned an impossible pair count");
         if (nrefs <= 32 * nt || (dims[0] == 1 && dims[1] == 1 && dims[2] == 1)) break;
         for (int k = 0; k < 3; ++k) dims[k] = (dims[k] + 1) / 2;
@@ -387,23 +369,22 @@ void loc_build(Locator &H, int64_t cell_target) {
     Dev<int> v0((size_t)nrefs);
     H.cell_tet.alloc((size_t)nrefs);
     H.cell_ptr.alloc((size_t)ncells + 1);
-    hipLaunchKernelGGL(loc_fill_kernel, loc_grid(nt), dim3(256), 0, 0, H.G, H.pts.p, H.tets.p, nt, off.p, k0.p, v0.p);
+    hipLaunchKernelGGL(loc_fill_kernel, grid_for(nt), dim3(256), 0, 0, H.G, H.pts.p, H.tets.p, nt, off.p, k0.p, v0.p);
     HIP_CHECK(hipGetLastError());
-    int bits = 1;
-    while (bits < 32 && ((uint64_t)ncells >> bits)) ++bits;
-    size_t sb = 0, rb = 0;
+    const int bits = key_bits((uint64_t)ncells);                     // (at most 31: ncells <= 2^30)
     Dev<int> lens((size_t)ncells), dmax(1);
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, k0.p, k1.p, v0.p, H.cell_tet.p, cnt, 0, bits));
-    HIP_CHECK(hipcub::DeviceReduce::Max(nullptr, rb, lens.p, dmax.p, (int)ncells));
-    Dev<char> tmp2(std::max(sb, rb));
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp2.p, sb, k0.p, k1.p, v0.p, H.cell_tet.p, cnt, 0, bits));
-    hipLaunchKernelGGL(loc_ptr_kernel, loc_grid(ncells + 1), dim3(256), 0, 0, k1.p, cnt, ncells, H.cell_ptr.p);
+    auto sort = [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k0.p, k1.p, v0.p, H.cell_tet.p, cnt, 0, bits); };
+    auto longest = [&](void *t, size_t &b) { return hipcub::DeviceReduce::Max(t, b, lens.p, dmax.p, (int)ncells); };
+    DevBuf<char> tmp2;
+    cub_reserve(tmp2, sort, longest);
+    cub_run(sort, tmp2);
+    hipLaunchKernelGGL(loc_ptr_kernel, grid_for(ncells + 1), dim3(256), 0, 0, k1.p, cnt, ncells, H.cell_ptr.p);
     HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(loc_len_kernel, loc_grid(ncells), dim3(256), 0, 0, H.cell_ptr.p, ncells, lens.p);
+    hipLaunchKernelGGL(loc_len_kernel, grid_for(ncells), dim3(256), 0, 0, H.cell_ptr.p, ncells, lens.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipcub::DeviceReduce::Max(tmp2.p, rb, lens.p, dmax.p, (int)ncells));
+    cub_run(longest, tmp2);
     int hmax = 0;
-    HIP_CHECK(hipMemcpy(&hmax, dmax.p, sizeof(int), hipMemcpyDeviceToHost));
+    dmax.to_host(&hmax, 1);
     H.nrefs = nrefs;
     H.maxlen = hmax;
 }
@@ -435,14 +416,9 @@ struct LocQuery {                       // the per-point inputs of a weights / s
     DevBuf<double> x, n;
     DevBuf<int> tet;
     LocQuery(int64_t nq, const double *hx, const int32_t *ht, const double *hn) {
-        x.alloc((size_t)nq * 3);
-        tet.alloc((size_t)nq);
-        HIP_CHECK(hipMemcpy(x.p, hx, (size_t)nq * 3 * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(tet.p, ht, (size_t)nq * sizeof(int), hipMemcpyHostToDevice));
-        if (hn) {
-            n.alloc((size_t)nq * 3);
-            HIP_CHECK(hipMemcpy(n.p, hn, (size_t)nq * 3 * sizeof(double), hipMemcpyHostToDevice));
-        }
+        x.from_host(hx, (size_t)nq * 3);
+        tet.from_host(ht, (size_t)nq);
+        if (hn) n.from_host(hn, (size_t)nq * 3);
     }
 };
 
@@ -455,18 +431,15 @@ int wae_locator_create(int32_t device, int64_t npoints, const double *points, in
         if (npoints < 0 || ntets < 0 || cell_target < 0) throw WaeError(WAE_ERR_INVALID, "a count is negative");
         if (!(out && points && tets && npoints > 0 && ntets > 0)) throw WaeError(WAE_ERR_INVALID, "bad argument");
         if (npoints > INT_MAX || ntets > INT_MAX / 32) throw WaeError(WAE_ERR_INVALID, "npoints or 32*ntets does not fit a 32-bit index");
-        for (int64_t i = 0; i < ntets * 4; ++i)
-            if (tets[i] < 0 || tets[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "tetrahedron refers to a point outside 0..npoints-1");
+        check_tets(tets, ntets, npoints);
         loc_check_finite(points, npoints * 3, "points");
         HIP_CHECK(hipSetDevice(device));
         std::unique_ptr<Locator> H(new Locator);
         H->device = device;
         H->np = npoints;
         H->nt = ntets;
-        H->pts.alloc((size_t)npoints * 3);
-        H->tets.alloc((size_t)ntets * 4);
-        HIP_CHECK(hipMemcpy(H->pts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(H->tets.p, tets, (size_t)ntets * 4 * sizeof(int), hipMemcpyHostToDevice));
+        H->pts.from_host(points, (size_t)npoints * 3);
+        H->tets.from_host(tets, (size_t)ntets * 4);
         loc_build(*H, cell_target);
         *out = H.release();
         return WAE_OK;
@@ -497,14 +470,13 @@ int wae_locator_find(const void *h, int64_t nq, const double *x, double tol, int
         HIP_CHECK(hipSetDevice(H.device));
         DevBuf<double> dx, dl;
         DevBuf<int> dt;
-        dx.alloc((size_t)nq * 3);
+        dx.from_host(x, (size_t)nq * 3);
         dt.alloc((size_t)nq);
         if (lambda) dl.alloc((size_t)nq * 4);
-        HIP_CHECK(hipMemcpy(dx.p, x, (size_t)nq * 3 * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(loc_find_kernel, loc_grid(nq), dim3(256), 0, 0, H.G, H.pts.p, H.tets.p, H.cell_ptr.p, H.cell_tet.p, nq, dx.p, tol, dt.p, dl.p);
+        hipLaunchKernelGGL(loc_find_kernel, grid_for(nq), dim3(256), 0, 0, H.G, H.pts.p, H.tets.p, H.cell_ptr.p, H.cell_tet.p, nq, dx.p, tol, dt.p, dl.p);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(tet, dt.p, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost));
-        if (lambda) HIP_CHECK(hipMemcpy(lambda, dl.p, (size_t)nq * 4 * sizeof(double), hipMemcpyDeviceToHost));
+        dt.to_host(tet, (size_t)nq);
+        dl.to_host(lambda, (size_t)nq * 4);
         return WAE_OK;
     });
 }
@@ -514,12 +486,10 @@ int wae_locator_set_p2(void *h, int64_t ndof, const int32_t *tets10) {
         Locator &H = const_cast<Locator &>(loc_handle(h));
         if (ndof < 0) throw WaeError(WAE_ERR_INVALID, "ndof is negative");
         if (!tets10 || ndof < 1 || ndof > INT_MAX) throw WaeError(WAE_ERR_INVALID, "bad argument");
-        for (int64_t i = 0; i < H.nt * 10; ++i)
-            if (tets10[i] < 0 || tets10[i] >= ndof) throw WaeError(WAE_ERR_INVALID, "tets10 holds an entry outside 0..ndof-1");
+        check_indices(tets10, H.nt * 10, ndof, "tets10 holds an entry outside 0..ndof-1");
         HIP_CHECK(hipSetDevice(H.device));
         DevBuf<int> t10;
-        t10.alloc((size_t)H.nt * 10);
-        HIP_CHECK(hipMemcpy(t10.p, tets10, (size_t)H.nt * 10 * sizeof(int), hipMemcpyHostToDevice));
+        t10.from_host(tets10, (size_t)H.nt * 10);
         H.tets10 = std::move(t10);
         H.ndof = ndof;
         return WAE_OK;
@@ -542,12 +512,12 @@ int wae_locator_weights(const void *h, int32_t order, int32_t kind, int64_t nq, 
         di.alloc((size_t)nq * nw);
         dv.alloc((size_t)nq * nw);
         if (order == 1)
-            hipLaunchKernelGGL(loc_weights_kernel<4>, loc_grid(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, di.p, dv.p);
+            hipLaunchKernelGGL(loc_weights_kernel<4>, grid_for(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, di.p, dv.p);
         else
-            hipLaunchKernelGGL(loc_weights_kernel<10>, loc_grid(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, di.p, dv.p);
+            hipLaunchKernelGGL(loc_weights_kernel<10>, grid_for(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, di.p, dv.p);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(idx, di.p, (size_t)nq * nw * sizeof(int), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(val, dv.p, (size_t)nq * nw * sizeof(double), hipMemcpyDeviceToHost));
+        di.to_host(idx, (size_t)nq * nw);
+        dv.to_host(val, (size_t)nq * nw);
         return WAE_OK;
     });
 }
@@ -564,17 +534,16 @@ int wae_locator_sample(const void *h, int32_t order, int32_t kind, int64_t nq, c
         HIP_CHECK(hipSetDevice(H.device));
         LocQuery Q(nq, x, tet, kind ? n : nullptr);
         DevBuf<cplx> dV, dO;
-        dV.alloc((size_t)d * (size_t)ncols);
+        dV.from_host((const cplx *)V, (size_t)d * (size_t)ncols);
         dO.alloc((size_t)nq * (size_t)ncols);
-        HIP_CHECK(hipMemcpy(dV.p, V, (size_t)d * (size_t)ncols * sizeof(cplx), hipMemcpyHostToDevice));
         if (order == 1)
-            hipLaunchKernelGGL(loc_sample_kernel<4>, loc_grid(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, d,
+            hipLaunchKernelGGL(loc_sample_kernel<4>, grid_for(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, d,
                                (int)ncols, dV.p, dO.p);
         else
-            hipLaunchKernelGGL(loc_sample_kernel<10>, loc_grid(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, d,
+            hipLaunchKernelGGL(loc_sample_kernel<10>, grid_for(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, d,
                                (int)ncols, dV.p, dO.p);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dO.p, (size_t)nq * (size_t)ncols * sizeof(cplx), hipMemcpyDeviceToHost));
+        dO.to_host((cplx *)out, (size_t)nq * (size_t)ncols);
         return WAE_OK;
     });
 }

@@ -28,32 +28,16 @@
 // The P2 prolongation between the levels ("P2 prolongation between two levels" below): the first P2 entry called on a handle numbers the
 // P2 edges of every level and builds every step as a CSR matrix in HBM; wae_octosplit_prolong_p2 applies it, wae_octosplit_prolongator_p2
 // copies it out.
-#include <hipcub/hipcub.hpp>
-
 #include <climits>
 #include <memory>
 #include <vector>
 
 #include "edge_keys.h"
-#include "wae_internal.h"
+#include "mesh_host.h"
 
 namespace {
 
 typedef unsigned long long u64;
-
-template <class F> int wae_guarded(F &&f) {
-    try {
-        return f();
-    } catch (const WaeError &e) {
-        wae_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        wae_set_error(e.what());
-        return WAE_ERR_INVALID;
-    }
-}
-
-inline dim3 octo_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 __global__ __launch_bounds__(256) void octo_edge_keys_kernel(const int *__restrict__ tets, int64_t nt, u64 np, u64 *__restrict__ keys) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -381,12 +365,6 @@ struct Octo {
     std::vector<OctoP2Level> p2;                     // empty until a P2 entry is called
 };
 
-int octo_bits(u64 x) {          // bits that hold every value below x
-    int b = 1;
-    while (b < 64 && (x >> b)) ++b;
-    return b;
-}
-
 // children (n of them, NV vertices each, with their keys) -> the sorted list `out` and the labels; bad[flag] set on equal neighbours
 template <int NV>
 void octo_sort_children(int64_t n, const int *child, u64 *hi, u64 *lo, int end_bit_hi, int end_bit_lo, int *out, int *labels, int *bad, int flag) {
@@ -394,17 +372,17 @@ void octo_sort_children(int64_t n, const int *child, u64 *hi, u64 *lo, int end_b
     const int cnt = (int)n;
     Dev<int> i0((size_t)n), i1((size_t)n), i2((size_t)n);
     Dev<u64> k1((size_t)n), k2((size_t)n);
-    hipLaunchKernelGGL(octo_iota_kernel, octo_grid(n), dim3(256), 0, 0, i0.p, n);
+    hipLaunchKernelGGL(octo_iota_kernel, grid_for(n), dim3(256), 0, 0, i0.p, n);
     HIP_CHECK(hipGetLastError());
-    size_t tb = 0, tb2 = 0;
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, lo, k1.p, i0.p, i1.p, cnt, 0, end_bit_lo));
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, k2.p, k1.p, i1.p, i2.p, cnt, 0, end_bit_hi));
-    Dev<char> tmp(std::max(tb, tb2));
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, lo, k1.p, i0.p, i1.p, cnt, 0, end_bit_lo));
-    hipLaunchKernelGGL(octo_gather_keys_kernel, octo_grid(n), dim3(256), 0, 0, hi, i1.p, n, k2.p);
+    auto by_lo = [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, lo, k1.p, i0.p, i1.p, cnt, 0, end_bit_lo); };
+    auto by_hi = [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, k2.p, k1.p, i1.p, i2.p, cnt, 0, end_bit_hi); };
+    DevBuf<char> tmp;
+    cub_reserve(tmp, by_lo, by_hi);
+    cub_run(by_lo, tmp);
+    hipLaunchKernelGGL(octo_gather_keys_kernel, grid_for(n), dim3(256), 0, 0, hi, i1.p, n, k2.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb2, k2.p, k1.p, i1.p, i2.p, cnt, 0, end_bit_hi));
-    hipLaunchKernelGGL(octo_place_kernel<NV>, octo_grid(n), dim3(256), 0, 0, child, i2.p, k1.p, lo, n, out, labels, bad, flag);
+    cub_run(by_hi, tmp);
+    hipLaunchKernelGGL(octo_place_kernel<NV>, grid_for(n), dim3(256), 0, 0, child, i2.p, k1.p, lo, n, out, labels, bad, flag);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -413,22 +391,11 @@ void octo_refine(const OctoLevel &in, OctoLevel &out, int level) {
     const std::string at = " (level " + std::to_string(level) + ")";
     if (nt * 8 > INT_MAX || ns * 4 > INT_MAX) throw WaeError(WAE_ERR_INVALID, "8*ntets or 4*ntris does not fit a 32-bit index" + at);
     const int nk = (int)(nt * 6);
-    Dev<u64> k0((size_t)nk), k1((size_t)nk), ek((size_t)nk);
-    Dev<int> dnum(1), bad(3);
-    hipLaunchKernelGGL(octo_edge_keys_kernel, octo_grid(nt), dim3(256), 0, 0, in.tets.p, nt, (u64)np, k0.p);
+    Dev<u64> k0((size_t)nk), ek((size_t)nk);
+    Dev<int> bad(3);
+    hipLaunchKernelGGL(octo_edge_keys_kernel, grid_for(nt), dim3(256), 0, 0, in.tets.p, nt, (u64)np, k0.p);
     HIP_CHECK(hipGetLastError());
-    const int bits = octo_bits((u64)np * (u64)np);
-    int ne = 0;
-    {
-        size_t tb = 0, tb2 = 0;
-        HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, k0.p, k1.p, nk, 0, bits));
-        HIP_CHECK(hipcub::DeviceSelect::Unique(nullptr, tb2, k1.p, ek.p, dnum.p, nk));
-        Dev<char> tmp(std::max(tb, tb2));
-        HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(tmp.p, tb, k0.p, k1.p, nk, 0, bits));
-        HIP_CHECK(hipcub::DeviceSelect::Unique(tmp.p, tb2, k1.p, ek.p, dnum.p, nk));
-        HIP_CHECK(hipMemcpy(&ne, dnum.p, sizeof(int), hipMemcpyDeviceToHost));
-    }
-    if (ne <= 0 || ne > nk) throw WaeError(WAE_ERR_HIP, "edge list: unique pass returned an impossible count");
+    const int ne = sorted_unique_keys(k0, nk, key_bits((u64)np * (u64)np), ek);
     if (np + (int64_t)ne > INT_MAX) throw WaeError(WAE_ERR_INVALID, "npoints + nedges does not fit a 32-bit index" + at);
     out.np = np + ne; out.nt = nt * 8; out.ns = ns * 4;
     out.pts.alloc((size_t)out.np * 3);
@@ -438,19 +405,19 @@ void octo_refine(const OctoLevel &in, OctoLevel &out, int level) {
     out.tet_labels.alloc((size_t)out.nt);
     out.tri_labels.alloc((size_t)out.ns);
     HIP_CHECK(hipMemcpy(out.pts.p, in.pts.p, (size_t)np * 3 * sizeof(double), hipMemcpyDeviceToDevice));
-    hipLaunchKernelGGL(octo_midpoints_kernel, octo_grid(ne), dim3(256), 0, 0, ek.p, (int64_t)ne, (u64)np, out.pts.p, out.parents.p);
+    hipLaunchKernelGGL(octo_midpoints_kernel, grid_for(ne), dim3(256), 0, 0, ek.p, (int64_t)ne, (u64)np, out.pts.p, out.parents.p);
     HIP_CHECK(hipGetLastError());
     Dev<int> tchild((size_t)out.nt * 4), schild((size_t)out.ns * 3);
     Dev<u64> thi((size_t)out.nt), tlo((size_t)out.nt), shi((size_t)out.ns), slo((size_t)out.ns);
     HIP_CHECK(hipMemset(bad.p, 0, 3 * sizeof(int)));
-    hipLaunchKernelGGL(octo_children_kernel, octo_grid(nt + ns), dim3(256), 0, 0, in.tets.p, nt, in.tris.p, ns, ek.p, (int64_t)ne, (u64)np, out.pts.p,
+    hipLaunchKernelGGL(octo_children_kernel, grid_for(nt + ns), dim3(256), 0, 0, in.tets.p, nt, in.tris.p, ns, ek.p, (int64_t)ne, (u64)np, out.pts.p,
                        tchild.p, thi.p, tlo.p, schild.p, shi.p, slo.p, bad.p);
     HIP_CHECK(hipGetLastError());
-    const int vb = octo_bits((u64)out.np);          // bits of a point number of the new level
+    const int vb = key_bits((u64)out.np);          // bits of a point number of the new level
     octo_sort_children<4>(out.nt, tchild.p, thi.p, tlo.p, 31 + vb, 31 + vb, out.tets.p, out.tet_labels.p, bad.p, 1);
     octo_sort_children<3>(out.ns, schild.p, shi.p, slo.p, 31 + vb, vb, out.tris.p, out.tri_labels.p, bad.p, 2);
     int hbad[3] = {0, 0, 0};
-    HIP_CHECK(hipMemcpy(hbad, bad.p, 3 * sizeof(int), hipMemcpyDeviceToHost));
+    bad.to_host(hbad, 3);
     if (hbad[0]) throw WaeError(WAE_ERR_INVALID, "a boundary triangle has an edge that is no tetrahedron's edge" + at);
     if (hbad[1]) throw WaeError(WAE_ERR_INVALID, "two children of the tetrahedra are equal: a tetrahedron is listed twice or repeats a point" + at);
     if (hbad[2]) throw WaeError(WAE_ERR_INVALID, "two children of the triangles are equal: a triangle is listed twice or repeats a point" + at);
@@ -463,10 +430,6 @@ const OctoLevel &octo_level(const void *h, int32_t level) {
     return H->lv[(size_t)level];
 }
 
-template <class T> void octo_copy_out(T *dst, const DevBuf<T> &src, size_t count) {
-    if (dst && count) HIP_CHECK(hipMemcpy(dst, src.p, count * sizeof(T), hipMemcpyDeviceToHost));
-}
-
 // the step l -> l + 1: row lengths by kind, an exclusive scan, one thread per row to fill it
 void octo_p2_step(const OctoLevel &F, const OctoLevel &T, const OctoP2Level &cf, const OctoP2Level &ct, OctoP2Level &out, int level) {
     const std::string at = " (P2 prolongator of level " + std::to_string(level) + ")";
@@ -474,25 +437,23 @@ void octo_p2_step(const OctoLevel &F, const OctoLevel &T, const OctoP2Level &cf,
     if (nd + 1 > INT_MAX) throw WaeError(WAE_ERR_INVALID, "npoints + nedges + 1 does not fit a 32-bit index" + at);
     DevBuf<long long> len, ptr64;
     len.alloc((size_t)nd + 1); ptr64.alloc((size_t)nd + 1);
-    hipLaunchKernelGGL(octo_p2_count_kernel, octo_grid(nd + 1), dim3(256), 0, 0, F.np, T.np, nd, ct.ek.p, T.parents.p, len.p);
+    hipLaunchKernelGGL(octo_p2_count_kernel, grid_for(nd + 1), dim3(256), 0, 0, F.np, T.np, nd, ct.ek.p, T.parents.p, len.p);
     HIP_CHECK(hipGetLastError());
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, len.p, ptr64.p, (int)(nd + 1)));
-    Dev<char> tmp(tb);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, len.p, ptr64.p, (int)(nd + 1)));
+    DevBuf<char> tmp;
+    exclusive_sum(len.p, ptr64.p, (int)(nd + 1), tmp);
     long long nnz = 0;
-    HIP_CHECK(hipMemcpy(&nnz, ptr64.p + nd, sizeof(long long), hipMemcpyDeviceToHost));
+    ptr64.to_host(&nnz, 1, (size_t)nd);
     if (nnz < nd || nnz > 10 * nd) throw WaeError(WAE_ERR_HIP, "P2 prolongator: the scan returned an impossible entry count" + at);
     if (nnz > INT_MAX) throw WaeError(WAE_ERR_INVALID, "the prolongator's entries do not fit a 32-bit index" + at);
     out.nnz = nnz;
     out.ptr.alloc((size_t)nd + 1); out.col.alloc((size_t)nnz); out.val.alloc((size_t)nnz);
     Dev<int> bad(1);
     HIP_CHECK(hipMemset(bad.p, 0, sizeof(int)));
-    hipLaunchKernelGGL(octo_p2_fill_kernel, octo_grid(nd + 1), dim3(256), 0, 0, F.np, T.np, nd, cf.ek.p, cf.ne, ct.ek.p, T.parents.p, ptr64.p,
+    hipLaunchKernelGGL(octo_p2_fill_kernel, grid_for(nd + 1), dim3(256), 0, 0, F.np, T.np, nd, cf.ek.p, cf.ne, ct.ek.p, T.parents.p, ptr64.p,
                        out.ptr.p, out.col.p, out.val.p, bad.p);
     HIP_CHECK(hipGetLastError());
     int hbad = 0;
-    HIP_CHECK(hipMemcpy(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost));
+    bad.to_host(&hbad, 1);
     if (hbad) throw WaeError(WAE_ERR_HIP, "P2 prolongator: an edge of the finer level does not come from the coarser one" + at);
 }
 
@@ -542,9 +503,9 @@ int wae_octosplit_prolongator_p2(void *h, int32_t from_level, int32_t *ptr, int3
         HIP_CHECK(hipSetDevice(H->device));
         const std::vector<OctoP2Level> &p2 = octo_p2(H);
         const OctoP2Level &P = p2[(size_t)from_level];
-        octo_copy_out(ptr, P.ptr, (size_t)p2[(size_t)from_level + 1].ndof + 1);
-        octo_copy_out(col, P.col, (size_t)P.nnz);
-        octo_copy_out(val, P.val, (size_t)P.nnz);
+        P.ptr.to_host(ptr, (size_t)p2[(size_t)from_level + 1].ndof + 1);
+        P.col.to_host(col, (size_t)P.nnz);
+        P.val.to_host(val, (size_t)P.nnz);
         return WAE_OK;
     });
 }
@@ -560,17 +521,16 @@ int wae_octosplit_prolong_p2(void *h, int32_t from_level, int32_t to_level, int3
         const std::vector<OctoP2Level> &p2 = octo_p2(H);
         DevBuf<cplx> a, b;                                  // the intermediate levels stay here
         const size_t nin = (size_t)p2[(size_t)from_level].ndof * (size_t)ncols;
-        a.alloc(nin);
-        HIP_CHECK(hipMemcpy(a.p, X, nin * sizeof(cplx), hipMemcpyHostToDevice));
+        a.from_host((const cplx *)X, nin);
         for (int32_t l = from_level; l < to_level; ++l) {
             const OctoP2Level &P = p2[(size_t)l];
             const int64_t nrow = p2[(size_t)l + 1].ndof;
             b.alloc((size_t)nrow * (size_t)ncols);
-            hipLaunchKernelGGL(octo_p2_apply_kernel, octo_grid(nrow), dim3(256), 0, 0, P.ptr.p, P.col.p, P.val.p, nrow, P.ndof, (int)ncols, a.p, b.p);
+            hipLaunchKernelGGL(octo_p2_apply_kernel, grid_for(nrow), dim3(256), 0, 0, P.ptr.p, P.col.p, P.val.p, nrow, P.ndof, (int)ncols, a.p, b.p);
             HIP_CHECK(hipGetLastError());
             std::swap(a, b);
         }
-        HIP_CHECK(hipMemcpy(Y, a.p, (size_t)p2[(size_t)to_level].ndof * (size_t)ncols * sizeof(cplx), hipMemcpyDeviceToHost));
+        a.to_host((cplx *)Y, (size_t)p2[(size_t)to_level].ndof * (size_t)ncols);
         return WAE_OK;
     });
 }
@@ -586,22 +546,17 @@ int wae_octosplit(int32_t device, int64_t npoints, const double *points, int64_t
         for (int64_t l = 0, nt = ntets, ns = ntris; l < levels; ++l, nt *= 8, ns *= 4)
             if (nt > INT_MAX / 8 || ns > INT_MAX / 4)
                 throw WaeError(WAE_ERR_INVALID, "8^levels * ntets or 4^levels * ntris does not fit a 32-bit index");
-        for (int64_t i = 0; i < ntets * 4; ++i)
-            if (tets[i] < 0 || tets[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "tetrahedron refers to a point outside 0..npoints-1");
-        for (int64_t i = 0; i < ntris * 3; ++i)
-            if (tris[i] < 0 || tris[i] >= npoints) throw WaeError(WAE_ERR_INVALID, "triangle refers to a point outside 0..npoints-1");
+        check_tets(tets, ntets, npoints);
+        check_tris(tris, ntris, npoints);
         HIP_CHECK(hipSetDevice(device));
         std::unique_ptr<Octo> H(new Octo);
         H->device = device;
         H->lv.resize((size_t)levels + 1);
         OctoLevel &L0 = H->lv[0];
         L0.np = npoints; L0.nt = ntets; L0.ns = ntris;
-        L0.pts.alloc((size_t)npoints * 3);
-        L0.tets.alloc((size_t)ntets * 4);
-        L0.tris.alloc((size_t)ntris * 3);
-        HIP_CHECK(hipMemcpy(L0.pts.p, points, (size_t)npoints * 3 * sizeof(double), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(L0.tets.p, tets, (size_t)ntets * 4 * sizeof(int), hipMemcpyHostToDevice));
-        if (ntris) HIP_CHECK(hipMemcpy(L0.tris.p, tris, (size_t)ntris * 3 * sizeof(int), hipMemcpyHostToDevice));
+        L0.pts.from_host(points, (size_t)npoints * 3);
+        L0.tets.from_host(tets, (size_t)ntets * 4);
+        L0.tris.from_host(tris, (size_t)ntris * 3);
         for (int32_t l = 1; l <= levels; ++l) octo_refine(H->lv[(size_t)l - 1], H->lv[(size_t)l], l);
         *out = H.release();
         return WAE_OK;
@@ -624,14 +579,14 @@ int wae_octosplit_get(const void *h, int32_t level, double *points, int32_t *tet
         const OctoLevel &L = octo_level(h, level);
         if (level == 0 && (parents || tet_labels || tri_labels)) throw WaeError(WAE_ERR_INVALID, "level 0 is the input: it has no parents and no labels");
         HIP_CHECK(hipSetDevice(((const Octo *)h)->device));
-        octo_copy_out(points, L.pts, (size_t)L.np * 3);
-        octo_copy_out(tets, L.tets, (size_t)L.nt * 4);
-        octo_copy_out(tris, L.tris, (size_t)L.ns * 3);
+        L.pts.to_host(points, (size_t)L.np * 3);
+        L.tets.to_host(tets, (size_t)L.nt * 4);
+        L.tris.to_host(tris, (size_t)L.ns * 3);
         if (level > 0) {
             const OctoLevel &P = octo_level(h, level - 1);
-            octo_copy_out(parents, L.parents, (size_t)(L.np - P.np) * 2);
-            octo_copy_out(tet_labels, L.tet_labels, (size_t)L.nt);
-            octo_copy_out(tri_labels, L.tri_labels, (size_t)L.ns);
+            L.parents.to_host(parents, (size_t)(L.np - P.np) * 2);
+            L.tet_labels.to_host(tet_labels, (size_t)L.nt);
+            L.tri_labels.to_host(tri_labels, (size_t)L.ns);
         }
         return WAE_OK;
     });
@@ -646,16 +601,15 @@ int wae_octosplit_prolong(const void *h, int32_t from_level, int32_t to_level, i
         const Octo *H = (const Octo *)h;
         HIP_CHECK(hipSetDevice(H->device));
         DevBuf<cplx> a, b;                                  // the intermediate levels stay here
-        a.alloc((size_t)F.np * (size_t)ncols);
-        HIP_CHECK(hipMemcpy(a.p, X, (size_t)F.np * (size_t)ncols * sizeof(cplx), hipMemcpyHostToDevice));
+        a.from_host((const cplx *)X, (size_t)F.np * (size_t)ncols);
         for (int32_t l = from_level + 1; l <= to_level; ++l) {
             const OctoLevel &P = H->lv[(size_t)l - 1], &L = H->lv[(size_t)l];
             b.alloc((size_t)L.np * (size_t)ncols);
-            hipLaunchKernelGGL(octo_prolong_kernel, octo_grid(L.np), dim3(256), 0, 0, a.p, P.np, L.parents.p, L.np, (int)ncols, b.p);
+            hipLaunchKernelGGL(octo_prolong_kernel, grid_for(L.np), dim3(256), 0, 0, a.p, P.np, L.parents.p, L.np, (int)ncols, b.p);
             HIP_CHECK(hipGetLastError());
             std::swap(a, b);
         }
-        HIP_CHECK(hipMemcpy(Y, a.p, (size_t)T.np * (size_t)ncols * sizeof(cplx), hipMemcpyDeviceToHost));
+        a.to_host((cplx *)Y, (size_t)T.np * (size_t)ncols);
         return WAE_OK;
     });
 }
@@ -672,11 +626,11 @@ int wae_octosplit_prolongator(const void *h, int32_t from_level, int32_t *ptr, i
         DevBuf<int> dptr, dcol;
         DevBuf<double> dval;
         dptr.alloc((size_t)T.np + 1); dcol.alloc((size_t)nnz); dval.alloc((size_t)nnz);
-        hipLaunchKernelGGL(octo_prolongator_kernel, octo_grid(T.np + 1), dim3(256), 0, 0, F.np, T.parents.p, T.np, dptr.p, dcol.p, dval.p);
+        hipLaunchKernelGGL(octo_prolongator_kernel, grid_for(T.np + 1), dim3(256), 0, 0, F.np, T.parents.p, T.np, dptr.p, dcol.p, dval.p);
         HIP_CHECK(hipGetLastError());
-        octo_copy_out(ptr, dptr, (size_t)T.np + 1);
-        octo_copy_out(col, dcol, (size_t)nnz);
-        octo_copy_out(val, dval, (size_t)nnz);
+        dptr.to_host(ptr, (size_t)T.np + 1);
+        dcol.to_host(col, (size_t)nnz);
+        dval.to_host(val, (size_t)nnz);
         return WAE_OK;
     });
 }

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <new>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -31,6 +32,21 @@ hipStream_t wae_internal_stream(const wae_family *h);
             throw WaeError(WAE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + " at " +   \
                                             __FILE__ + ":" + std::to_string(__LINE__));                  \
     } while (0)
+// every C-ABI entry runs its body through this: an exception becomes the return code, its text wae_last_error()
+template <class F> int wae_guarded(F &&f) {
+    try {
+        return f();
+    } catch (const WaeError &e) {
+        wae_set_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        wae_set_error("out of host memory");
+        return WAE_ERR_INVALID;
+    } catch (const std::exception &e) {
+        wae_set_error(e.what());
+        return WAE_ERR_INVALID;
+    }
+}
 #define WAE_REQUIRE(cond, msg)                                  \
     do {                                                        \
         if (!(cond)) throw WaeError(WAE_ERR_INVALID, (msg));    \
@@ -131,7 +147,7 @@ constexpr int WAE_LONG_ROW = 256;
 constexpr int WAE_LONG_SPLIT = 32;       // workgroups a long row's entries are split over (kernels.hip long_row_piece)
 
 // device buffer: owns its allocation (freed on destruction, so an exception that leaves a C-ABI entry through guarded()
-// releases every function-local buffer); movable, not copyable
+// releases every function-local buffer); movable, not copyable.  An empty buffer holds no allocation (p == nullptr).
 template <class T> struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
@@ -153,6 +169,13 @@ template <class T> struct DevBuf {
     void upload(const T *h, size_t count, hipStream_t s) {
         if (count > n) alloc(count);
         if (count) HIP_CHECK(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s));
+    }
+    void from_host(const T *h, size_t count) {          // alloc(count) and a blocking copy of count host elements
+        alloc(count);
+        if (count) HIP_CHECK(hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice));
+    }
+    void to_host(T *dst, size_t count, size_t first = 0) const {      // elements first .. first + count - 1; a null dst or an empty range: no copy
+        if (dst && count) HIP_CHECK(hipMemcpy(dst, p + first, count * sizeof(T), hipMemcpyDeviceToHost));
     }
     void release() {
         if (p) (void)hipFree(p);
@@ -250,9 +273,15 @@ struct P1Handle {                   // an assembled CSR pattern with up to two r
     std::vector<int> rowptr, col;
     std::vector<double> m, k;
 };
-template <class T> struct Dev {     // function-local device array of the assembly entries
+template <class T> struct Dev {     // function-local device array of the mesh entries: at least one element, so p is never null
     T *p = nullptr;
     explicit Dev(size_t n) { HIP_CHECK(hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T))); }
+    Dev(const T *host, size_t n) : Dev(n) {             // ... holding a copy of n host elements
+        if (n) HIP_CHECK(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
+    }
+    void to_host(T *dst, size_t n, size_t first = 0) const {          // elements first .. first + n - 1; a null dst or an empty range: no copy
+        if (dst && n) HIP_CHECK(hipMemcpy(dst, p + first, n * sizeof(T), hipMemcpyDeviceToHost));
+    }
     Dev(const Dev &) = delete;
     Dev &operator=(const Dev &) = delete;
     ~Dev() { if (p) (void)hipFree(p); }
