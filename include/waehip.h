@@ -451,6 +451,46 @@ int wae_p2_assemble_boundary(int32_t device, int64_t npoints, const double *poin
 int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t nflame,
                           const int32_t *flame_tets, int32_t ref_tet, const double *x_ref, const double *n_ref, double nglobal_scaled, void **out,
                           double *volume_out);
+/* -- Hermite (cubic) assembly on the device: `discretize(...; order=:herm)` ------------------------------------------
+ * The element (aggregate_elements, src/FEM/FEM.jl:117-160; recombine_hermite, FEM.jl:171-336): P3 on the tetrahedron p0..p3, 20 DoF, the
+ * basis dual to  u(p_k) (local 0..3, global p_k),  du/dx, du/dy, du/dz at p_k (local 4..7, 8..11, 12..15, global N + p_k, 2N + p_k,
+ * 3N + p_k; N = npoints; physical gradients, not reference ones),  u at the centroid of the face opposite p_k (local 16..19, global
+ * 4N + face number).  Boundary triangle: the trace, 13 DoF -- 3 values, the x, y, z derivatives at the 3 points, the face value.
+ * Face numbering (collect_triangles, FEM.jl:49-68): the boundary triangle at position t of `tris` is face t; every tetrahedron face that
+ * is not in `tris` (interior, or a boundary face the caller did not list) follows as ntris + rank, the rank ascending by (largest point,
+ * middle point, smallest point); ndof = 4N + ntris + ninner.  With `tris` in the reference's sorted order this is its numbering.  Face
+ * keys, radix sort, unique pass, scan and the binary searches run on the device, without atomics: the same bits on every call.
+ * wae_herm_connectivity returns a handle, wae_herm_connectivity_info the sizes, wae_herm_connectivity_get copies out faces[3*ninner]
+ * (each as smallest, middle, largest point), tets20[20*ntets], tris13[13*ntris] (0-based; any pointer may be NULL),
+ * wae_herm_connectivity_free releases it.  WAE_ERR_INVALID, nothing written: an index outside 0..npoints-1, a boundary triangle that is
+ * no tetrahedron's face, a triangle listed twice, a face shared by more than two tetrahedra, 400*ntets or 169*ntris beyond a 32-bit
+ * count, or npoints > 2^21 = 2097152: the 64-bit face key holds three point numbers, larger meshes are refused, never truncated. */
+int wae_herm_connectivity(int32_t device, int64_t npoints, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris, void **out);
+int wae_herm_connectivity_info(const void *handle, int64_t *ninner, int64_t *ntets, int64_t *ntris, int64_t *ndof);
+int wae_herm_connectivity_get(const void *handle, int32_t *faces, int32_t *tets20, int32_t *tris13);
+int wae_herm_connectivity_free(void *handle);
+/* The three operators on the Hermite space.  Each entry takes the plain mesh and numbers the faces itself -- `tris` is always part of
+ * that numbering (ntris may be 0 for the interior and the flame) -- and returns the handle type of the P1 entries (wae_p1_info /
+ * wae_p1_get / wae_p1_free) with ndof rows; triplets sorted and summed on the device, deterministic, no atomics.  With x = p3 + J xi,
+ * J[:, j] = p_j - p_3 (CooTrafo, FEM.jl:9-21), the function of d/dx_i at p_k is sum_j J[i][j] (reference function of d/dxi_j at p_k);
+ * the entries of J keep their sign, the measure is |det J|: a tetrahedron listed with det J < 0 is legal.  The reference-element
+ * tensors come from a table generated in exact rational arithmetic from this definition (dev/gen_herm_tables.py).
+ *  - interior (src/Helmholtz.jl:120-149,405-441):
+ *        M_ab += |det J| int phi_a phi_b,      K_ab += -c_tet^2 |det J| int grad(phi_a).grad(phi_b)     (c_tet NULL = 1)
+ *  - admittance boundary (Helmholtz.jl:151-170,443-463): b_ab = c_tri |(x0-x2) x (x1-x2)| int phi_a phi_b on the 13-DoF triangle, only
+ *    the tangential part of a vertex gradient acting; the operator term is C = -i b; the full 13 x 13 coupling stays in the pattern.
+ *  - flame (Helmholtz.jl:292-344,464-487): Q = sum over the flame tetrahedra of S (x) g,  S_a = |det J| int phi_a (|det J|/240 on the
+ *    values, 0 on the gradients, 3|det J|/80 on the faces),  g_b = -nlocal grad(phi_b)(x_ref).n_ref on the 20 DoF of ref_tet,
+ *    nlocal = nglobal_scaled / V_flame; arguments as wae_p2_assemble_flame.
+ * Out of scope for Hermite elements: a nodal speed of sound, source vectors, shape sensitivity, Bloch numbering, prolongation across
+ * octosplit levels, point location and sampling, the tile path; the multigrid set-up was not designed for unknowns of mixed type. */
+int wae_herm_assemble(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris,
+                      const double *c_tet, void **out);
+int wae_herm_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                               const int32_t *tris, const double *c_tri, void **out);
+int wae_herm_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                            const int32_t *tris, int64_t nflame, const int32_t *flame_tets, int32_t ref_tet, const double *x_ref, const double *n_ref,
+                            double nglobal_scaled, void **out, double *volume_out);
 /* -- uniform mesh refinement on the device: `octosplit(mesh)` with the nested P1 and P2 prolongations ------------------
  * Every tetrahedron is split into 8 and every boundary triangle into 4 (src/Meshutils.jl:589-747); the handle keeps `levels`
  * successive refinements in HBM, level 0 being the input.  points: 3 doubles per point, tets: 4 point indices (0-based) per

@@ -1781,6 +1781,64 @@ function assemble_p2_flame(points::Matrix{Float64}, tets::AbstractMatrix{<:Integ
     return _take_p1(h[], false), vol[]
 end
 
+# Hermite (cubic) elements, `discretize(...; order=:herm)`: face DoFs numbered on the device (aggregate_elements, FEM.jl:117-160) and the three
+# operators on the 20-DoF tetrahedra / 13-DoF triangles.  Arguments as for the P2 wrappers (1-based indices in, 1-based out); `tris` is part
+# of the numbering in every call: the boundary triangle at position t is face t, the other faces follow by rank.
+"faces (3 x ninner), tets20 (20 x ntet), tris13 (13 x ntri), ndof = herm_connectivity(npoints, tets[, tris]; device): values at the points (DoF p),
+their x, y, z derivatives (N + p, 2N + p, 3N + p), one value per face centroid (4N + face); faces: those that are not in tris, each as (smallest,
+middle, largest point), ranked by (largest, middle, smallest)"
+function herm_connectivity(npoints::Integer, tets::AbstractMatrix{<:Integer}, tris::Union{Nothing,AbstractMatrix{<:Integer}}=nothing; device::Integer=0)
+    t0 = _zero_based(tets); s0 = tris === nothing ? zeros(Int32, 3, 0) : _zero_based(tris); h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:wae_herm_connectivity, libwaehip), Cint, (Int32, Int64, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ref{Ptr{Cvoid}}),
+                device, npoints, size(t0, 2), t0, size(s0, 2), size(s0, 2) == 0 ? C_NULL : s0, h))
+    try
+        nf = Ref{Int64}(0); nt = Ref{Int64}(0); ns = Ref{Int64}(0); nd = Ref{Int64}(0)
+        check(ccall((:wae_herm_connectivity_info, libwaehip), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], nf, nt, ns, nd))
+        faces = zeros(Int32, 3, nf[]); t20 = zeros(Int32, 20, nt[]); t13 = zeros(Int32, 13, ns[])
+        check(ccall((:wae_herm_connectivity_get, libwaehip), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), h[], faces, t20, t13))
+        return faces .+ Int32(1), t20 .+ Int32(1), t13 .+ Int32(1), Int(nd[])
+    finally
+        ccall((:wae_herm_connectivity_free, libwaehip), Cint, (Ptr{Cvoid},), h[])
+    end
+end
+
+"M, K = assemble_herm(points, tets[, tris]; c_tet, device): Hermite mass and stiffness (Helmholtz.jl:120-149,405-441 with order=:herm), size ndof;
+c_tet per tetrahedron (nothing = 1).  A speed of sound per mesh point is not implemented for Hermite elements."
+function assemble_herm(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, tris::Union{Nothing,AbstractMatrix{<:Integer}}=nothing; c_tet=nothing,
+                       device::Integer=0)
+    t0 = _zero_based(tets); s0 = tris === nothing ? zeros(Int32, 3, 0) : _zero_based(tris); h = Ref{Ptr{Cvoid}}(C_NULL)
+    cc = c_tet === nothing ? C_NULL : Vector{Float64}(c_tet)
+    check(ccall((:wae_herm_assemble, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                device, size(points, 2), points, size(t0, 2), t0, size(s0, 2), size(s0, 2) == 0 ? C_NULL : s0, cc, h))
+    return _take_p1(h[], true)
+end
+
+"C = assemble_herm_boundary(points, tets, tris; c_tri, device): Hermite admittance-boundary operator -i c |e1×e2| ∫φ_aφ_b on the 13-DoF triangles, the
+traces of the tetrahedron functions (Helmholtz.jl:151-170,443-463)"
+function assemble_herm_boundary(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, tris::AbstractMatrix{<:Integer}; c_tri=nothing, device::Integer=0)
+    t0 = _zero_based(tets); s0 = _zero_based(tris); h = Ref{Ptr{Cvoid}}(C_NULL)
+    cc = c_tri === nothing ? C_NULL : Vector{Float64}(c_tri)
+    check(ccall((:wae_herm_assemble_boundary, libwaehip), Cint,
+                (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                device, size(points, 2), points, size(t0, 2), t0, size(s0, 2), s0, cc, h))
+    return -1im .* _take_p1(h[], false)
+end
+
+"Q, V_flame = assemble_herm_flame(points, tets, tris, flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled; device): Hermite flame operator Q = Σ_flame S ⊗ g
+(Helmholtz.jl:292-344,464-487); as assemble_p2_flame, tris (or nothing) numbers the faces as in assemble_herm"
+function assemble_herm_flame(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, tris::Union{Nothing,AbstractMatrix{<:Integer}},
+                             flame_tets::AbstractVector{<:Integer}, ref_tet::Integer, x_ref::Vector{Float64}, n_ref::Vector{Float64}, nglobal_scaled::Real;
+                             device::Integer=0)
+    t0 = _zero_based(tets); s0 = tris === nothing ? zeros(Int32, 3, 0) : _zero_based(tris)
+    fl = Vector{Int32}(flame_tets) .- Int32(1); h = Ref{Ptr{Cvoid}}(C_NULL); vol = Ref{Float64}(0.0)
+    check(ccall((:wae_herm_assemble_flame, libwaehip), Cint,
+                (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Int32, Ptr{Float64}, Ptr{Float64}, Float64,
+                 Ref{Ptr{Cvoid}}, Ref{Float64}),
+                device, size(points, 2), points, size(t0, 2), t0, size(s0, 2), size(s0, 2) == 0 ? C_NULL : s0, length(fl), fl, ref_tet - 1, x_ref, n_ref,
+                Float64(nglobal_scaled), h, vol))
+    return _take_p1(h[], false), vol[]
+end
+
 "m = assemble_source(points, tris; tets, c_tri, c_point, device): the source vector of a :speaker boundary, m = -i s with s_a = |e1×e2| ∫c φ_a over
 the speaker triangles (Helmholtz.jl:488-505,519-522), as the sparse vector the `rhs` family of `discretize(...; source=true)` holds.  tets given:
 the P2 space (they number the edges), size npoints + nedges; else P1.  c_tri (per triangle, nothing = 1) or c_point (per mesh point)."
@@ -1934,7 +1992,7 @@ function bloch_fold(A::SparseMatrixCSC, nb::BlochNumbering; axis::Bool=true, dev
 end
 
 "M, K, C, Q, V_flame = discretize_device(points, tets; order, c, c_tet, bnd_tris, bnd_c, flame): the term matrices of `discretize` assembled on the
-device, order = :lin or :quad (Helmholtz.jl:36-54).  c: the speed of sound as `discretize` takes it (Helmholtz.jl:59-74) -- one value per
+device, order = :lin, :quad or :herm (Helmholtz.jl:36-54; :herm: c per tetrahedron only, no source=true, no bloch; bnd_tris numbers the first faces).  c: the speed of sound as `discretize` takes it (Helmholtz.jl:59-74) -- one value per
 tetrahedron, or one per mesh point (then linear on every simplex, in K and in C; bnd_c is not used); c_tet = the first form alone.
 bnd_tris / bnd_c: admittance-boundary triangles and the speed of sound behind each; flame = (flame_tets, ref_tet, x_ref, n_ref,
 nglobal_scaled).  Terms that were not asked for come back as `nothing`.
@@ -1944,7 +2002,7 @@ bloch=(nsector, naxis): the mesh is the extended unit cell of a Bloch computatio
 the call returns (M, K, C, Q, V_flame, numbering); not together with source=true.  bloch=nothing (the default): the plain matrices."
 function discretize_device(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}; order::Symbol=:lin, c=nothing, c_tet=nothing, bnd_tris=nothing,
                            bnd_c=nothing, flame=nothing, device::Integer=0, source::Bool=false, speaker=(:Y, 1e15, :A, 1.0), bloch=nothing)
-    order in (:lin, :quad) || error("discretize_device: order must be :lin or :quad")
+    order in (:lin, :quad, :herm) || error("discretize_device: order must be :lin, :quad or :herm")
     bloch === nothing || !source || throw(ArgumentError("discretize_device: bloch and source=true cannot be combined"))
     quad = order == :quad
     c_point = nothing
@@ -1956,6 +2014,17 @@ function discretize_device(points::Matrix{Float64}, tets::AbstractMatrix{<:Integ
             c_point = c
             bnd_c === nothing || throw(ArgumentError("discretize_device: with a nodal c the boundary term takes c from the mesh points, not bnd_c"))
         end
+    end
+    if order == :herm
+        c_point === nothing || throw(ArgumentError("discretize_device: order=:herm with a speed of sound per mesh point is not implemented"))
+        source && throw(ArgumentError("discretize_device: order=:herm with source=true is not implemented"))
+        bloch === nothing || throw(ArgumentError("discretize_device: order=:herm with bloch is not implemented"))
+        M, K = assemble_herm(points, tets, bnd_tris; c_tet=c_tet, device=device)
+        C = bnd_tris === nothing ? nothing : assemble_herm_boundary(points, tets, bnd_tris; c_tri=bnd_c, device=device)
+        flame === nothing && return M, K, C, nothing, nothing
+        flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled = flame
+        Q, V = assemble_herm_flame(points, tets, bnd_tris, flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled; device=device)
+        return M, K, C, Q, V
     end
     M, K = quad ? assemble_p2(points, tets; c_tet=c_tet, c_point=c_point, device=device) :
                   assemble_p1(points, tets; c_tet=c_tet, c_point=c_point, device=device)

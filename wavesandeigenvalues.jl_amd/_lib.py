@@ -49,6 +49,8 @@ EXPORTS = [
     "wae_octosplit_p2_info", "wae_octosplit_prolongator_p2", "wae_octosplit_prolong_p2", "wae_p2_embedding",
     "wae_locator_create", "wae_locator_info", "wae_locator_find", "wae_locator_set_p2", "wae_locator_weights", "wae_locator_sample",
     "wae_locator_free",
+    "wae_herm_connectivity", "wae_herm_connectivity_info", "wae_herm_connectivity_get", "wae_herm_connectivity_free", "wae_herm_assemble",
+    "wae_herm_assemble_boundary", "wae_herm_assemble_flame",
 ]
 BLOCH_IMAGE, BLOCH_AXIS = 1, 2      # WAE_BLOCH_* flag bits
 TALL_MAXCOLS = 64           # WAE_TALL_MAXCOLS
@@ -181,6 +183,14 @@ def lib():
     L.wae_locator_weights.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, i32p, dp, i32p, dp]
     L.wae_locator_sample.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, i32p, dp, C.c_int64, C.c_int32, dp, dp]
     L.wae_locator_free.argtypes = [C.c_void_p]
+    L.wae_herm_connectivity.argtypes = [C.c_int32, C.c_int64, C.c_int64, i32p, C.c_int64, i32p, C.POINTER(C.c_void_p)]
+    L.wae_herm_connectivity_info.argtypes = [C.c_void_p, i64p, i64p, i64p, i64p]
+    L.wae_herm_connectivity_get.argtypes = [C.c_void_p, i32p, i32p, i32p]
+    L.wae_herm_connectivity_free.argtypes = [C.c_void_p]
+    L.wae_herm_assemble.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, dp, C.POINTER(C.c_void_p)]
+    L.wae_herm_assemble_boundary.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, dp, C.POINTER(C.c_void_p)]
+    L.wae_herm_assemble_flame.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, C.c_int64, i32p, C.c_int32, dp, dp, C.c_double,
+                                          C.POINTER(C.c_void_p), dp]
     L.wae_solver_setup_nested.argtypes = [C.c_void_p, dp, dp, C.c_int32, C.c_int32, i64p, i64p, vpp, vpp, vpp]
     L.wae_bench_spmv.argtypes = [C.c_void_p, dp, C.c_int32, C.c_int32, dp]
     L.wae_bench_triad.argtypes = [C.c_int32, C.c_int64, C.c_int32, dp]

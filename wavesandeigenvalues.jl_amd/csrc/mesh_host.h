@@ -1,4 +1,4 @@
-// Host-side helpers of the mesh entries (assemble.hip, assemble_p2.hip, bloch.hip, octosplit.hip, locate.hip): the range check of an index
+// Host-side helpers of the mesh entries (assemble.hip, assemble_p2.hip, assemble_herm.hip, bloch.hip, octosplit.hip, locate.hip): the range check of an index
 // list, the launch grid, and the hipCUB calls with their temporary storage.  wae_guarded and the copies of Dev / DevBuf are in wae_internal.h.
 #pragma once
 #include <hipcub/hipcub.hpp>

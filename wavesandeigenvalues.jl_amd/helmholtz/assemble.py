@@ -232,6 +232,117 @@ def assemble_p2_flame(points, tets, flame_tets, ref_tet, x_ref, n_ref, nglobal_s
     return _take_csr(L, h, np.complex128), vol.value
 
 
+# ---- Hermite (cubic) elements: `discretize(...; order=:herm)` -------------------------------------------------------------------
+def _herm_no_nodal_c(c_point):
+    if c_point is not None:
+        raise NotImplementedError("Hermite elements with a speed of sound per mesh point (c_point) are not implemented: "
+                                  "the nodal element matrices of order='herm' are missing; give c per simplex")
+
+
+def _tris_args(tr):
+    """(ntris, pointer or None) of an optional triangle list"""
+    ip = C.POINTER(C.c_int32)
+    return (0, None) if tr is None or not len(tr) else (tr.shape[0], tr.ctypes.data_as(ip))
+
+
+def herm_connectivity(points, tets, tris=None, device=0):
+    """DoFs of the Hermite space numbered on the device (wae_herm_connectivity; aggregate_elements, src/FEM/FEM.jl:117-160): values at
+    the points (DoF p), the x, y, z derivatives there (N + p, 2N + p, 3N + p, N = npoints), one value per face centroid (4N + face).
+    The boundary triangle at position t of ``tris`` is face t, every other tetrahedron face follows as ntris + rank, ascending by
+    (largest, middle, smallest point).  ``points``: the (npoints, 3) array or just npoints.  Returns (faces (ninner, 3) -- the faces
+    that are not in ``tris``, each as (smallest, middle, largest) --, tets20 (ntets, 20), tris13 (ntris, 13), ndof), 0-based; local
+    order: the 4 (3) values, the x, the y, the z derivatives, then the faces opposite point 1, 2, 3, 4 (the triangle's own face)."""
+    npoints = int(points) if np.ndim(points) == 0 else np.asarray(points).reshape(-1, 3).shape[0]
+    _, tt, tr = _mesh_args(np.zeros((0, 3)), tets, tris)
+    L = _lib.lib()
+    ip = C.POINTER(C.c_int32)
+    h = C.c_void_p()
+    _lib.check(L.wae_herm_connectivity(int(device), npoints, tt.shape[0], tt.ctypes.data_as(ip), *_tris_args(tr), C.byref(h)))
+    try:
+        nf, nt, ns, nd = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(L.wae_herm_connectivity_info(h, C.byref(nf), C.byref(nt), C.byref(ns), C.byref(nd)))
+        faces = np.zeros((nf.value, 3), dtype=np.int32)
+        t20 = np.zeros((nt.value, 20), dtype=np.int32)
+        t13 = np.zeros((ns.value, 13), dtype=np.int32)
+        _lib.check(L.wae_herm_connectivity_get(h, faces.ctypes.data_as(ip), t20.ctypes.data_as(ip), t13.ctypes.data_as(ip)))
+    finally:
+        L.wae_herm_connectivity_free(h)
+    return faces, t20, t13, nd.value
+
+
+def herm_dof_count(points, tets, tris=None):
+    """4 npoints + number of distinct tetrahedron faces = the dimension of the Hermite space (host side; the device numbers the faces
+    itself).  ``points``: the array or just npoints; ``tris`` does not change the count (every listed triangle is a tetrahedron face)."""
+    npoints = int(points) if np.ndim(points) == 0 else np.asarray(points).reshape(-1, 3).shape[0]
+    tt = np.asarray(tets, dtype=np.int64).reshape(-1, 4)
+    f = np.sort(np.concatenate([tt[:, [b for b in range(4) if b != a]] for a in range(4)]), axis=1)
+    return 4 * npoints + len(np.unique(f, axis=0))
+
+
+def herm_dofs(points, faces, tris, f, grad_f):
+    """The DoF vector of a given function in the numbering of ``herm_connectivity`` (host helper: start fields, tests): f(points)
+    (npoints,), then grad_f(points) (npoints, 3) as the x, the y, the z derivatives, then f at the centroids of the boundary triangles
+    ``tris`` (None: none) and of ``faces``.  f and grad_f take an (n, 3) array of positions."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    fc = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    tr = np.zeros((0, 3), dtype=np.int64) if tris is None else np.asarray(tris, dtype=np.int64).reshape(-1, 3)
+    cen = pts[np.concatenate([tr, fc])].mean(axis=1).reshape(-1, 3)
+    val = np.asarray(f(pts))
+    g = np.asarray(grad_f(pts)).reshape(len(pts), 3)
+    return np.concatenate([val, g[:, 0], g[:, 1], g[:, 2], np.asarray(f(cen)).reshape(-1) if len(cen) else np.zeros(0, dtype=val.dtype)])
+
+
+def assemble_herm(points, tets, tris=None, c_tet=None, device=0, dtype=np.complex128, c_point=None):
+    """Hermite mass and stiffness matrices on the device (wae_herm_assemble; src/Helmholtz.jl:120-149,405-441 with order=:herm).
+    ``tris``: the boundary triangles, which take the first face numbers (None: every face numbered by rank).  Returns (M, K) as scipy
+    CSR matrices of size ndof sharing one pattern.  ``c_point`` raises NotImplementedError."""
+    _herm_no_nodal_c(c_point)
+    pts, tt, tr = _mesh_args(points, tets, tris)
+    cc = None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
+    if cc is not None and cc.shape != (tt.shape[0],):
+        raise ValueError(f"c_tet has shape {cc.shape}, the mesh has {tt.shape[0]} tetrahedra")
+    L = _lib.lib()
+    h = C.c_void_p()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _lib.check(L.wae_herm_assemble(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), *_tris_args(tr),
+                                   None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
+    return _take_pair(L, h, dtype)
+
+
+def assemble_herm_boundary(points, tets, tris, c_tri=None, device=0, c_point=None):
+    """Hermite boundary mass term of an admittance boundary on the device (wae_herm_assemble_boundary; src/Helmholtz.jl:151-170,443-463):
+    C = -i·c·|e1×e2|·∫φ_aφ_b on the 13-DoF triangles, the traces of the tetrahedron functions.  Returns C (complex CSR, ndof)."""
+    _herm_no_nodal_c(c_point)
+    pts, tt, tr = _mesh_args(points, tets, tris)
+    cc = None if c_tri is None else np.ascontiguousarray(c_tri, dtype=np.float64)
+    if cc is not None and cc.shape != (tr.shape[0],):
+        raise ValueError(f"c_tri has shape {cc.shape}, the boundary has {tr.shape[0]} triangles")
+    L = _lib.lib()
+    h = C.c_void_p()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _lib.check(L.wae_herm_assemble_boundary(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), tr.shape[0],
+                                            tr.ctypes.data_as(ip), None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
+    return -1j * _take_csr(L, h, np.complex128)
+
+
+def assemble_herm_flame(points, tets, tris, flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled, device=0):
+    """Hermite flame operator Q = Σ_flame S ⊗ g on the device (wae_herm_assemble_flame; src/Helmholtz.jl:292-344,464-487): as
+    ``assemble_p2_flame``; ``tris`` (may be None) numbers the faces as in ``assemble_herm``.  Returns (Q, V_flame)."""
+    pts, tt, tr = _mesh_args(points, tets, tris)
+    fl = np.ascontiguousarray(flame_tets, dtype=np.int32)
+    xr = np.ascontiguousarray(x_ref, dtype=np.float64)
+    nr = np.ascontiguousarray(n_ref, dtype=np.float64)
+    assert xr.shape == (3,) and nr.shape == (3,)
+    L = _lib.lib()
+    h = C.c_void_p()
+    vol = C.c_double(0.0)
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _lib.check(L.wae_herm_assemble_flame(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), *_tris_args(tr), len(fl),
+                                         fl.ctypes.data_as(ip), int(ref_tet), xr.ctypes.data_as(dp), nr.ctypes.data_as(dp), float(nglobal_scaled),
+                                         C.byref(h), C.byref(vol)))
+    return _take_csr(L, h, np.complex128), vol.value
+
+
 # ---- speaker source vector: `discretize(...; source=true)` with a :speaker domain ---------------------------------------------
 def _source_column(s):
     """the term m = -i·s of the `rhs` family as a complex d x 1 sparse column (sparsevec(I, V, dim) with V ./= 1im, Helmholtz.jl:500,520)"""
