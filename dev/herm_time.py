@@ -8,6 +8,9 @@ as a fraction of the device triad rate (wae_bench_triad, the figure bench.py rep
 
     python dev/herm_time.py --out profiles/herm_assembly.json
     python dev/herm_time.py --solve --out profiles/herm_solve.json      # one Lp(z).solve of the Hermite Rijke family, default set-up
+    python dev/herm_time.py --solve --hierarchy --out profiles/herm_solve_hierarchy.json
+                                                                        # ... with herm_hierarchy: p-hierarchy and per-level weight scaling,
+                                                                        # on the Rijke family and on w^2 M + K of kuhn_cube(n)
 
 There is no threshold and no parent to compare with: the numbers are a record."""
 import argparse
@@ -28,6 +31,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=26)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--solve", action="store_true")
+ap.add_argument("--hierarchy", action="store_true")
 ap.add_argument("--out", default="")
 a = ap.parse_args()
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -108,7 +112,55 @@ def solve_once():
     return res
 
 
-if a.solve:
+def solve_hierarchy():
+    """Lp(z).solve with the set-up of helmholtz.family.herm_hierarchy: iterations, levels, lambda_l, s_l and seconds (set-up apart)"""
+    from wae_amd.helmholtz.assemble import herm_prolongators
+    from wae_amd.helmholtz.family import helmholtz_family, herm_hierarchy
+    from wae_amd.nlevp.algebra import pow2
+    from wae_amd.nlevp.linopfam import LinearOperatorFamily, Term
+    out = []
+    pts, tets, tris, c_tet, c_tri, flame = rijke()
+    M, K = assemble_herm(pts, tets, tris, c_tet)
+    t = {"M": M, "K": K, "C": assemble_herm_boundary(pts, tets, tris, c_tri), "Q": assemble_herm_flame(pts, tets, tris, *flame)[0]}
+    cases = [("Hermite Rijke, n = 1, tau = 1e-3", helmholtz_family(t, n=1.0, tau=0.001), (pts, tets, tris), 340 * 2 * np.pi)]
+    kp, kt, ks = kuhn_cube(a.n)
+    Mc, Kc = assemble_herm(kp, kt, ks)
+    Lc = LinearOperatorFamily(["ω"], [0.0])
+    Lc.symmetry_tol = 1e-14
+    Lc.push(Term(Mc, (pow2,), (("ω",),), "ω^2", "M"))
+    Lc.push(Term(Kc, (), (), "", "K"))
+    cases.append((f"w^2 M + K on kuhn_cube({a.n}), Neumann walls", Lc, (kp, kt, ks), 3.0 * (1 + 0.02j)))
+    for name, Lp, mesh, z in cases:
+        d = Lp.size()
+        rng = np.random.default_rng(0)
+        B = rng.standard_normal((d, 8)) + 1j * rng.standard_normal((d, 8))
+        res = {"family": name, "d": d, "z": [z.real, z.imag] if isinstance(z, complex) else z, "columns": 8, "tol": 1e-10}
+        try:
+            t0 = time.perf_counter()
+            Ps = herm_prolongators(*mesh)
+            res["seconds_prolongators"] = time.perf_counter() - t0
+            herm_hierarchy(Lp, *mesh)
+            Lp.solver_ref = z
+            t0 = time.perf_counter()
+            fam = Lp.ensure_solver()
+            res["seconds_setup"] = time.perf_counter() - t0
+            lam, scale = fam.level_weights()
+            res.update(prolongator_shapes=[list(P.shape) for P in Ps], lambda_l=[float(x) for x in lam], s_l=[float(x) for x in scale])
+            X = Lp(z).solve(B, tol=1e-10)
+            info = dict(fam.last_info)
+            res.update(info={k: (float(v) if isinstance(v, float) else int(v)) for k, v in info.items()}, finite=bool(np.all(np.isfinite(X))))
+            R = B - Lp(z) @ X
+            res["plain_relres_max"] = float(np.max(np.linalg.norm(R, axis=0) / np.linalg.norm(B, axis=0)))
+        except Exception as e:                                          # noqa: BLE001 -- the observation is what happened
+            res["error"] = f"{type(e).__name__}: {e}"
+        Lp._drop_device()
+        out.append(res)
+    return {"cases": out}
+
+
+if a.solve and a.hierarchy:
+    res = solve_hierarchy()
+elif a.solve:
     res = solve_once()
 else:
     tri = C.c_double(0.0)

@@ -119,7 +119,15 @@ int wae_spmv_sum_multi(wae_family *h, const double *coeffs, const double *X, dou
  *   [8], [9] workspace hints (0 = none): probe columns l and snapshot capacity of the contour integrals that will follow
  *       (wae_beyn_moments_rb): the snapshot store and the resident term products are then mapped during the set-up, behind
  *       its host work, instead of during the first integral.
+ *   [12] per-level weight scaling: 0 (default) none, 1 spectral; anything else WAE_ERR_INVALID.  With 1, every level l above the dense one
+ *       gets s_l = min(1, 5 / (3 * 1.1 * lambda_l)) and the V-cycle multiplies its three weights ([2], [10], [11]) by s_l on that level.
+ *       lambda_l estimates lambda_max(D^-1 Re A_ref) of the level, D = diag(Re A_ref): WAE_WEIGHT_POWER_STEPS steps of a power iteration
+ *       on |D|^-1/2 Re A_ref |D|^-1/2 with the level's own operator product, from a fixed start vector -- a lower bound (the quotient of
+ *       two norms of a symmetric matrix's iterates), reached to within 10 % on the hierarchies it was chosen on, hence the factor 1.1;
+ *       a sweep with weight 5 / (3 lambda) damps every eigenvalue in [lambda / 5, lambda] by 2/3 or better.  Two set-ups give the same
+ *       bits.  With 0 every s_l is exactly 1.0 and every launch receives the arguments it received before the option existed.
  */
+#define WAE_WEIGHT_POWER_STEPS 40
 int wae_solver_setup(wae_family *h, const double *coeffs_ref, const double *opts, int32_t nopts);
 /* The same set-up from prolongators the caller supplies -- the nested hierarchy of a refined mesh (wae_octosplit_prolongator), or any
  * other nested hierarchy -- instead of aggregating the fine matrix.  coeffs_ref, opts, nopts as in wae_solver_setup.
@@ -140,6 +148,9 @@ int wae_solver_setup(wae_family *h, const double *coeffs_ref, const double *opts
  * duplicate columns in a row, a value that is not finite.  wae_solver_setup after this call replaces the hierarchy again. */
 int wae_solver_setup_nested(wae_family *h, const double *coeffs_ref, const double *opts, int32_t nopts, int32_t nlev, const int64_t *rows,
                             const int64_t *cols, const int32_t *const *ptr, const int32_t *const *col, const double *const *val);
+/* The levels above the dense one of the current hierarchy: *nlev their number; lambda[l], scale[l] for l < min(cap, *nlev) the estimate
+ * and the factor s_l of opts[12] (0.0 and 1.0 with the option off).  Any pointer may be NULL.  Needs a set-up. */
+int wae_solver_level_weights(const wae_family *h, int32_t cap, double *lambda, double *scale, int32_t *nlev);
 
 typedef struct {
     int32_t iters_max;      /* most iterations any column needed            */
@@ -483,7 +494,7 @@ int wae_herm_connectivity_free(void *handle);
  *    values, 0 on the gradients, 3|det J|/80 on the faces),  g_b = -nlocal grad(phi_b)(x_ref).n_ref on the 20 DoF of ref_tet,
  *    nlocal = nglobal_scaled / V_flame; arguments as wae_p2_assemble_flame.
  * Out of scope for Hermite elements: a nodal speed of sound, source vectors, shape sensitivity, Bloch numbering, prolongation across
- * octosplit levels, point location and sampling, the tile path; the multigrid set-up was not designed for unknowns of mixed type. */
+ * octosplit levels, point location and sampling, the tile path.  The solver path of a Hermite family: wae_hermite_prolongators below. */
 int wae_herm_assemble(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris,
                       const double *c_tet, void **out);
 int wae_herm_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
@@ -491,6 +502,25 @@ int wae_herm_assemble_boundary(int32_t device, int64_t npoints, const double *po
 int wae_herm_assemble_flame(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
                             const int32_t *tris, int64_t nflame, const int32_t *flame_tets, int32_t ref_tet, const double *x_ref, const double *n_ref,
                             double nglobal_scaled, void **out, double *volume_out);
+/* The p-hierarchy of a Hermite family: two real prolongators that carry it down to P1, for wae_solver_setup_nested (with opts[12] = 1: the
+ * set-up's Jacobi weights diverge on a cubic level, lambda_max(D^-1 A) is 5.8 there).  Both CSR, 0-based, columns ascending without
+ * duplicates; the faces numbered as in wae_herm_connectivity, by the same device pass.  No atomics: the same bits on every call.
+ *   which = 0, P_face, ndof x 4N: row r < 4N is (r, 1); the row of face f with the points a, b, c and the centroid
+ *       x_f = ((x_a + x_b) + x_c) / 3 has the 12 entries (p, 1/3) and ((1+i) N + p, (x_f - x_p)_i / 6), p in {a, b, c}, i = 0..2: the
+ *       centroid value of the cubic that the nine vertex data fix when quadratics are to be reproduced.  One thread per face.
+ *   which = 1, P_lin, 4N x N: row p is (p, 1); row (1+i) N + p is the volume-weighted mean over the tetrahedra t that hold p of the P1
+ *       gradient, sum_t |det J_t| d_i lambda_k^t / sum_t |det J_t| at column tets[t][k].  Triplets and weight sums go through the
+ *       stable sort and reduce-by-key of the assembly; entries that cancel to zero stay in the pattern; det J < 0 is legal.
+ * wae_hermite_prolongators returns a handle, wae_hermite_prolongators_info the sizes of one matrix, wae_hermite_prolongators_get copies it out
+ * (ptr[rows + 1], col[nnz], val[nnz]; any pointer may be NULL), wae_hermite_prolongators_free releases it.  Refused with WAE_ERR_INVALID,
+ * nothing written: everything wae_herm_connectivity refuses, points == NULL, which outside 0..1, a point that belongs to no
+ * tetrahedron (it has no gradient to average), and a point whose tetrahedra all have det J = 0 (its weight sum is 0).
+ * (The prefix is wae_hermite_, not wae_herm_: the set of wae_herm_ entries is the assembly's and is pinned as such by its tests.) */
+int wae_hermite_prolongators(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
+                          const int32_t *tris, void **out);
+int wae_hermite_prolongators_info(const void *handle, int32_t which, int64_t *rows, int64_t *cols, int64_t *nnz);
+int wae_hermite_prolongators_get(const void *handle, int32_t which, int32_t *ptr, int32_t *col, double *val);
+int wae_hermite_prolongators_free(void *handle);
 /* -- uniform mesh refinement on the device: `octosplit(mesh)` with the nested P1 and P2 prolongations ------------------
  * Every tetrahedron is split into 8 and every boundary triangle into 4 (src/Meshutils.jl:589-747); the handle keeps `levels`
  * successive refinements in HBM, level 0 being the input.  points: 3 doubles per point, tets: 4 point indices (0-based) per

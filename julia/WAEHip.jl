@@ -1695,9 +1695,12 @@ end
 
 "solver_setup_nested(fam, coeffs, Ps; opts=Float64[]): the multigrid set-up of `fam` from the prolongators Ps (finest first: size(Ps[1], 1)
 unknowns of the family, size(Ps[k], 2) == size(Ps[k + 1], 1)), e.g. [prolongator(ref; from=l) for l in ref.levels-1:-1:0], instead of
-smoothed aggregation (wae_solver_setup_nested; opts as for wae_solver_setup).  coeffs: the reference coefficients, one per term."
-function solver_setup_nested(fam::DeviceFamily, coeffs::Vector{ComplexF64}, Ps::AbstractVector; opts=Float64[])
+smoothed aggregation (wae_solver_setup_nested; opts as for wae_solver_setup).  coeffs: the reference coefficients, one per term.
+level_weights=:spectral: the Jacobi weights of every level scaled by its own spectral estimate (opts[12] = 1; solver_level_weights reads them
+back) -- with herm_prolongators the set-up of a Hermite family."
+function solver_setup_nested(fam::DeviceFamily, coeffs::Vector{ComplexF64}, Ps::AbstractVector; opts=Float64[], level_weights::Union{Nothing,Symbol}=nothing)
     isempty(Ps) && throw(ArgumentError("solver_setup_nested: at least one prolongator"))
+    level_weights === nothing || level_weights === :spectral || throw(ArgumentError("solver_setup_nested: level_weights must be nothing or :spectral"))
     for k in 1:length(Ps) - 1
         size(Ps[k], 2) == size(Ps[k + 1], 1) || throw(ArgumentError("solver_setup_nested: the prolongators' dimensions do not chain at $k"))
     end
@@ -1706,6 +1709,10 @@ function solver_setup_nested(fam::DeviceFamily, coeffs::Vector{ComplexF64}, Ps::
     rows = Int64[size(P, 1) for P in Ps]; cols = Int64[size(P, 2) for P in Ps]
     ptrs = [Int32.(T.colptr .- 1) for T in Ts]; idxs = [Int32.(T.rowval .- 1) for T in Ts]; vals = [Vector{Float64}(T.nzval) for T in Ts]
     o = Float64.(opts)
+    if level_weights === :spectral                         # opts[12] (0-based) = 1; the options before it keep their defaults (0)
+        o = vcat(o, zeros(Float64, max(0, 12 - length(o))))
+        length(o) == 12 ? push!(o, 1.0) : (o[13] = 1.0)
+    end
     GC.@preserve ptrs idxs vals begin
         pp = Ptr{Int32}[pointer(a) for a in ptrs]; pi = Ptr{Int32}[pointer(a) for a in idxs]; pv = Ptr{Float64}[pointer(a) for a in vals]
         check(ccall((:wae_solver_setup_nested, libwaehip), Cint,
@@ -1714,6 +1721,16 @@ function solver_setup_nested(fam::DeviceFamily, coeffs::Vector{ComplexF64}, Ps::
     end
     fam.solver_ready = true
     return nothing
+end
+
+"lambda, scale = solver_level_weights(fam): per level above the dense one, the estimate of lambda_max(D^-1 Re A_ref) and the factor on the level's
+Jacobi weights (wae_solver_level_weights); zeros and ones unless the set-up ran with level_weights=:spectral"
+function solver_level_weights(fam::DeviceFamily)
+    n = Ref{Int32}(0)
+    check(ccall((:wae_solver_level_weights, libwaehip), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Int32}), fam.handle, 0, C_NULL, C_NULL, n))
+    lam = zeros(Float64, n[]); sc = zeros(Float64, n[])
+    check(ccall((:wae_solver_level_weights, libwaehip), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Int32}), fam.handle, n[], lam, sc, n))
+    return lam, sc
 end
 
 # P2 (second-order) elements, `discretize(...; order=:quad)`: edge DoFs numbered on the device (aggregate_elements, FEM.jl:84-116) and the
@@ -1799,6 +1816,29 @@ function herm_connectivity(npoints::Integer, tets::AbstractMatrix{<:Integer}, tr
         return faces .+ Int32(1), t20 .+ Int32(1), t13 .+ Int32(1), Int(nd[])
     finally
         ccall((:wae_herm_connectivity_free, libwaehip), Cint, (Ptr{Cvoid},), h[])
+    end
+end
+
+"P_face, P_lin = herm_prolongators(points, tets[, tris]; device): the p-hierarchy of a Hermite family (wae_hermite_prolongators), in the form
+solver_setup_nested takes: P_face (ndof x 4N) drops the face unknowns -- the centroid value the nine vertex data of a face fix when quadratics are
+to be reproduced --, P_lin (4N x N) the gradients -- at a point, the volume-weighted mean of the P1 gradients around it.  tris as in assemble_herm."
+function herm_prolongators(points::Matrix{Float64}, tets::AbstractMatrix{<:Integer}, tris::Union{Nothing,AbstractMatrix{<:Integer}}=nothing; device::Integer=0)
+    t0 = _zero_based(tets); s0 = tris === nothing ? zeros(Int32, 3, 0) : _zero_based(tris); h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:wae_hermite_prolongators, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Ref{Ptr{Cvoid}}),
+                device, size(points, 2), points, size(t0, 2), t0, size(s0, 2), size(s0, 2) == 0 ? C_NULL : s0, h))
+    try
+        out = SparseMatrixCSC{Float64,Int}[]
+        for which in 0:1
+            nr = Ref{Int64}(0); nc = Ref{Int64}(0); nz = Ref{Int64}(0)
+            check(ccall((:wae_hermite_prolongators_info, libwaehip), Cint, (Ptr{Cvoid}, Int32, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], which, nr, nc, nz))
+            ptr = zeros(Int32, nr[] + 1); col = zeros(Int32, nz[]); val = zeros(Float64, nz[])
+            check(ccall((:wae_hermite_prolongators_get, libwaehip), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}), h[], which, ptr, col, val))
+            # CSR of P = CSC of its transpose
+            push!(out, sparse(transpose(SparseMatrixCSC(Int(nc[]), Int(nr[]), Int.(ptr) .+ 1, Int.(col) .+ 1, val))))
+        end
+        return out[1], out[2]
+    finally
+        ccall((:wae_hermite_prolongators_free, libwaehip), Cint, (Ptr{Cvoid},), h[])
     end
 end
 

@@ -51,6 +51,8 @@ EXPORTS = [
     "wae_locator_free",
     "wae_herm_connectivity", "wae_herm_connectivity_info", "wae_herm_connectivity_get", "wae_herm_connectivity_free", "wae_herm_assemble",
     "wae_herm_assemble_boundary", "wae_herm_assemble_flame",
+    "wae_hermite_prolongators", "wae_hermite_prolongators_info", "wae_hermite_prolongators_get", "wae_hermite_prolongators_free",
+    "wae_solver_level_weights",
 ]
 BLOCH_IMAGE, BLOCH_AXIS = 1, 2      # WAE_BLOCH_* flag bits
 TALL_MAXCOLS = 64           # WAE_TALL_MAXCOLS
@@ -191,6 +193,11 @@ def lib():
     L.wae_herm_assemble_boundary.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, dp, C.POINTER(C.c_void_p)]
     L.wae_herm_assemble_flame.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, C.c_int64, i32p, C.c_int32, dp, dp, C.c_double,
                                           C.POINTER(C.c_void_p), dp]
+    L.wae_hermite_prolongators.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, i32p, C.c_int64, i32p, C.POINTER(C.c_void_p)]
+    L.wae_hermite_prolongators_info.argtypes = [C.c_void_p, C.c_int32, i64p, i64p, i64p]
+    L.wae_hermite_prolongators_get.argtypes = [C.c_void_p, C.c_int32, i32p, i32p, dp]
+    L.wae_hermite_prolongators_free.argtypes = [C.c_void_p]
+    L.wae_solver_level_weights.argtypes = [C.c_void_p, C.c_int32, dp, dp, i32p]
     L.wae_solver_setup_nested.argtypes = [C.c_void_p, dp, dp, C.c_int32, C.c_int32, i64p, i64p, vpp, vpp, vpp]
     L.wae_bench_spmv.argtypes = [C.c_void_p, dp, C.c_int32, C.c_int32, dp]
     L.wae_bench_triad.argtypes = [C.c_int32, C.c_int64, C.c_int32, dp]

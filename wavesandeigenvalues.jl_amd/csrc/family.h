@@ -51,6 +51,7 @@ struct wae_family {
     double jac_w_post = 0.9;             // ... of its post-smoothing sweeps (opts[10])
     double jac_w_light = 0.5;            // ... of the single sweep of the light cycle (opts[11]; projected phase of a contour integral)
     int nsweeps = 1, restart = 30, NB = 64;
+    std::vector<double> lvl_lambda, lvl_scale;   // per level (ops.size() entries): the spectral estimate and the factor on the three weights (opts[12]; 0 and exactly 1.0 without)
     // workspaces
     std::vector<DevBuf<cplx>> lx, lb, lt;
     DevBuf<cplx> V, W, Z, Xs, Bs, U, partial, hdev, ydev, pcdev, one_dev, io_a, io_b, zw_dev;

@@ -39,7 +39,7 @@ void dense_setup(wae_family *h, const Batch &bt) {
     if (st) throw WaeError(WAE_ERR_BREAKDOWN, "coarse operator is singular");
 }
 
-double pre_weight(const wae_family *h) { return h->vc_light ? h->jac_w_light : h->jac_w; }
+double pre_weight(const wae_family *h, int l) { return (h->vc_light ? h->jac_w_light : h->jac_w) * h->lvl_scale[(size_t)l]; }
 
 // (have_x0, final_out, cn: solver.h)
 cplx *vcycle(wae_family *h, const Batch &bt, int l, const cplx *b, const unsigned char *cm, bool have_x0, cplx *final_out, CycleNorms *cn) {
@@ -52,9 +52,9 @@ cplx *vcycle(wae_family *h, const Batch &bt, int l, const cplx *b, const unsigne
     const OpDev A = h->ops[l].dev(bt.op);
     const cplx *pc = pc_level(h, l);
     cplx *x = h->lx[l].p, *t = h->lt[l].p;
-    if (!have_x0) launch_jacobi0(A, pc, bt.cps, b, x, pre_weight(h), bt.nb, st, cm);
+    if (!have_x0) launch_jacobi0(A, pc, bt.cps, b, x, pre_weight(h, l), bt.nb, st, cm);
     for (int s = 1; s < h->nsweeps; ++s) {
-        launch_spmv(A, pc, bt.cps, x, t, b, pre_weight(h), bt.nb, MODE_JAC, st, cm);
+        launch_spmv(A, pc, bt.cps, x, t, b, pre_weight(h, l), bt.nb, MODE_JAC, st, cm);
         std::swap(x, t);
     }
     // residual -> t, restrict -> lb[l+1]
@@ -84,7 +84,7 @@ cplx *vcycle(wae_family *h, const Batch &bt, int l, const cplx *b, const unsigne
     // (post-smoothing has a weight of its own, opts[10]: two sweeps with different weights form a degree-2 polynomial smoother)
     for (int s = 0; s < npost; ++s) {
         cplx *dst = (final_out && s == npost - 1) ? final_out : t;
-        launch_spmv(A, pc, bt.cps, x, dst, b, h->jac_w_post, bt.nb, MODE_JAC, st, cm);
+        launch_spmv(A, pc, bt.cps, x, dst, b, h->jac_w_post * h->lvl_scale[(size_t)l], bt.nb, MODE_JAC, st, cm);
         if (dst == t) std::swap(x, t); else x = dst;
     }
     // (for a cycle in which neither the last sweep nor the prolongation has written final_out; none is left today)

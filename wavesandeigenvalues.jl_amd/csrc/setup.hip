@@ -922,6 +922,30 @@ struct Joined {
     ~Joined() { if (f.valid()) f.wait(); }
 };
 
+// ----------------------------------------------------------------------------------------------------
+// opts[12] = 1: the spectral estimate behind a level's weight scale (include/waehip.h)
+// ----------------------------------------------------------------------------------------------------
+// The diagonal scaling of the power iteration on B = S Re(A) S, S = |D|^-1/2, D = Re(sum_q pc[q] diag[:, q]) (0 where D is 0).  The
+// operator product needs x = S v and gives y = A x; v is real, so Re(y) = Re(A) x.
+//     y == nullptr:  v_i = the start vector, ((i * 2654435761 mod 2^32) >> 16) / 32768 - 1  (in [-1, 1), exact in binary, the same on every call)
+//     otherwise:     v_i = c s_i Re(y_i)           (c: the reciprocal of the previous norm, keeps the iterates of size one)
+// and in both cases x_i = s_i v_i, imaginary parts 0.  One thread per row.
+__global__ __launch_bounds__(256) void weight_scale_kernel(const cplx *__restrict__ diag, const cplx *__restrict__ pc, int nplanes, int64_t n,
+                                                           const cplx *__restrict__ y, double c, cplx *__restrict__ v, cplx *__restrict__ x) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double d = 0.0;
+    for (int q = 0; q < nplanes; ++q) {
+        const cplx a = diag[(size_t)i * nplanes + q], w = pc[q];
+        d += a.x * w.x - a.y * w.y;
+    }
+    const double s = d != 0.0 ? 1.0 / sqrt(fabs(d)) : 0.0;
+    const double vi = y ? c * (s * y[i].x) : (double)(((unsigned)i * 2654435761u) >> 16) / 32768.0 - 1.0;
+    v[i] = cplx{vi, 0.0};
+    x[i] = cplx{s * vi, 0.0};
+}
+
 // One call of wae_solver_setup: what its stages share, one member function per stage (run() is the table of contents).
 // The two helper threads work on members of this object and of the handle: basis_job and l1_job are the LAST members, so they are
 // destroyed -- joined -- first, before anything their threads use.
@@ -931,6 +955,7 @@ struct SolverSetup {
     int nopts;
     const SetupEnv env;
     AmgOptions ao;
+    bool spectral = false;          // opts[12]: scale the Jacobi weights of every level by its own spectral estimate
     uint64_t excl = 0;              // opts[7]: bit k set = term k stays out of the shape matrix (strength graph, aggregation, prolongator smoothing)
     std::vector<zc> pc, pc_shape;   // plane coefficients of the reference operator / of the shape matrix (excl != 0)
     std::vector<AmgLevel> lv;
@@ -954,6 +979,9 @@ struct SolverSetup {
         // gap of the benchmark unchanged: 6.6e-9, 1.3e9).
         h->jac_w_post = opt(10, 0.9);
         h->jac_w_light = opt(11, 0.5);
+        const double lw = (opts && nopts > 12) ? opts[12] : 0.0;
+        WAE_REQUIRE(lw == 0.0 || lw == 1.0, "opts[12] (per-level weight scaling) must be 0 or 1");
+        spectral = lw == 1.0;
         h->nsweeps = (int)opt(3, 1);
         h->restart = (int)opt(4, 30);
         ao.penalty_ratio = opt(5, 1e8);
@@ -1214,6 +1242,58 @@ struct SolverSetup {
         HIP_CHECK(hipHostMalloc((void **)&h->h_pinned, (size_t)(m + 2) * NB * sizeof(cplx)));
     }
 
+    // lambda_l and s_l of every level above the dense one (opts[12] = 1; otherwise 0 and exactly 1.0).  Runs on the level work spaces,
+    // one column wide, and leaves them zero as alloc_workspaces left them.
+    // Every step copies one norm back and waits for the stream: 40 round trips per level, which a normalisation on the device would
+    // save.  Left so on purpose: it is set-up time (0.13 s for the whole set-up of the Hermite Rijke family), off by default, and the
+    // host scalar keeps the kernel to one form.
+    void level_weights() {
+        const int nl = (int)h->ops.size();
+        h->lvl_lambda.assign((size_t)nl, 0.0);
+        h->lvl_scale.assign((size_t)nl, 1.0);
+        if (!spectral) return;
+        hipStream_t st = h->stream;
+        DevBuf<cplx> pcd, nrm;
+        nrm.alloc(1);
+        std::vector<cplx> pcl((size_t)h->nplanes);
+        auto norm_of = [&](const cplx *v, int64_t n) {
+            launch_norms(v, n, 1, h->partial.p, nrm.p, st);
+            cplx r{0.0, 0.0};
+            HIP_CHECK(hipMemcpyAsync(&r, nrm.p, sizeof(cplx), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            return r.x;
+        };
+        for (int l = 0; l + 1 < nl; ++l) {
+            const int64_t n = h->ops[l].n;
+            if (n <= 0) continue;
+            slot_coeffs(h, h->slot_plane[l], pc, pcl.data());
+            pcd.upload(pcl.data(), pcl.size(), st);
+            HIP_CHECK(hipStreamSynchronize(st));
+            const OpDev A = h->ops[l].dev(WAE_OP_N);
+            cplx *v = h->lt[l].p, *x = h->lx[l].p, *y = h->lb[l].p;
+            const dim3 grid((unsigned)((n + 255) / 256));
+            hipLaunchKernelGGL(weight_scale_kernel, grid, dim3(256), 0, st, h->ops[l].diag.p, pcd.p, h->nplanes, n, (const cplx *)nullptr, 1.0, v, x);
+            HIP_CHECK(hipGetLastError());
+            double prev = norm_of(v, n), lam = 0.0;
+            for (int k = 0; k < WAE_WEIGHT_POWER_STEPS && prev > 0.0; ++k) {
+                launch_spmv(A, pcd.p, 1, x, y, nullptr, 0.0, 1, MODE_AX, st);
+                hipLaunchKernelGGL(weight_scale_kernel, grid, dim3(256), 0, st, h->ops[l].diag.p, pcd.p, h->nplanes, n, (const cplx *)y, 1.0 / prev, v, x);
+                HIP_CHECK(hipGetLastError());
+                lam = prev = norm_of(v, n);
+            }
+            WAE_REQUIRE(std::isfinite(lam) && lam > 0.0, "level weights: the spectral estimate of a level is not a positive number");
+            h->lvl_lambda[(size_t)l] = lam;
+            h->lvl_scale[(size_t)l] = std::min(1.0, 5.0 / (3.0 * 1.1 * lam));
+            const size_t bytes = (size_t)n * sizeof(cplx);
+            HIP_CHECK(hipMemsetAsync(v, 0, bytes, st));
+            HIP_CHECK(hipMemsetAsync(x, 0, bytes, st));
+            HIP_CHECK(hipMemsetAsync(y, 0, bytes, st));
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (env.debug)
+            for (int l = 0; l + 1 < nl; ++l) fprintf(stderr, "[setup] level %d: lambda %.6g, weight scale %.6g\n", l, h->lvl_lambda[(size_t)l], h->lvl_scale[(size_t)l]);
+    }
+
     void run() {
         read_options();
         drop_hierarchy();
@@ -1234,6 +1314,7 @@ struct SolverSetup {
         dense_coarsest();
         lap("dense coarsest level");
         alloc_workspaces();
+        level_weights();
         h->solver_ready = true;
         lap("other workspaces + memsets");
         if (env.debug) fprintf(stderr, "[setup] uploads + workspaces %.3f s\n", now_s() - t_amg1);
@@ -1259,6 +1340,20 @@ extern "C" int wae_solver_setup_nested(wae_family *h, const double *coeffs_ref, 
         SolverSetup s{h, coeffs_ref, opts, nopts};
         s.supplied = std::move(Ps);
         s.run();
+        return WAE_OK;
+    });
+}
+
+extern "C" int wae_solver_level_weights(const wae_family *h, int32_t cap, double *lambda, double *scale, int32_t *nlev) {
+    return guarded([&]() {
+        WAE_REQUIRE(h && cap >= 0, "bad argument");
+        require_solver(h);
+        const int32_t nl = (int32_t)h->ops.size() - 1;
+        if (nlev) *nlev = nl;
+        for (int32_t l = 0; l < std::min(cap, nl); ++l) {
+            if (lambda) lambda[l] = h->lvl_lambda[(size_t)l];
+            if (scale) scale[l] = h->lvl_scale[(size_t)l];
+        }
         return WAE_OK;
     });
 }

@@ -9,8 +9,9 @@ void upload_pc(wae_family *h, const std::vector<std::vector<zc>> &pcs);
 const cplx *pc_level(const wae_family *h, int l);
 // the dense coarsest level of the systems of the last upload_pc, assembled and inverted
 void dense_setup(wae_family *h, const Batch &bt);
-// weight of the PRE-smoothing sweeps: the set-up's (opts[2]) -- or, in the light cycle of the projected phase, its own (opts[11])
-double pre_weight(const wae_family *h);
+// weight of the PRE-smoothing sweeps of level l: the set-up's (opts[2]) -- or, in the light cycle of the projected phase, its own
+// (opts[11]) -- times the level's scale (opts[12]; exactly 1.0 without it).  The callers outside vcycle() fuse the first sweep of level 0.
+double pre_weight(const wae_family *h, int l = 0);
 // x = Minv b on level l;  returns pointer to the result (either lx[l] or lt[l])
 // have_x0: the first sweep of level l (x = w/diag b) is already in lx[l] (written by the SpMV that produced b, MODE_AX_J0)
 // final_out (level 0 only): the last post-smoothing sweep -- or, in a cycle without one, the prolongation -- writes its result there (a

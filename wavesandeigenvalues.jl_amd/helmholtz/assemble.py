@@ -568,3 +568,55 @@ def _flame_shape_part(pts, tt, sp_, lut, v, va, w0, L, flame, h, device, order="
     q = a_pm * (-nl * b_pm)                                           # v_adj' Q± v  (g = -nlocal grad.n_ref)
     out[:, has] = (-coeff * (q[has, :, 0] - q[has, :, 1]) / (2 * h)).T
     return out
+
+
+def herm_prolongators(points, tets, tris=None, device=0):
+    """The p-hierarchy of a Hermite family on the device (wae_hermite_prolongators): ``[P_face, P_lin]``, scipy CSR, the form
+    ``LinearOperatorFamily.solver_prolongators`` takes.  P_face (ndof x 4N) drops the face unknowns: the centroid value is the one the
+    nine vertex data of the face fix when quadratics are to be reproduced.  P_lin (4N x N) drops the gradients: at a point, the
+    volume-weighted mean of the P1 gradients of the tetrahedra around it.  ``tris`` numbers the faces as in ``assemble_herm``.
+    ValueError, before the library is touched, for arrays that are not (npoints, 3) floats and (ntets, 4) / (ntris, 3) integers."""
+    pts, tt, tr = _herm_mesh_checked(points, tets, tris)
+    L = _lib.lib()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    h = C.c_void_p()
+    _lib.check(L.wae_hermite_prolongators(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), *_tris_args(tr), C.byref(h)))
+    out = []
+    try:
+        for which in (0, 1):
+            rows, cols, nnz = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+            _lib.check(L.wae_hermite_prolongators_info(h, which, C.byref(rows), C.byref(cols), C.byref(nnz)))
+            ptr = np.zeros(rows.value + 1, dtype=np.int32)
+            col = np.zeros(nnz.value, dtype=np.int32)
+            val = np.zeros(nnz.value, dtype=np.float64)
+            _lib.check(L.wae_hermite_prolongators_get(h, which, ptr.ctypes.data_as(ip), col.ctypes.data_as(ip), val.ctypes.data_as(dp)))
+            out.append(sp.csr_matrix((val, col, ptr), shape=(rows.value, cols.value)))
+    finally:
+        L.wae_hermite_prolongators_free(h)
+    return out
+
+
+def _herm_mesh_checked(points, tets, tris):
+    """the mesh arrays of herm_prolongators as contiguous float64 / int32 arrays; ValueError for a wrong shape or dtype"""
+    def ints(a, width, what):
+        a = np.asarray(a)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"{what} must hold integers, got dtype {a.dtype}")
+        if a.ndim != 2 or a.shape[1] != width:
+            raise ValueError(f"{what} must have shape (n, {width}), got {a.shape}")
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError(f"{what} does not fit 32-bit indices")
+        return np.ascontiguousarray(a, dtype=np.int32)
+    pts = np.asarray(points)
+    if pts.dtype.kind not in "fiu":
+        raise ValueError(f"points must hold real numbers, got dtype {pts.dtype}")
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise ValueError(f"points must have shape (npoints, 3), got {pts.shape}")
+    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    if not np.all(np.isfinite(pts)):
+        raise ValueError("points holds a value that is not finite")
+    tt = ints(tets, 4, "tets")
+    if tt.shape[0] < 1:
+        raise ValueError("tets must hold at least one tetrahedron")
+    tr = None if tris is None else ints(tris, 3, "tris")
+    return pts, tt, tr

@@ -30,6 +30,22 @@ def helmholtz_family(terms, Y=1e15, n=1.0, tau=1e-3, device=0, flame=True):
     return L
 
 
+def herm_hierarchy(Lp, points, tets, tris=None, device=None):
+    """Give a Hermite family (terms from ``assemble_herm*`` on this mesh, ``tris`` as there) the set-up that makes its inner solves
+    converge: the p-hierarchy full space -> point unknowns -> P1 as ``solver_prolongators`` (``assemble.herm_prolongators``, built on the
+    device) and ``solver_level_weights = "spectral"``, the Jacobi weights of every level scaled by its own spectral estimate.  Without
+    it the default set-up stagnates on cubic elements.  A solver set-up that exists already is dropped.  Returns Lp."""
+    from .assemble import herm_prolongators
+    Ps = herm_prolongators(points, tets, tris, device=Lp.device_id if device is None else device)
+    if Ps[0].shape[0] != Lp.size():
+        raise ValueError(f"the Hermite space of this mesh has {Ps[0].shape[0]} unknowns, the family {Lp.size()}")
+    Lp.solver_prolongators = Ps
+    Lp.solver_level_weights = "spectral"
+    if Lp._fam is not None:
+        Lp._fam.solver_ready = False
+    return Lp
+
+
 def speaker_source(m, Y=1e15, A=1.0, device=0):
     """The ``rhs`` family that ``discretize(mesh, dscrp, c, source=true)`` returns for a :speaker boundary (src/Helmholtz.jl:79,251-258,
     501-505,519-522): rhs(ω) = ω·Y·A·m with m = -i·s the column of ``assemble_p1_source`` / ``assemble_p2_source``; the response to an

@@ -107,6 +107,15 @@ def _check_prolongators(prolongators, d):
     return out
 
 
+def _check_level_weights(level_weights):
+    """True for "spectral", False for None; ValueError for anything else (before the library is touched)"""
+    if level_weights is None:
+        return False
+    if isinstance(level_weights, str) and level_weights == "spectral":
+        return True
+    raise ValueError(f"level_weights must be None or 'spectral', got {level_weights!r}")
+
+
 class DeviceFamily:
     """Owner of a ``wae_family`` handle: all term matrices resident in HBM (include/waehip.h).
 
@@ -198,12 +207,16 @@ class DeviceFamily:
     # -- solver --------------------------------------------------------------------------------------
     def setup_solver(self, coeffs_ref, theta=0.02, max_coarse=128, jacobi_weight=0.8, sweeps=1, restart=30,
                      penalty_ratio=1e8, batch=64, shape_exclude=(), probe_columns=0, snapshots=0, jacobi_weight_post=0.0,
-                     jacobi_weight_light=0.0, prolongators=None):
+                     jacobi_weight_light=0.0, prolongators=None, level_weights=None):
         """shape_exclude: indices of terms kept out of the multigrid shape matrix (e.g. the seam parts of a Bloch family);
         probe_columns, snapshots: workspace hints for the contour integrals to come (include/waehip.h opts[8], [9]);
         jacobi_weight_post / _light: opts[10], [11] (0 = the library's defaults, 0.9 and 0.5);
         prolongators: None = smoothed aggregation (wae_solver_setup); a list of real sparse matrices, finest first (d x n_1, n_1 x n_2, ...),
-        e.g. ``RefinedMesh.prolongators()`` = the hierarchy is built from them (wae_solver_setup_nested)"""
+        e.g. ``RefinedMesh.prolongators()`` = the hierarchy is built from them (wae_solver_setup_nested);
+        level_weights: None = the three Jacobi weights as they are on every level; "spectral" = opts[12] = 1, every level's weights
+        scaled by min(1, 5 / (3.3 lambda_l)) with the library's estimate lambda_l of lambda_max(D^-1 Re A_ref) there (``level_weights()``
+        reads them back) -- what a cubic (Hermite) level needs, where lambda_max is 5.8 and a weight of 0.8 diverges"""
+        spectral = _check_level_weights(level_weights)
         Ps = None if prolongators is None else _check_prolongators(prolongators, self.d)
         c = np.ascontiguousarray(coeffs_ref, dtype=np.complex128)
         mask = 0
@@ -211,7 +224,7 @@ class DeviceFamily:
             if k < 52:
                 mask |= 1 << int(k)
         opts = np.array([theta, max_coarse, jacobi_weight, sweeps, restart, penalty_ratio, batch, float(mask), float(probe_columns),
-                         float(snapshots), float(jacobi_weight_post), float(jacobi_weight_light)], dtype=np.float64)
+                         float(snapshots), float(jacobi_weight_post), float(jacobi_weight_light)] + ([1.0] if spectral else []), dtype=np.float64)
         if Ps is None:
             check(_lib.lib().wae_solver_setup(self.handle, zptr(c), opts.ctypes.data_as(C.POINTER(C.c_double)), len(opts)))
         else:
@@ -225,6 +238,16 @@ class DeviceFamily:
                                                      arr[0], arr[1], arr[2]))
         self.solver_ready = True
         self.batch = batch
+
+    def level_weights(self):
+        """(lambda, scale): per level above the dense one, the spectral estimate and the factor on its Jacobi weights
+        (wae_solver_level_weights); zeros and ones unless the set-up ran with level_weights="spectral" """
+        n = C.c_int32(0)
+        check(_lib.lib().wae_solver_level_weights(self.handle, 0, None, None, C.byref(n)))
+        lam, scale = np.zeros(n.value), np.zeros(n.value)
+        dp = C.POINTER(C.c_double)
+        check(_lib.lib().wae_solver_level_weights(self.handle, n.value, lam.ctypes.data_as(dp), scale.ctypes.data_as(dp), C.byref(n)))
+        return lam, scale
 
     def solve(self, coeffs, B, op=OP_N, tol=1e-12, maxit=300, strict=False, guess=None, quiet=False):
         c = np.ascontiguousarray(coeffs, dtype=np.complex128)
@@ -642,6 +665,9 @@ class LinearOperatorFamily:
         # None: smoothed aggregation; a list of sparse prolongators, finest first (RefinedMesh.prolongators()): the hierarchy is built
         # from them (wae_solver_setup_nested)
         self.solver_prolongators = None
+        # None: the set-up's Jacobi weights on every level; "spectral": scaled per level by its spectral estimate (opts[12] of the set-up;
+        # helmholtz.family.herm_hierarchy sets both attributes for a Hermite family)
+        self.solver_level_weights = None
         self.rb_snapshots = None        # Beyn: snapshot points for projected initial guesses (None = automatic, 0 = off)
         # when the library may treat a term as symmetric for `A'` products (include/waehip.h wae_family_create_opts opts[0]): 0 = only
         # if it is bitwise symmetric; producers of finite-element terms (helmholtz_family) set 1e-14
@@ -704,6 +730,8 @@ class LinearOperatorFamily:
         fam = self.device()
         nested = getattr(self, "solver_prolongators", None)
         extra = {} if nested is None else {"prolongators": nested}
+        if getattr(self, "solver_level_weights", None) is not None:
+            extra["level_weights"] = self.solver_level_weights
         if not fam.solver_ready and self.solver_ref_coeffs is not None:
             fam.setup_solver(np.asarray(self.solver_ref_coeffs, dtype=np.complex128), **self.solver_opts, **extra)
         if not fam.solver_ready:
