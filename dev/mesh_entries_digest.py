@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""SHA-256 of the raw bytes of everything the mesh-side entries return (assemble.hip, assemble_p2.hip, bloch.hip, octosplit.hip,
-locate.hip), called through the wrappers of helmholtz/ on small fixed meshes: the Kuhn cube with 3^3 cells (64 points, 162 tetrahedra)
-with its boundary triangles, two levels of octosplit, the cube as a periodic cell (3 parts) and the six-point wedge with an axis
+"""SHA-256 of the raw bytes of everything the mesh-side entries return (assemble.hip, assemble_p2.hip, assemble_herm.hip, bloch.hip,
+octosplit.hip, locate.hip), called through the wrappers of helmholtz/ on small fixed meshes: the Kuhn cube with 3^3 cells (64 points,
+162 tetrahedra) with its boundary triangles, two levels of octosplit, the cube as a periodic cell (3 parts) and the six-point wedge with an axis
 (6 parts).  Every variant is called: speed of sound per simplex and per point, P1 and P2, flame, source (also the empty speaker), both
 shape sensitivities with their flame forms, Bloch numbering and fold, P1 and P2 prolongators and prolongation, the locator's find,
-weights and sample for both orders and kinds.
+weights and sample for both orders and kinds; the Hermite entries; and, keys *_jit, assembly, flame and shape sensitivities of every
+order on the cube with jittered points.
 
 The kernels, their launch order and the hipCUB calls fix every bit of these arrays, so two builds of the library that differ only in
-host code must print the same digests.  Prints one JSON object (and writes it to --out).
+host code, or in where a kernel's expressions are written down, must print the same digests.  Prints one JSON object (and writes it
+to --out).
 
     python dev/mesh_entries_digest.py --out profiles/mesh_entries_digest.json
 """
@@ -176,6 +178,48 @@ for target in (0, 2):
             put(f"locator_weights_{target}_{order}_{kind}", *loc.weights(Q, order, kind, n, outside="nan", tol=1e-9))
             put(f"locator_sample_{target}_{order}_{kind}", loc.sample(V, Q, order, kind, n, outside="nan", tol=1e-9))
     loc.close()
+
+# ---- Hermite entries (added after the keys above; nothing above depends on them) --------------------------------------------------------
+put("herm_connectivity", *A.herm_connectivity(pts, tets))
+put("herm_connectivity_tris", *A.herm_connectivity(pts, tets, tris))
+for tag, tr in (("", None), ("_tris", tris)):
+    put(f"herm_assemble{tag}", *A.assemble_herm(pts, tets, tr, dtype=np.float64))
+    put(f"herm_assemble{tag}_c_tet", *A.assemble_herm(pts, tets, tr, c_tet, dtype=np.float64))
+put("herm_boundary", A.assemble_herm_boundary(pts, tets, tris))
+put("herm_boundary_c_tri", A.assemble_herm_boundary(pts, tets, tris, c_tri))
+put("herm_flame", *A.assemble_herm_flame(pts, tets, tris, flame_tets, ref_tet, x_ref, n_ref, 1.75))
+put("herm_prolongators", *A.herm_prolongators(pts, tets, tris))
+
+# ---- the jittered cube: generic Jacobians (on the Kuhn cube they hold only 0 and +-1/3, most products vanish and a different FMA
+# contraction cannot show).  Every point moves by a fixed vector of amplitude 0.05, a sixth of the cell: no tetrahedron inverts.
+ptsj = pts + np.random.default_rng(11).uniform(-0.05, 0.05, pts.shape)
+
+
+def det_j(p):
+    return np.linalg.det(np.transpose(p[tets[:, :3]] - p[tets[:, 3:4]], (0, 2, 1)))
+
+
+assert np.all(np.sign(det_j(ptsj)) == np.sign(det_j(pts))) and np.all(np.abs(det_j(ptsj)) > 1e-3)
+x_refj = ptsj[tets[ref_tet]].mean(axis=0)
+put("p1_assemble_c_tet_jit", *A.assemble_p1(ptsj, tets, c_tet, dtype=np.float64))
+put("p1_assemble_cpoint_jit", *A.assemble_p1(ptsj, tets, c_point=c_point, dtype=np.float64))
+put("p2_assemble_c_tet_jit", *A.assemble_p2(ptsj, tets, c_tet, dtype=np.float64))
+put("p2_assemble_cpoint_jit", *A.assemble_p2(ptsj, tets, c_point=c_point, dtype=np.float64))
+put("herm_assemble_c_tet_jit", *A.assemble_herm(ptsj, tets, tris, c_tet, dtype=np.float64))
+put("p1_flame_jit", *A.assemble_p1_flame(ptsj, tets, flame_tets, ref_tet, n_ref, 1.75))
+put("p2_flame_jit", *A.assemble_p2_flame(ptsj, tets, flame_tets, ref_tet, x_refj, n_ref, 1.75))
+put("herm_flame_jit", *A.assemble_herm_flame(ptsj, tets, tris, flame_tets, ref_tet, x_refj, n_ref, 1.75))
+rngj = np.random.default_rng(13)
+flamej = dict(flame, x_ref=x_refj)
+for order, dim in (("lin", NP), ("quad", NP + NE)):
+    v = rngj.standard_normal(dim) + 1j * rngj.standard_normal(dim)
+    va = rngj.standard_normal(dim) + 1j * rngj.standard_normal(dim)
+    sol = Solution({"ω": 3.0 + 0.4j}, v, va, "ω")
+    kw = dict(v_ext=(v, va), order=order, h=1e-6, Y=0.7 - 0.1j)
+    put(f"shape_{order}_jit", A.discrete_adjoint_shape_sensitivity(ptsj, tets, c_tet, surface, sol, None, bnd_tris=tris, bnd_c=c_tri, **kw))
+    put(f"shape_{order}_cpoint_jit", A.discrete_adjoint_shape_sensitivity(ptsj, tets, None, surface, sol, None, bnd_tris=tris, c_point=c_point, **kw))
+    put(f"shape_{order}_flame_jit",
+        A.discrete_adjoint_shape_sensitivity(ptsj, tets, c_tet, np.unique(tets[flame_tets])[::2], sol, None, flame=flamej, **kw))
 
 print(json.dumps(res))
 if a.out:

@@ -76,6 +76,8 @@ def lib():
     L = C.CDLL(LIB_PATH)
     dp = C.POINTER(C.c_double)
     vpp = C.POINTER(C.c_void_p)
+    i32p = C.POINTER(C.c_int32)
+    i64p = C.POINTER(C.c_int64)
     L.wae_last_error.restype = C.c_char_p
     L.wae_version.restype = C.c_char_p
     L.wae_device_count.argtypes = [C.POINTER(C.c_int)]
@@ -102,9 +104,8 @@ def lib():
                                       C.POINTER(SolveInfo)]
     L.wae_beyn_moments_mgpu.argtypes = [vpp, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, dp,
                                         C.POINTER(SolveInfo)]
-    ip = C.POINTER(C.c_int32)
-    L.wae_rb_export.argtypes = [C.c_void_p, ip, ip, ip, ip, dp, dp]
-    L.wae_rb_import.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, ip, dp, dp]
+    L.wae_rb_export.argtypes = [C.c_void_p, i32p, i32p, i32p, i32p, dp, dp]
+    L.wae_rb_import.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, i32p, dp, dp]
     L.wae_eig_residuals.argtypes = [C.c_void_p, C.c_int32, dp, dp, C.c_uint64, dp]
     L.wae_arnoldi_shiftinvert.argtypes = [C.c_void_p, dp, dp, C.c_int32, dp, C.c_int32, C.c_double, C.c_int32, dp, dp,
                                           C.POINTER(SolveInfo)]
@@ -112,20 +113,19 @@ def lib():
                                                 dp, dp, C.POINTER(SolveInfo)]
     L.wae_perturb.argtypes = [C.c_void_p, dp, C.c_int32, dp, dp, C.c_int32, dp, C.c_double, C.c_int32, dp, dp,
                               C.POINTER(SolveInfo)]
-    ip = C.POINTER(C.c_int32)
     L.wae_slot_write.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp]
     L.wae_slot_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, dp]
-    L.wae_slot_axpby.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip, C.c_int32, ip, dp, dp, C.c_int32]
-    L.wae_slot_forms.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, C.c_int32, ip, C.c_int32, ip, dp]
-    L.wae_arnoldi_shiftinvert_slots.argtypes = [C.c_void_p, C.c_int32, dp, dp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_double, C.c_int32, C.c_double,
+    L.wae_slot_axpby.argtypes = [C.c_void_p, C.c_int32, C.c_int32, i32p, C.c_int32, i32p, dp, dp, C.c_int32]
+    L.wae_slot_forms.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, C.c_int32, i32p, C.c_int32, i32p, dp]
+    L.wae_arnoldi_shiftinvert_slots.argtypes = [C.c_void_p, C.c_int32, dp, dp, C.c_int32, C.c_int32, i32p, C.c_int32, C.c_double, C.c_int32, C.c_double,
                                                 dp, C.POINTER(SolveInfo)]
-    L.wae_arnoldi_ritz_to_slot.argtypes = [C.c_void_p, C.c_int32, C.c_int32, dp, C.c_int32, ip, C.c_int32]
+    L.wae_arnoldi_ritz_to_slot.argtypes = [C.c_void_p, C.c_int32, C.c_int32, dp, C.c_int32, i32p, C.c_int32]
     L.wae_perturb_slots.argtypes = [C.c_void_p, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, C.c_double, C.c_int32, dp, dp,
                                     C.POINTER(SolveInfo)]
-    L.wae_perturb_batch.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, dp, dp, C.c_int32, dp, C.c_double, C.c_int32, dp, dp, ip,
+    L.wae_perturb_batch.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, dp, dp, C.c_int32, dp, C.c_double, C.c_int32, dp, dp, i32p,
                                     C.POINTER(SolveInfo)]
-    L.wae_perturb_batch_slots.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, C.c_int32, ip, C.c_int32, ip, C.c_int32, dp, C.c_double, C.c_int32,
-                                          dp, dp, ip, C.POINTER(SolveInfo)]
+    L.wae_perturb_batch_slots.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, C.c_int32, i32p, C.c_int32, i32p, C.c_int32, dp, C.c_double, C.c_int32,
+                                          dp, dp, i32p, C.POINTER(SolveInfo)]
     L.wae_p1_assemble.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, C.POINTER(C.c_int32), dp, C.POINTER(C.c_void_p)]
     L.wae_p1_assemble_boundary.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, C.POINTER(C.c_int32), dp, C.POINTER(C.c_void_p)]
     L.wae_p1_assemble_flame.argtypes = [C.c_int32, C.c_int64, dp, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int32), C.c_int32, dp,
@@ -133,8 +133,6 @@ def lib():
     L.wae_p1_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.wae_p1_get.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp]
     L.wae_p1_free.argtypes = [C.c_void_p]
-    i32p = C.POINTER(C.c_int32)
-    i64p = C.POINTER(C.c_int64)
     L.wae_p2_connectivity.argtypes = [C.c_int32, C.c_int64, C.c_int64, i32p, C.c_int64, i32p, C.POINTER(C.c_void_p)]
     L.wae_p2_connectivity_info.argtypes = [C.c_void_p, i64p, i64p, i64p]
     L.wae_p2_connectivity_get.argtypes = [C.c_void_p, i32p, i32p, i32p]
@@ -207,9 +205,9 @@ def lib():
     L.wae_debug_prolong.argtypes = [C.c_void_p, C.c_int32, dp, dp, dp, dp, C.c_int32, C.POINTER(C.c_uint8), C.c_int32]
     L.wae_debug_vcycle.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
     L.wae_debug_vec.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.c_int32,
-                                C.POINTER(C.c_uint8), ip, ip]
+                                C.POINTER(C.c_uint8), i32p, i32p]
     L.wae_debug_gmres.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, dp, C.POINTER(C.c_int64), dp, C.c_int32, dp, C.c_int64,
-                                  dp, dp, dp, ip, C.POINTER(C.c_uint8), dp, dp, dp]
+                                  dp, dp, dp, i32p, C.POINTER(C.c_uint8), dp, dp, dp]
     L.wae_tall_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32]
     L.wae_tall_destroy.argtypes = [C.c_void_p]
     L.wae_tall_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]

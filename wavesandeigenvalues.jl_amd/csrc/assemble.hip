@@ -2,7 +2,7 @@
 //
 // Replaces the element loops of `discretize` for the two operators that dominate its run time
 // (src/Helmholtz.jl:405-441: every tetrahedron contributes a 4x4 block to M and to K) with
-//   1. one kernel: per tetrahedron the coordinate transformation (src/FEM/FEM.jl:9-20), the local mass matrix
+//   1. one kernel: per tetrahedron the coordinate transformation (src/FEM/FEM.jl:9-20; tet_geometry.h), the local mass matrix
 //      |det J|/120 (1 + delta_ab) (FEM.jl:704-710) and the local stiffness matrix -c^2 |det J|/6 grad phi_a . grad phi_b
 //      (FEM.jl:1745-1766, Helmholtz.jl:120-124), written as 16 (key = row*np + col, m, k) triplets;
 //   2. a stable radix sort of the keys (hipCUB) -- duplicates become adjacent, in element order, so the sums below are
@@ -13,27 +13,15 @@
 #include <memory>
 #include <vector>
 
-#include "mesh_host.h"
+#include "tet_geometry.h"
 #include "../../include/waehip.h"
 
 namespace {
 
 // local P1 matrices of one tetrahedron with corner coordinates X: M_ab = |det J|/120 (1+delta_ab), K_ab = -c^2 |det J|/6 grad_a.grad_b
 __device__ inline void p1_local(const double X[4][3], double c, double M[16], double K[16]) {
-    double J[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int a = 0; a < 3; ++a) J[r][a] = X[a][r] - X[3][r];
-    const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-    const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-    const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-    const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-    const double adet = fabs(det);
-    const double id = 1.0 / det;
     double G[4][3];
-    G[0][0] = c00 * id; G[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id; G[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-    G[1][0] = c01 * id; G[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id; G[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-    G[2][0] = c02 * id; G[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id; G[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-    for (int k = 0; k < 3; ++k) G[3][k] = -(G[0][k] + G[1][k] + G[2][k]);
+    const double adet = fabs(tet_gradients(X, G));
     const double ks = -(c * c) * adet / 6.0;
     for (int a = 0; a < 4; ++a)
         for (int b = 0; b < 4; ++b) {
@@ -287,7 +275,7 @@ P1Handle *triplets_to_csr(int64_t npoints, size_t ne, Dev<unsigned long long> &k
     return H.release();
 }
 
-// (declared in mesh_host.h: assemble_p2.hip sums its flame with it too)
+// (declared in mesh_host.h: FlameSetup of tet_geometry.h sums every order's flame with it)
 double flame_volume(const Dev<double> &adet, int64_t nflame) {
     const double volume = device_sum(adet.p, (int)nflame) / 6.0;
     if (!(volume > 0.0)) throw WaeError(WAE_ERR_INVALID, "flame domain has no volume");
@@ -381,22 +369,6 @@ __global__ __launch_bounds__(256) void p1_source_kernel(const double *__restrict
     }
 }
 
-// |det J| of the listed tetrahedra (volume source S_a = |det J|/24 per node, FEM.jl:2429-2431; flame volume = sum |det J|/6)
-__global__ __launch_bounds__(256) void p1_det_kernel(const double *__restrict__ pts, const int *__restrict__ tets, const int *__restrict__ list, int64_t n,
-                                                     double *__restrict__ adet) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int t = list[i];
-    double X[4][3];
-    for (int a = 0; a < 4; ++a)
-        for (int k = 0; k < 3; ++k) X[a][k] = pts[(size_t)tets[(size_t)t * 4 + a] * 3 + k];
-    double J[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int a = 0; a < 3; ++a) J[r][a] = X[a][r] - X[3][r];
-    const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) + J[0][1] * (J[1][2] * J[2][0] - J[1][0] * J[2][2]) +
-                       J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-    adet[i] = fabs(det);
-}
 // Q triplets: (node a of flame tetrahedron i, node b of the reference tetrahedron) -> |det J_i|/24 * g_b   (Helmholtz.jl:19-33,483)
 __global__ __launch_bounds__(256) void p1_flame_kernel(const int *__restrict__ tets, const int *__restrict__ list, int64_t n, const double *__restrict__ adet,
                                                        int r0, int r1, int r2, int r3, double g0, double g1, double g2, double g3, int64_t np,
@@ -445,11 +417,8 @@ __global__ __launch_bounds__(256) void shape_flame_kernel(const double *__restri
     }
     if (crd == 0) ssum[pr] = sa;
     auto adet = [&]() {
-        double J[3][3];
-        for (int r = 0; r < 3; ++r)
-            for (int a = 0; a < 3; ++a) J[r][a] = X[a][r] - X[3][r];
-        return fabs(J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) + J[0][1] * (J[1][2] * J[2][0] - J[1][0] * J[2][2]) +
-                    J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]));
+        double J[3][3], Ji[3][3];
+        return fabs(tet_jacobian(X, J, Ji));
     };
     if (a0 < 0) { det_pm[e * 2] = det_pm[e * 2 + 1] = adet(); return; }
     const double x0 = X[a0][crd];
@@ -474,16 +443,8 @@ __global__ void shape_ref_kernel(const double *__restrict__ pts, const int *__re
         for (int a = 0; a < 4; ++a)
             if (vtx[a] == pair_pt[pr]) X[a][crd] += sgn ? -h : h;
     }
-    double J[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int a = 0; a < 3; ++a) J[r][a] = X[a][r] - X[3][r];
-    const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1], c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2], c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-    const double id = 1.0 / (J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02);
     double G[4][3];
-    G[0][0] = c00 * id; G[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id; G[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-    G[1][0] = c01 * id; G[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id; G[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-    G[2][0] = c02 * id; G[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id; G[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-    for (int k = 0; k < 3; ++k) G[3][k] = -(G[0][k] + G[1][k] + G[2][k]);
+    tet_gradients(X, G);
     cplx acc = {0.0, 0.0};
     for (int b = 0; b < 4; ++b) {
         const double gb = G[b][0] * n0 + G[b][1] * n1 + G[b][2] * n2;
@@ -584,37 +545,17 @@ int wae_p1_assemble_flame(int32_t device, int64_t npoints, const double *points,
         check_tets(tets, ntets, npoints);
         HIP_CHECK(hipSetDevice(device));
         const size_t ne = (size_t)nflame * 16;
-        Dev<double> dpts(points, (size_t)npoints * 3), adet((size_t)nflame), qv(ne);
-        Dev<int> dt(tets, (size_t)ntets * 4), dl(flame_tets, (size_t)nflame);
+        Dev<double> dpts(points, (size_t)npoints * 3), qv(ne);
+        Dev<int> dt(tets, (size_t)ntets * 4);
         Dev<unsigned long long> k0(ne);
-        hipLaunchKernelGGL(p1_det_kernel, grid_for(nflame), dim3(256), 0, 0, dpts.p, dt.p, dl.p, nflame, adet.p);
-        HIP_CHECK(hipGetLastError());
-        const double volume = flame_volume(adet, nflame);
-        if (volume_out) *volume_out = volume;
-        const double nlocal = nglobal_scaled / volume;                                 // Helmholtz.jl:325
+        FlameSetup<4> f(dpts.p, dt.p, nflame, flame_tets, nglobal_scaled, volume_out, points, tets, ref_tet);
         // g_b = -nlocal grad(phi_b) . n_ref on the reference tetrahedron (FEM.jl:2442-2448, Helmholtz.jl:482): 4 numbers, on the host
-        int rn[4];
-        double X[4][3];
-        for (int a = 0; a < 4; ++a) {
-            rn[a] = tets[(size_t)ref_tet * 4 + a];
-            for (int k = 0; k < 3; ++k) X[a][k] = points[(size_t)rn[a] * 3 + k];
-        }
-        double J[3][3];
-        for (int r = 0; r < 3; ++r)
-            for (int a = 0; a < 3; ++a) J[r][a] = X[a][r] - X[3][r];
-        const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1], c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2], c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-        const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-        if (det == 0.0) throw WaeError(WAE_ERR_INVALID, "degenerate reference tetrahedron");
-        const double id = 1.0 / det;
-        double G[4][3];
-        G[0][0] = c00 * id; G[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id; G[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-        G[1][0] = c01 * id; G[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id; G[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-        G[2][0] = c02 * id; G[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id; G[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-        for (int k = 0; k < 3; ++k) G[3][k] = -(G[0][k] + G[1][k] + G[2][k]);
-        double g[4];
-        for (int b = 0; b < 4; ++b) g[b] = -nlocal * (G[b][0] * n_ref[0] + G[b][1] * n_ref[1] + G[b][2] * n_ref[2]);
-        hipLaunchKernelGGL(p1_flame_kernel, grid_for(nflame), dim3(256), 0, 0, dt.p, dl.p, nflame, adet.p, rn[0], rn[1], rn[2], rn[3], g[0], g[1], g[2], g[3], npoints,
-                           k0.p, qv.p);
+        double G[4][3], g[4];
+        if (tet_gradients(f.X, G) == 0.0) throw WaeError(WAE_ERR_INVALID, "degenerate reference tetrahedron");
+        for (int b = 0; b < 4; ++b) g[b] = -f.nlocal * (G[b][0] * n_ref[0] + G[b][1] * n_ref[1] + G[b][2] * n_ref[2]);
+        const int32_t *rn = tets + (size_t)ref_tet * 4;
+        hipLaunchKernelGGL(p1_flame_kernel, grid_for(nflame), dim3(256), 0, 0, dt.p, f.list.p, nflame, f.adet.p, rn[0], rn[1], rn[2], rn[3], g[0], g[1], g[2], g[3],
+                           npoints, k0.p, qv.p);
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(npoints, ne, k0, qv, nullptr);
         return WAE_OK;

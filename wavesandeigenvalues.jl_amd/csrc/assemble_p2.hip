@@ -8,6 +8,7 @@
 //   2. Element kernels, one thread per (simplex, local row): 10 (tetrahedron) or 6 (triangle) triplets of that row.  A thread keeps
 //      no array that it indexes by its row number: what depends on the row is read from the basis tables in constant memory.
 //   3. triplets_to_csr (assemble.hip): stable sort, reduce-by-key, row pointer -- deterministic, no atomics.
+// The gradients of the barycentric coordinates, |det J| of the flame tetrahedra and the flame set-up: tet_geometry.h.
 //
 // Basis (barycentric coordinates l_1..l_n, n = 4 or 3): vertex functions l_i (2 l_i - 1), edge functions 4 l_i l_j, local order
 // vertices first, then the edges (1,2), (1,3), (1,4), (2,3), (2,4), (3,4) resp. (1,2), (1,3), (2,3).  With sum l = 1 every function is
@@ -20,7 +21,7 @@
 #include <vector>
 
 #include "edge_keys.h"
-#include "mesh_host.h"
+#include "tet_geometry.h"
 
 namespace {
 
@@ -161,23 +162,6 @@ constexpr P2SourceC make_p2_source_c() {
 constexpr P2SourceC kSourceC = make_p2_source_c();
 __constant__ P2SourceC dSourceC = kSourceC;
 
-// G[a] = grad l_a of the tetrahedron with corners X (l_4 = 1 - l_1 - l_2 - l_3, corner 4 is the origin: CooTrafo, FEM.jl:9-20); returns det J
-__host__ __device__ inline double p2_tet_gradients(const double X[4][3], double G[4][3]) {
-    double J[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int a = 0; a < 3; ++a) J[r][a] = X[a][r] - X[3][r];
-    const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-    const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-    const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-    const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-    const double id = 1.0 / det;
-    G[0][0] = c00 * id; G[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id; G[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-    G[1][0] = c01 * id; G[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id; G[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-    G[2][0] = c02 * id; G[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id; G[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-    for (int k = 0; k < 3; ++k) G[3][k] = -(G[0][k] + G[1][k] + G[2][k]);
-    return det;
-}
-
 // grad phi = sum_k l_k w[k] with w[k] = sum_i d[i][k] grad l_i; s = sum_k w[k].  One fixed order of operations, so that the row's and
 // the column's function get the same bits and K_ab == K_ba.
 __host__ __device__ inline void p2_grad_coeffs(const double d[4][4], const double G[4][3], double w[4][3], double s[3]) {
@@ -272,7 +256,7 @@ __global__ __launch_bounds__(256) void p2_local_kernel(const double *__restrict_
 #pragma unroll
     for (int v = 0; v < 4; ++v)
         for (int k = 0; k < 3; ++k) X[v][k] = pts[(size_t)nd[v] * 3 + k];
-    const double adet = fabs(p2_tet_gradients(X, G));
+    const double adet = fabs(tet_gradients(X, G));
     const double c = c_tet ? c_tet[t] : 1.0;
     const double ks = -(c * c) * adet / 120.0;
     double wa[4][3], sa[3];
@@ -376,7 +360,7 @@ __global__ __launch_bounds__(256) void p2_local_cpoint_kernel(const double *__re
         for (int pq = 1; pq < 10; ++pq) x = fma(cc[pq], dNodalC.quart[km][pq], x);
         W[km] = x;
     }
-    const double nadet = -fabs(p2_tet_gradients(X, G));
+    const double nadet = -fabs(tet_gradients(X, G));
 #pragma unroll
     for (int v = 0; v < 4; ++v)
         for (int k = 0; k < 3; ++k) G[v][k] = p2_opaque(G[v][k]);
@@ -457,19 +441,6 @@ __global__ __launch_bounds__(256) void p2_source_kernel(const double *__restrict
     else sv[e] = (c ? c[t] : 1.0) * det * dTri.src[a];
 }
 
-// |det J| of the listed tetrahedra (flame volume = sum |det J| / 6)
-__global__ __launch_bounds__(256) void p2_det_kernel(const double *__restrict__ pts, const int *__restrict__ t10, const int *__restrict__ list, int64_t n,
-                                                     double *__restrict__ adet) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int64_t t = list[i];
-    double X[4][3], G[4][3];
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-        for (int k = 0; k < 3; ++k) X[v][k] = pts[(size_t)t10[t * 10 + v] * 3 + k];
-    adet[i] = fabs(p2_tet_gradients(X, G));
-}
-
 // Q triplets: (node a of flame tetrahedron i, node b of the reference tetrahedron) -> |det J_i| int phi_a * g_b
 __global__ __launch_bounds__(256) void p2_flame_kernel(const int *__restrict__ t10, const int *__restrict__ list, int64_t n, const double *__restrict__ adet,
                                                        int ref_tet, const double *__restrict__ g, u64 dim, u64 *__restrict__ keys, double *__restrict__ qv) {
@@ -508,7 +479,7 @@ template <int CRD> __device__ inline double p2_shape_geometry(const double X[4][
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int k = 0; k < 3; ++k) Xd[a][k] = (k == CRD && a == a0) ? X[a][k] + d : X[a][k];
-    const double adet = fabs(p2_tet_gradients(Xd, G));
+    const double adet = fabs(tet_gradients(Xd, G));
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -726,7 +697,7 @@ template <int CRD> __device__ inline double p2_shape_adet(const double X[4][3], 
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int k = 0; k < 3; ++k) Xd[a][k] = (k == CRD && a == a0) ? X[a][k] + d : X[a][k];
-    return fabs(p2_tet_gradients(Xd, G));
+    return fabs(tet_gradients(Xd, G));
 }
 
 __global__ __launch_bounds__(256) void p2_shape_flame_kernel(const double *__restrict__ pts, const int *__restrict__ t10, int64_t npair,
@@ -772,7 +743,7 @@ template <int CRD> __device__ inline cplx p2_shape_ref_value(const double X[4][3
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int k = 0; k < 3; ++k) Xd[a][k] = (k == CRD && a == a0) ? X[a][k] + d : X[a][k];
-    p2_tet_gradients(Xd, G);
+    tet_gradients(Xd, G);
     lam[3] = 1.0;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -1124,19 +1095,13 @@ int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points,
         HIP_CHECK(hipSetDevice(device));
         P2Mesh m(npoints, points, ntets, tets, 0, nullptr);
         const size_t ne = (size_t)nflame * 100;
-        Dev<double> adet((size_t)nflame), qv(ne);
-        Dev<int> dl(flame_tets, (size_t)nflame);
+        Dev<double> qv(ne);
         Dev<u64> k0(ne);
-        hipLaunchKernelGGL(p2_det_kernel, grid_for(nflame), dim3(256), 0, 0, m.pts.p, m.t10.p, dl.p, nflame, adet.p);
-        HIP_CHECK(hipGetLastError());
-        const double volume = flame_volume(adet, nflame);
-        if (volume_out) *volume_out = volume;
-        const double nlocal = nglobal_scaled / volume;                                 // Helmholtz.jl:325
+        FlameSetup<10> f(m.pts.p, m.t10.p, nflame, flame_tets, nglobal_scaled, volume_out, points, tets, ref_tet);
         // g_b = -nlocal grad(phi_b)(x_ref) . n_ref on the 10 nodes of the reference tetrahedron (Helmholtz.jl:477-482): 10 numbers, on the host
-        double X[4][3], G[4][3];
-        for (int a = 0; a < 4; ++a)
-            for (int k = 0; k < 3; ++k) X[a][k] = points[(size_t)tets[(size_t)ref_tet * 4 + a] * 3 + k];
-        if (p2_tet_gradients(X, G) == 0.0) throw WaeError(WAE_ERR_INVALID, "degenerate reference tetrahedron");
+        const double(&X)[4][3] = f.X;
+        double G[4][3];
+        if (tet_gradients(X, G) == 0.0) throw WaeError(WAE_ERR_INVALID, "degenerate reference tetrahedron");
         double lam[4];
         lam[3] = 1.0;
         for (int a = 0; a < 3; ++a) {
@@ -1148,10 +1113,10 @@ int wae_p2_assemble_flame(int32_t device, int64_t npoints, const double *points,
             double w[4][3], s[3], acc = 0.0;
             p2_grad_coeffs(kTet.d[b], G, w, s);
             for (int k = 0; k < 4; ++k) acc += lam[k] * (w[k][0] * n_ref[0] + w[k][1] * n_ref[1] + w[k][2] * n_ref[2]);
-            g[b] = -nlocal * acc;
+            g[b] = -f.nlocal * acc;
         }
         Dev<double> dg(g, 10);
-        hipLaunchKernelGGL(p2_flame_kernel, grid_for(nflame * 10), dim3(256), 0, 0, m.t10.p, dl.p, nflame, adet.p, ref_tet, dg.p,
+        hipLaunchKernelGGL(p2_flame_kernel, grid_for(nflame * 10), dim3(256), 0, 0, m.t10.p, f.list.p, nflame, f.adet.p, ref_tet, dg.p,
                            (u64)m.dim, k0.p, qv.p);
         HIP_CHECK(hipGetLastError());
         *out = triplets_to_csr(m.dim, ne, k0, qv, nullptr);

@@ -33,117 +33,125 @@ def _nodal(c_point, c_simplex, npoints, what):
     return cp
 
 
-def assemble_p1(points, tets, c_tet=None, device=0, dtype=np.complex128, c_point=None):
-    """points (npoints, 3), tets (ntets, 4) 0-based, c_tet (ntets,) speed of sound per tetrahedron (None = 1) or c_point (npoints,)
-    speed of sound per mesh point, linear on every tetrahedron (wae_p1_assemble_cpoint; Helmholtz.jl:59-74).
-    Returns (M, K) as scipy CSR matrices sharing one pattern; K = -∫ c² ∇φ_a·∇φ_b as in the reference (Helmholtz.jl:120-124)."""
+DP, I32P = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+
+
+def _ptr(a):
+    """the pointer of a float64 or int32 array; None stays NULL"""
+    return None if a is None else a.ctypes.data_as(DP if a.dtype == np.float64 else I32P)
+
+
+def _npoints(points):
+    """``points``: the (npoints, 3) array or just npoints"""
+    return int(points) if np.ndim(points) == 0 else np.asarray(points).reshape(-1, 3).shape[0]
+
+
+def _mesh_args(points, tets=None, tris=None):
     pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    tt = np.ascontiguousarray(tets, dtype=np.int32).reshape(-1, 4)
-    cp = _nodal(c_point, c_tet, pts.shape[0], "c_tet")
-    cc = cp if cp is not None else None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
-    L = _lib.lib()
-    h = C.c_void_p()
-    dp = C.POINTER(C.c_double)
-    entry = L.wae_p1_assemble if cp is None else L.wae_p1_assemble_cpoint
-    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
-                     None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
-    return _take_pair(L, h, dtype)
+    tt = None if tets is None else np.ascontiguousarray(tets, dtype=np.int32).reshape(-1, 4)
+    tr = None if tris is None else np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    return pts, tt, tr
 
 
-def _take_pair(L, h, dtype):
-    """copy an assembly handle with two value streams out as (M, K), scipy CSR matrices sharing one pattern, and free it"""
-    dp = C.POINTER(C.c_double)
+def _counted(a, optional=False):
+    """(count, pointer) of an index list; optional: (0, NULL) for None and for an empty list"""
+    return (0, None) if optional and (a is None or not len(a)) else (a.shape[0], _ptr(a))
+
+
+def _prefix(device, pts, simplices, *tris):
+    """the arguments every mesh entry starts with: device, npoints, points*, ntets, tets* (P1 boundary and source: the triangles in their
+    place), and for the entries that take both lists what _counted made of the triangles: ntris, tris*"""
+    return [int(device), pts.shape[0], _ptr(pts), *_counted(simplices), *tris]
+
+
+def _matrix_c(c_simplex, c_point, npoints, what):
+    """(values or None, nodal?) of the speed of sound of a matrix wrapper, c_point checked"""
+    cp = _nodal(c_point, c_simplex, npoints, what)
+    if cp is not None:
+        return cp, True
+    return None if c_simplex is None else np.ascontiguousarray(c_simplex, dtype=np.float64), False
+
+
+def _take(L, h, dtype, pair=False):
+    """copy an assembly handle out and free it: one scipy CSR matrix (values = the `mass` array) or, pair, (M, K) sharing one pattern"""
     try:
         n, nnz = C.c_int64(0), C.c_int64(0)
         _lib.check(L.wae_p1_info(h, C.byref(n), C.byref(nnz)))
         rowptr = np.zeros(n.value + 1, dtype=np.int32)
         col = np.zeros(nnz.value, dtype=np.int32)
         m = np.zeros(nnz.value, dtype=np.float64)
-        k = np.zeros(nnz.value, dtype=np.float64)
-        _lib.check(L.wae_p1_get(h, rowptr.ctypes.data_as(C.POINTER(C.c_int32)), col.ctypes.data_as(C.POINTER(C.c_int32)),
-                                m.ctypes.data_as(dp), k.ctypes.data_as(dp)))
+        k = np.zeros(nnz.value, dtype=np.float64) if pair else None
+        _lib.check(L.wae_p1_get(h, _ptr(rowptr), _ptr(col), _ptr(m), _ptr(k)))
     finally:
         L.wae_p1_free(h)
     shape = (n.value, n.value)
-    return (sp.csr_matrix((m.astype(dtype), col, rowptr), shape=shape), sp.csr_matrix((k.astype(dtype), col.copy(), rowptr.copy()), shape=shape))
+    M = sp.csr_matrix((m.astype(dtype), col, rowptr), shape=shape)
+    return (M, sp.csr_matrix((k.astype(dtype), col.copy(), rowptr.copy()), shape=shape)) if pair else M
 
 
-def _take_csr(L, h, dtype):
-    """copy a P1 handle out as a scipy CSR matrix (values = the `mass` array) and free it"""
-    dp = C.POINTER(C.c_double)
-    try:
-        n, nnz = C.c_int64(0), C.c_int64(0)
-        _lib.check(L.wae_p1_info(h, C.byref(n), C.byref(nnz)))
-        rowptr = np.zeros(n.value + 1, dtype=np.int32)
-        col = np.zeros(nnz.value, dtype=np.int32)
-        v = np.zeros(nnz.value, dtype=np.float64)
-        _lib.check(L.wae_p1_get(h, rowptr.ctypes.data_as(C.POINTER(C.c_int32)), col.ctypes.data_as(C.POINTER(C.c_int32)), v.ctypes.data_as(dp), None))
-    finally:
-        L.wae_p1_free(h)
-    return sp.csr_matrix((v.astype(dtype), col, rowptr), shape=(n.value, n.value))
+def _assembled(name, args, dtype=np.complex128, pair=False):
+    """the matrix (or pair) of the entry `name` called with args and the handle's address"""
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(getattr(L, name)(*args, C.byref(h)))
+    return _take(L, h, dtype, pair)
+
+
+def _flame(name, prefix, flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled):
+    """(Q, V_flame) of a flame entry; x_ref: None for P1, which takes none"""
+    fl = np.ascontiguousarray(flame_tets, dtype=np.int32)
+    ref = [np.ascontiguousarray(x, dtype=np.float64) for x in (x_ref, n_ref) if x is not None]
+    assert x_ref is None or (ref[0].shape == (3,) and ref[1].shape == (3,))
+    L = _lib.lib()
+    h = C.c_void_p()
+    vol = C.c_double(0.0)
+    _lib.check(getattr(L, name)(*prefix, len(fl), _ptr(fl), int(ref_tet), *[_ptr(x) for x in ref], float(nglobal_scaled), C.byref(h), C.byref(vol)))
+    return _take(L, h, np.complex128), vol.value
+
+
+def assemble_p1(points, tets, c_tet=None, device=0, dtype=np.complex128, c_point=None):
+    """points (npoints, 3), tets (ntets, 4) 0-based, c_tet (ntets,) speed of sound per tetrahedron (None = 1) or c_point (npoints,)
+    speed of sound per mesh point, linear on every tetrahedron (wae_p1_assemble_cpoint; Helmholtz.jl:59-74).
+    Returns (M, K) as scipy CSR matrices sharing one pattern; K = -∫ c² ∇φ_a·∇φ_b as in the reference (Helmholtz.jl:120-124)."""
+    pts, tt, _ = _mesh_args(points, tets)
+    cc, nodal = _matrix_c(c_tet, c_point, pts.shape[0], "c_tet")
+    return _assembled("wae_p1_assemble_cpoint" if nodal else "wae_p1_assemble", [*_prefix(device, pts, tt), _ptr(cc)], dtype, pair=True)
 
 
 def assemble_p1_boundary(points, tris, c_tri=None, device=0, c_point=None):
     """Boundary mass term of an admittance boundary on the device (wae_p1_assemble_boundary):
     C = -i·c·|e1×e2|·(1+δ_ab)/24 per boundary triangle (src/Helmholtz.jl:443-463, src/FEM/FEM.jl:435-441); with c_point (npoints,)
     instead of c_tri, C = -i·|e1×e2|·∫c φ_aφ_b with c linear on every triangle (wae_p1_assemble_boundary_cpoint).  Returns C (complex CSR)."""
-    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    tt = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
-    cp = _nodal(c_point, c_tri, pts.shape[0], "c_tri")
-    cc = cp if cp is not None else None if c_tri is None else np.ascontiguousarray(c_tri, dtype=np.float64)
-    L = _lib.lib()
-    h = C.c_void_p()
-    dp = C.POINTER(C.c_double)
-    entry = L.wae_p1_assemble_boundary if cp is None else L.wae_p1_assemble_boundary_cpoint
-    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
-                     None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
-    return -1j * _take_csr(L, h, np.complex128)
+    pts, _, tr = _mesh_args(points, tris=tris)
+    cc, nodal = _matrix_c(c_tri, c_point, pts.shape[0], "c_tri")
+    return -1j * _assembled("wae_p1_assemble_boundary_cpoint" if nodal else "wae_p1_assemble_boundary", [*_prefix(device, pts, tr), _ptr(cc)])
 
 
 def assemble_p1_flame(points, tets, flame_tets, ref_tet, n_ref, nglobal_scaled, device=0):
     """Flame operator Q = Σ_flame S ⊗ g on the device (wae_p1_assemble_flame; src/Helmholtz.jl:292-344,464-487):
     ``nglobal_scaled`` = (γ-1)/ρ·Q02U0, the library divides by the flame volume it sums itself.  Returns (Q, V_flame)."""
-    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    tt = np.ascontiguousarray(tets, dtype=np.int32).reshape(-1, 4)
-    fl = np.ascontiguousarray(flame_tets, dtype=np.int32)
-    nr = np.ascontiguousarray(n_ref, dtype=np.float64)
-    L = _lib.lib()
-    h = C.c_void_p()
-    vol = C.c_double(0.0)
-    dp = C.POINTER(C.c_double)
-    ip = C.POINTER(C.c_int32)
-    _lib.check(L.wae_p1_assemble_flame(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), len(fl), fl.ctypes.data_as(ip),
-                                       int(ref_tet), nr.ctypes.data_as(dp), float(nglobal_scaled), C.byref(h), C.byref(vol)))
-    return _take_csr(L, h, np.complex128), vol.value
+    pts, tt, _ = _mesh_args(points, tets)
+    return _flame("wae_p1_assemble_flame", _prefix(device, pts, tt), flame_tets, ref_tet, None, n_ref, nglobal_scaled)
 
 
 # ---- P2 (second-order) elements: `discretize(...; order=:quad)` ---------------------------------------------------------------
-def _mesh_args(points, tets, tris=None):
-    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    tt = np.ascontiguousarray(tets, dtype=np.int32).reshape(-1, 4)
-    tr = None if tris is None else np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
-    return pts, tt, tr
-
-
 def p2_connectivity(points, tets, tris=None, device=0):
     """Edge DoFs of the P2 space numbered on the device (wae_p2_connectivity; aggregate_elements, src/FEM/FEM.jl:84-116): the unique
     mesh edges sorted by (smaller point, larger point), DoF of edge e = npoints + e.  ``points``: the (npoints, 3) array or just
     npoints.  Returns (edges (nedges, 2), tets10 (ntets, 10), tris6 (ntris, 6)), 0-based, local node order = the points, then the
     edges (1,2), (1,3), (1,4), (2,3), (2,4), (3,4) resp. (1,2), (1,3), (2,3)."""
-    npoints = int(points) if np.ndim(points) == 0 else np.asarray(points).reshape(-1, 3).shape[0]
+    npoints = _npoints(points)
     _, tt, tr = _mesh_args(np.zeros((0, 3)), tets, tris)
     L = _lib.lib()
-    ip = C.POINTER(C.c_int32)
     h = C.c_void_p()
-    _lib.check(L.wae_p2_connectivity(int(device), npoints, tt.shape[0], tt.ctypes.data_as(ip), 0 if tr is None else tr.shape[0],
-                                     None if tr is None or not len(tr) else tr.ctypes.data_as(ip), C.byref(h)))
+    _lib.check(L.wae_p2_connectivity(int(device), npoints, *_counted(tt), *_counted(tr, True), C.byref(h)))
     try:
         ne, nt, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         _lib.check(L.wae_p2_connectivity_info(h, C.byref(ne), C.byref(nt), C.byref(ns)))
         edges = np.zeros((ne.value, 2), dtype=np.int32)
         t10 = np.zeros((nt.value, 10), dtype=np.int32)
         t6 = np.zeros((ns.value, 6), dtype=np.int32)
-        _lib.check(L.wae_p2_connectivity_get(h, edges.ctypes.data_as(ip), t10.ctypes.data_as(ip), t6.ctypes.data_as(ip)))
+        _lib.check(L.wae_p2_connectivity_get(h, _ptr(edges), _ptr(t10), _ptr(t6)))
     finally:
         L.wae_p2_connectivity_free(h)
     return edges, t10, t6
@@ -165,18 +173,17 @@ def p2_embedding(points, tets, device=0):
     npoints + 2 nedges entries, columns ascending), built by a kernel from the edge list of ``wae_p2_connectivity``
     (wae_p2_embedding): the coarse space of p-coarsening, a prolongator ``DeviceFamily.setup_solver(prolongators=...)`` takes.
     ``points``: the (npoints, 3) array or just npoints."""
-    npoints = int(points) if np.ndim(points) == 0 else np.asarray(points).reshape(-1, 3).shape[0]
+    npoints = _npoints(points)
     _, tt, _ = _mesh_args(np.zeros((0, 3)), tets)
     L = _lib.lib()
-    ip = C.POINTER(C.c_int32)
     h = C.c_void_p()
-    _lib.check(L.wae_p2_connectivity(int(device), npoints, tt.shape[0], tt.ctypes.data_as(ip), 0, None, C.byref(h)))
+    _lib.check(L.wae_p2_connectivity(int(device), npoints, *_counted(tt), 0, None, C.byref(h)))
     try:
         ne = C.c_int64(0)
         _lib.check(L.wae_p2_connectivity_info(h, C.byref(ne), None, None))
         n, nnz = npoints + ne.value, npoints + 2 * ne.value
         ptr, col, val = np.zeros(n + 1, dtype=np.int32), np.zeros(nnz, dtype=np.int32), np.zeros(nnz)
-        _lib.check(L.wae_p2_embedding(h, npoints, ptr.ctypes.data_as(ip), col.ctypes.data_as(ip), val.ctypes.data_as(C.POINTER(C.c_double))))
+        _lib.check(L.wae_p2_embedding(h, npoints, _ptr(ptr), _ptr(col), _ptr(val)))
     finally:
         L.wae_p2_connectivity_free(h)
     return sp.csr_matrix((val, col, ptr), shape=(n, npoints))
@@ -186,16 +193,9 @@ def assemble_p2(points, tets, c_tet=None, device=0, dtype=np.complex128, c_point
     """P2 mass and stiffness matrices on the device (wae_p2_assemble, wae_p2_assemble_cpoint; src/Helmholtz.jl:120-149,405-441 with
     order=:quad), arguments as ``assemble_p1``.  Returns (M, K) as scipy CSR matrices of size npoints + nedges sharing one pattern."""
     pts, tt, _ = _mesh_args(points, tets)
-    cp = _nodal(c_point, c_tet, pts.shape[0], "c_tet")
-    cc = cp if cp is not None else None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
-    assert cp is not None or cc is None or cc.shape == (tt.shape[0],)
-    L = _lib.lib()
-    h = C.c_void_p()
-    dp = C.POINTER(C.c_double)
-    entry = L.wae_p2_assemble if cp is None else L.wae_p2_assemble_cpoint
-    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
-                     None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
-    return _take_pair(L, h, dtype)
+    cc, nodal = _matrix_c(c_tet, c_point, pts.shape[0], "c_tet")
+    assert nodal or cc is None or cc.shape == (tt.shape[0],)
+    return _assembled("wae_p2_assemble_cpoint" if nodal else "wae_p2_assemble", [*_prefix(device, pts, tt), _ptr(cc)], dtype, pair=True)
 
 
 def assemble_p2_boundary(points, tets, tris, c_tri=None, device=0, c_point=None):
@@ -203,33 +203,16 @@ def assemble_p2_boundary(points, tets, tris, c_tri=None, device=0, c_point=None)
     C = -i·c·|e1×e2|·∫φ_aφ_b on the 6-node triangles; ``tets`` gives the edge numbers; with c_point (npoints,) instead of c_tri, c is
     linear on every triangle and under the integral (wae_p2_assemble_boundary_cpoint).  Returns C (complex CSR, npoints + nedges)."""
     pts, tt, tr = _mesh_args(points, tets, tris)
-    cp = _nodal(c_point, c_tri, pts.shape[0], "c_tri")
-    cc = cp if cp is not None else None if c_tri is None else np.ascontiguousarray(c_tri, dtype=np.float64)
-    assert cp is not None or cc is None or cc.shape == (tr.shape[0],)
-    L = _lib.lib()
-    h = C.c_void_p()
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    entry = L.wae_p2_assemble_boundary if cp is None else L.wae_p2_assemble_boundary_cpoint
-    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), tr.shape[0],
-                     tr.ctypes.data_as(ip), None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
-    return -1j * _take_csr(L, h, np.complex128)
+    cc, nodal = _matrix_c(c_tri, c_point, pts.shape[0], "c_tri")
+    assert nodal or cc is None or cc.shape == (tr.shape[0],)
+    return -1j * _assembled("wae_p2_assemble_boundary_cpoint" if nodal else "wae_p2_assemble_boundary", [*_prefix(device, pts, tt, *_counted(tr)), _ptr(cc)])
 
 
 def assemble_p2_flame(points, tets, flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled, device=0):
     """P2 flame operator Q = Σ_flame S ⊗ g on the device (wae_p2_assemble_flame; src/Helmholtz.jl:292-344,464-487): as
     ``assemble_p1_flame``, and ``x_ref``, the reference point inside ``ref_tet`` at which the gradients are taken.  Returns (Q, V_flame)."""
     pts, tt, _ = _mesh_args(points, tets)
-    fl = np.ascontiguousarray(flame_tets, dtype=np.int32)
-    xr = np.ascontiguousarray(x_ref, dtype=np.float64)
-    nr = np.ascontiguousarray(n_ref, dtype=np.float64)
-    assert xr.shape == (3,) and nr.shape == (3,)
-    L = _lib.lib()
-    h = C.c_void_p()
-    vol = C.c_double(0.0)
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    _lib.check(L.wae_p2_assemble_flame(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), len(fl), fl.ctypes.data_as(ip),
-                                       int(ref_tet), xr.ctypes.data_as(dp), nr.ctypes.data_as(dp), float(nglobal_scaled), C.byref(h), C.byref(vol)))
-    return _take_csr(L, h, np.complex128), vol.value
+    return _flame("wae_p2_assemble_flame", _prefix(device, pts, tt), flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled)
 
 
 # ---- Hermite (cubic) elements: `discretize(...; order=:herm)` -------------------------------------------------------------------
@@ -239,10 +222,12 @@ def _herm_no_nodal_c(c_point):
                                   "the nodal element matrices of order='herm' are missing; give c per simplex")
 
 
-def _tris_args(tr):
-    """(ntris, pointer or None) of an optional triangle list"""
-    ip = C.POINTER(C.c_int32)
-    return (0, None) if tr is None or not len(tr) else (tr.shape[0], tr.ctypes.data_as(ip))
+def _herm_c(c_simplex, count, what, where):
+    """the speed of sound per simplex of a Hermite matrix wrapper (None = 1), checked"""
+    cc, _ = _matrix_c(c_simplex, None, 0, what)
+    if cc is not None and cc.shape != (count,):
+        raise ValueError(f"{what} has shape {cc.shape}, the {where}")
+    return cc
 
 
 def herm_connectivity(points, tets, tris=None, device=0):
@@ -252,19 +237,18 @@ def herm_connectivity(points, tets, tris=None, device=0):
     (largest, middle, smallest point).  ``points``: the (npoints, 3) array or just npoints.  Returns (faces (ninner, 3) -- the faces
     that are not in ``tris``, each as (smallest, middle, largest) --, tets20 (ntets, 20), tris13 (ntris, 13), ndof), 0-based; local
     order: the 4 (3) values, the x, the y, the z derivatives, then the faces opposite point 1, 2, 3, 4 (the triangle's own face)."""
-    npoints = int(points) if np.ndim(points) == 0 else np.asarray(points).reshape(-1, 3).shape[0]
+    npoints = _npoints(points)
     _, tt, tr = _mesh_args(np.zeros((0, 3)), tets, tris)
     L = _lib.lib()
-    ip = C.POINTER(C.c_int32)
     h = C.c_void_p()
-    _lib.check(L.wae_herm_connectivity(int(device), npoints, tt.shape[0], tt.ctypes.data_as(ip), *_tris_args(tr), C.byref(h)))
+    _lib.check(L.wae_herm_connectivity(int(device), npoints, *_counted(tt), *_counted(tr, True), C.byref(h)))
     try:
         nf, nt, ns, nd = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
         _lib.check(L.wae_herm_connectivity_info(h, C.byref(nf), C.byref(nt), C.byref(ns), C.byref(nd)))
         faces = np.zeros((nf.value, 3), dtype=np.int32)
         t20 = np.zeros((nt.value, 20), dtype=np.int32)
         t13 = np.zeros((ns.value, 13), dtype=np.int32)
-        _lib.check(L.wae_herm_connectivity_get(h, faces.ctypes.data_as(ip), t20.ctypes.data_as(ip), t13.ctypes.data_as(ip)))
+        _lib.check(L.wae_herm_connectivity_get(h, _ptr(faces), _ptr(t20), _ptr(t13)))
     finally:
         L.wae_herm_connectivity_free(h)
     return faces, t20, t13, nd.value
@@ -273,7 +257,7 @@ def herm_connectivity(points, tets, tris=None, device=0):
 def herm_dof_count(points, tets, tris=None):
     """4 npoints + number of distinct tetrahedron faces = the dimension of the Hermite space (host side; the device numbers the faces
     itself).  ``points``: the array or just npoints; ``tris`` does not change the count (every listed triangle is a tetrahedron face)."""
-    npoints = int(points) if np.ndim(points) == 0 else np.asarray(points).reshape(-1, 3).shape[0]
+    npoints = _npoints(points)
     tt = np.asarray(tets, dtype=np.int64).reshape(-1, 4)
     f = np.sort(np.concatenate([tt[:, [b for b in range(4) if b != a]] for a in range(4)]), axis=1)
     return 4 * npoints + len(np.unique(f, axis=0))
@@ -298,15 +282,8 @@ def assemble_herm(points, tets, tris=None, c_tet=None, device=0, dtype=np.comple
     CSR matrices of size ndof sharing one pattern.  ``c_point`` raises NotImplementedError."""
     _herm_no_nodal_c(c_point)
     pts, tt, tr = _mesh_args(points, tets, tris)
-    cc = None if c_tet is None else np.ascontiguousarray(c_tet, dtype=np.float64)
-    if cc is not None and cc.shape != (tt.shape[0],):
-        raise ValueError(f"c_tet has shape {cc.shape}, the mesh has {tt.shape[0]} tetrahedra")
-    L = _lib.lib()
-    h = C.c_void_p()
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    _lib.check(L.wae_herm_assemble(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), *_tris_args(tr),
-                                   None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
-    return _take_pair(L, h, dtype)
+    cc = _herm_c(c_tet, tt.shape[0], "c_tet", f"mesh has {tt.shape[0]} tetrahedra")
+    return _assembled("wae_herm_assemble", [*_prefix(device, pts, tt, *_counted(tr, True)), _ptr(cc)], dtype, pair=True)
 
 
 def assemble_herm_boundary(points, tets, tris, c_tri=None, device=0, c_point=None):
@@ -314,33 +291,15 @@ def assemble_herm_boundary(points, tets, tris, c_tri=None, device=0, c_point=Non
     C = -i·c·|e1×e2|·∫φ_aφ_b on the 13-DoF triangles, the traces of the tetrahedron functions.  Returns C (complex CSR, ndof)."""
     _herm_no_nodal_c(c_point)
     pts, tt, tr = _mesh_args(points, tets, tris)
-    cc = None if c_tri is None else np.ascontiguousarray(c_tri, dtype=np.float64)
-    if cc is not None and cc.shape != (tr.shape[0],):
-        raise ValueError(f"c_tri has shape {cc.shape}, the boundary has {tr.shape[0]} triangles")
-    L = _lib.lib()
-    h = C.c_void_p()
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    _lib.check(L.wae_herm_assemble_boundary(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), tr.shape[0],
-                                            tr.ctypes.data_as(ip), None if cc is None else cc.ctypes.data_as(dp), C.byref(h)))
-    return -1j * _take_csr(L, h, np.complex128)
+    cc = _herm_c(c_tri, tr.shape[0], "c_tri", f"boundary has {tr.shape[0]} triangles")
+    return -1j * _assembled("wae_herm_assemble_boundary", [*_prefix(device, pts, tt, *_counted(tr)), _ptr(cc)])
 
 
 def assemble_herm_flame(points, tets, tris, flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled, device=0):
     """Hermite flame operator Q = Σ_flame S ⊗ g on the device (wae_herm_assemble_flame; src/Helmholtz.jl:292-344,464-487): as
     ``assemble_p2_flame``; ``tris`` (may be None) numbers the faces as in ``assemble_herm``.  Returns (Q, V_flame)."""
     pts, tt, tr = _mesh_args(points, tets, tris)
-    fl = np.ascontiguousarray(flame_tets, dtype=np.int32)
-    xr = np.ascontiguousarray(x_ref, dtype=np.float64)
-    nr = np.ascontiguousarray(n_ref, dtype=np.float64)
-    assert xr.shape == (3,) and nr.shape == (3,)
-    L = _lib.lib()
-    h = C.c_void_p()
-    vol = C.c_double(0.0)
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    _lib.check(L.wae_herm_assemble_flame(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), *_tris_args(tr), len(fl),
-                                         fl.ctypes.data_as(ip), int(ref_tet), xr.ctypes.data_as(dp), nr.ctypes.data_as(dp), float(nglobal_scaled),
-                                         C.byref(h), C.byref(vol)))
-    return _take_csr(L, h, np.complex128), vol.value
+    return _flame("wae_herm_assemble_flame", _prefix(device, pts, tt, *_counted(tr, True)), flame_tets, ref_tet, x_ref, n_ref, nglobal_scaled)
 
 
 # ---- speaker source vector: `discretize(...; source=true)` with a :speaker domain ---------------------------------------------
@@ -353,30 +312,22 @@ def _source_column(s):
 
 def _source_c(points, ntris, c_tri, c_point):
     """(values or None, nodal?) of the speed of sound of a source vector, checked"""
-    cp = _nodal(c_point, c_tri, points.shape[0], "c_tri")
-    if cp is not None:
-        return cp, True
-    if c_tri is None:
-        return None, False
-    cc = np.ascontiguousarray(c_tri, dtype=np.float64)
-    if cc.shape != (ntris,):
+    cc, nodal = _matrix_c(c_tri, c_point, points.shape[0], "c_tri")
+    if not nodal and cc is not None and cc.shape != (ntris,):
         raise ValueError(f"c_tri has shape {cc.shape}, the speaker domain has {ntris} triangles")
-    return cc, False
+    return cc, nodal
 
 
 def assemble_p1_source(points, tris, c_tri=None, device=0, c_point=None):
     """Source vector of a :speaker boundary on the device (wae_p1_assemble_source, wae_p1_assemble_source_cpoint; src/Helmholtz.jl:488-505):
     s_a = |e1×e2|·∫c φ_a over the speaker triangles, c per triangle (``c_tri``, None = 1) or per mesh point (``c_point``, linear on every
     triangle).  Returns the term m = -i·s of the ``rhs`` family as a complex npoints x 1 scipy sparse column."""
-    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    tt = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
-    cc, nodal = _source_c(pts, tt.shape[0], c_tri, c_point)
+    pts, _, tr = _mesh_args(points, tris=tris)
+    cc, nodal = _source_c(pts, tr.shape[0], c_tri, c_point)
     L = _lib.lib()
-    dp = C.POINTER(C.c_double)
     out = np.zeros(pts.shape[0], dtype=np.float64)
     entry = L.wae_p1_assemble_source_cpoint if nodal else L.wae_p1_assemble_source
-    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(C.POINTER(C.c_int32)),
-                     None if cc is None else cc.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+    _lib.check(entry(*_prefix(device, pts, tr), _ptr(cc), _ptr(out)))
     return _source_column(out)
 
 
@@ -385,13 +336,10 @@ def assemble_p2_source(points, tets, tris, c_tri=None, device=0, c_point=None):
     ``assemble_p1_source`` on the 6-node triangles; ``tets`` gives the edge numbers.  Returns m = -i·s, complex (npoints + nedges) x 1."""
     pts, tt, tr = _mesh_args(points, tets, tris)
     cc, nodal = _source_c(pts, tr.shape[0], c_tri, c_point)
-    nedges = len(np.unique(np.sort(np.concatenate([tt[:, [i, j]] for i in range(4) for j in range(i + 1, 4)]), axis=1), axis=0))
     L = _lib.lib()
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    out = np.zeros(pts.shape[0] + nedges, dtype=np.float64)
+    out = np.zeros(pts.shape[0] + p2_edge_count(tt), dtype=np.float64)
     entry = L.wae_p2_assemble_source_cpoint if nodal else L.wae_p2_assemble_source
-    _lib.check(entry(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), tr.shape[0], tr.ctypes.data_as(ip),
-                     None if cc is None else cc.ctypes.data_as(dp), out.ctypes.data_as(dp), len(out)))
+    _lib.check(entry(*_prefix(device, pts, tt, *_counted(tr)), _ptr(cc), _ptr(out), len(out)))
     return _source_column(out)
 
 
@@ -436,8 +384,7 @@ def discrete_adjoint_shape_sensitivity(points, tets, c_tet, surface_points, sol,
     corner points of the straight-sided elements move, and ``flame`` needs ``x_ref``).  ``c_point`` (npoints,): the speed of sound per
     mesh point, linear on every simplex, instead of ``c_tet`` and ``bnd_c`` (the *_cpoint entries; the values stay with their points).
     Returns a complex array (3, len(surface_points))."""
-    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    tt = np.ascontiguousarray(tets, dtype=np.int32).reshape(-1, 4)
+    pts, tt, _ = _mesh_args(points, tets)
     cp, dim = _shape_arguments(pts, tt, order, c_tet, c_point, bnd_c, flame,
                                [("v", v_ext[0]), ("v_adj", v_ext[1])] if v_ext is not None else [("sol.v", sol.v), ("sol.v_adj", sol.v_adj)])
     quad = order == "quad"
@@ -477,8 +424,7 @@ def discrete_adjoint_shape_sensitivity(points, tets, c_tet, surface_points, sol,
         pair_tri, pair_pt_s, own_s = js.astype(np.int32), tri[js, ja].astype(np.int32), loc_s[js, ja]
         npair_s = len(pair_tri)
         out_s = np.zeros((npair_s, 3), dtype=np.complex128)
-    dp = C.POINTER(C.c_double)
-    ip = C.POINTER(C.c_int32)
+    dp, ip = DP, I32P
     om = np.array([w0.real, w0.imag])
     wy = complex(w0 * (Y if Y is not None else 0.0))
     omy = np.array([wy.real, wy.imag])
@@ -539,7 +485,7 @@ def _flame_shape_part(pts, tt, sp_, lut, v, va, w0, L, flame, h, device, order="
     ssum = np.zeros(npair, dtype=np.complex128)
     g_pm = np.zeros((npr, 3, 2), dtype=np.complex128)
     g0 = np.zeros(1, dtype=np.complex128)
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    dp, ip = DP, I32P
 
     def P(a, t):
         return a.ctypes.data_as(t) if a.size else None
@@ -578,9 +524,8 @@ def herm_prolongators(points, tets, tris=None, device=0):
     ValueError, before the library is touched, for arrays that are not (npoints, 3) floats and (ntets, 4) / (ntris, 3) integers."""
     pts, tt, tr = _herm_mesh_checked(points, tets, tris)
     L = _lib.lib()
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     h = C.c_void_p()
-    _lib.check(L.wae_hermite_prolongators(int(device), pts.shape[0], pts.ctypes.data_as(dp), tt.shape[0], tt.ctypes.data_as(ip), *_tris_args(tr), C.byref(h)))
+    _lib.check(L.wae_hermite_prolongators(*_prefix(device, pts, tt, *_counted(tr, True)), C.byref(h)))
     out = []
     try:
         for which in (0, 1):
@@ -589,7 +534,7 @@ def herm_prolongators(points, tets, tris=None, device=0):
             ptr = np.zeros(rows.value + 1, dtype=np.int32)
             col = np.zeros(nnz.value, dtype=np.int32)
             val = np.zeros(nnz.value, dtype=np.float64)
-            _lib.check(L.wae_hermite_prolongators_get(h, which, ptr.ctypes.data_as(ip), col.ctypes.data_as(ip), val.ctypes.data_as(dp)))
+            _lib.check(L.wae_hermite_prolongators_get(h, which, _ptr(ptr), _ptr(col), _ptr(val)))
             out.append(sp.csr_matrix((val, col, ptr), shape=(rows.value, cols.value)))
     finally:
         L.wae_hermite_prolongators_free(h)
