@@ -494,7 +494,8 @@ int wae_herm_connectivity_free(void *handle);
  *    values, 0 on the gradients, 3|det J|/80 on the faces),  g_b = -nlocal grad(phi_b)(x_ref).n_ref on the 20 DoF of ref_tet,
  *    nlocal = nglobal_scaled / V_flame; arguments as wae_p2_assemble_flame.
  * Out of scope for Hermite elements: a nodal speed of sound, source vectors, shape sensitivity, Bloch numbering, prolongation across
- * octosplit levels, point location and sampling, the tile path.  The solver path of a Hermite family: wae_hermite_prolongators below. */
+ * octosplit levels, the tile path.  The solver path of a Hermite family: wae_hermite_prolongators below; sampling a Hermite vector at
+ * located points, and carrying it onto another mesh: wae_hermite_locator_set and order 3 of the locator entries below. */
 int wae_herm_assemble(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris, const int32_t *tris,
                       const double *c_tet, void **out);
 int wae_herm_assemble_boundary(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t ntris,
@@ -588,7 +589,7 @@ int wae_octosplit_p2_info(void *handle, int32_t level, int64_t *nedges, int64_t 
 int wae_octosplit_prolongator_p2(void *handle, int32_t from_level, int32_t *ptr, int32_t *col, double *val);
 int wae_octosplit_prolong_p2(void *handle, int32_t from_level, int32_t to_level, int32_t ncols, const double *X, double *Y);
 int wae_octosplit_free(void *handle);
-/* -- point location in a tetrahedral mesh and sampling of P1 / P2 vectors there, on the device --------------------------
+/* -- point location in a tetrahedral mesh and sampling of P1 / P2 / Hermite vectors there, on the device --------------------------
  * find_tetrahedron_containing_point (src/Meshutils.jl:800-815) and get_p / get_n_grad_p (src/FEM/helmholtz_getters.jl:7-45) for many
  * points at once.  wae_locator_create keeps the mesh (points: 3 doubles per point, tets: 4 point indices per tetrahedron, 0-based) and a
  * uniform cell grid over it in HBM; every pointer of these entries is a host pointer.
@@ -609,22 +610,33 @@ int wae_octosplit_free(void *handle);
  * wae_locator_info: the sizes, dims[3], nrefs = the (cell, tet) pairs, max_per_cell = the longest list; any pointer may be NULL.
  * wae_locator_set_p2: the P2 unknowns of every tetrahedron (tets10: 10 per tetrahedron as wae_p2_connectivity_get gives them: the 4
  * points, then the edges (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)), ndof = npoints + nedges; needed before any call with order 2.
- * wae_locator_weights: the rows of the point functionals, idx / val with 4 (order 1) or 10 (order 2) entries per point: kind 0, p(x) =
- * sum val v[idx]: l_i on the points (order 1), l_i (2 l_i - 1) on the points and 4 l_i l_j on the edges (order 2); kind 1, n . grad p(x):
+ * wae_hermite_locator_set: the Hermite unknowns of every tetrahedron (tets20: 20 per tetrahedron as wae_herm_connectivity_get gives
+ * them for the boundary triangles the family was assembled with: b * npoints + point k at 4 b + k, b = 0 the value, b = 1..3 the x, y, z
+ * derivative, then 4 npoints + the number of the face opposite point k), ndof = 4 npoints + nfaces; needed before any call with order 3 (until
+ * then order 3 is refused like any unknown order, "order must be 1 or 2").  A
+ * second call replaces the table; a refused one keeps nothing and leaves the table of an earlier call untouched.
+ * wae_locator_weights: the rows of the point functionals, idx / val with 4 (order 1), 10 (order 2) or 20 (order 3) entries per point:
+ * kind 0, p(x) = sum val v[idx]: l_i on the points (order 1), l_i (2 l_i - 1) on the points and 4 l_i l_j on the edges (order 2), the
+ * functions of the assembled Hermite space in the order of tets20 (order 3: with xi = (l_1, l_2, l_3) the reference functions psi_a(xi), the
+ * twelve of the vertex gradients recombined with J = [p1-p4, p2-p4, p3-p4] as w[4 (1 + i) + k] = sum_j J[i][j] psi[4 (1 + j) + k], since the
+ * unknowns are physical gradients); kind 1, n . grad p(x):
  * the derivative of those weights along n (3 per point).  tet: the tetrahedron of every point (from wae_locator_find); a row with tet ==
  * -1 has idx 0 and val 0.
  * wae_locator_sample: out[q, c] = sum_i val[q, i] V[idx[q, i], c] in one gather kernel, i ascending, without the weights leaving the
- * device.  V: d x ncols complex column-major (interleaved re/im), d = npoints (order 1) or ndof (order 2); out: nq x ncols complex
+ * device.  V: d x ncols complex column-major (interleaved re/im), d = npoints (order 1) or the ndof of the table (orders 2 and 3); out: nq x ncols complex
  * column-major; a row with tet == -1 is NaN.
  * WAE_ERR_INVALID, nothing launched: a negative count, a tetrahedron index outside 0..npoints-1, a point or query coordinate that is
- * not finite, tol outside [0, 1e-6], a tet outside -1..ntets-1, order 2 before wae_locator_set_p2, d different from npoints / ndof, an
- * entry of tets10 outside 0..ndof-1, kind 1 with n == NULL, npoints or 32 ntets beyond a 32-bit index.  nq == 0 returns WAE_OK and
- * touches nothing.  Out of scope: Hermite elements, nearest-tetrahedron answers outside the mesh, curved geometry, Bloch-expanded fields. */
+ * not finite, tol outside [0, 1e-6], a tet outside -1..ntets-1, order 2 before wae_locator_set_p2, order 3 before
+ * wae_hermite_locator_set, d different from npoints / ndof, an entry of tets10 outside 0..ndof-1, tets20 == NULL, its ndof below 4 npoints
+ * or beyond a 32-bit index, an entry 4 b + k of tets20 that is not b npoints + point k of the tetrahedron, an entry 16..19 outside 4 npoints
+ * .. ndof-1, kind 1 with n == NULL, npoints or 32 ntets beyond a 32-bit index.  nq == 0 returns WAE_OK and
+ * touches nothing.  Out of scope: Hermite source vectors, nearest-tetrahedron answers outside the mesh, curved geometry, Bloch-expanded fields. */
 int wae_locator_create(int32_t device, int64_t npoints, const double *points, int64_t ntets, const int32_t *tets, int64_t cell_target,
                        void **out);
 int wae_locator_info(const void *handle, int64_t *npoints, int64_t *ntets, int64_t *dims, int64_t *nrefs, int64_t *max_per_cell);
 int wae_locator_find(const void *handle, int64_t nq, const double *x, double tol, int32_t *tet, double *lambda);
 int wae_locator_set_p2(void *handle, int64_t ndof, const int32_t *tets10);
+int wae_hermite_locator_set(void *locator, int64_t ndof, const int32_t *tets20);
 int wae_locator_weights(const void *handle, int32_t order, int32_t kind, int64_t nq, const double *x, const int32_t *tet, const double *n,
                         int32_t *idx, double *val);
 int wae_locator_sample(const void *handle, int32_t order, int32_t kind, int64_t nq, const double *x, const int32_t *tet, const double *n,

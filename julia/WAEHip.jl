@@ -1532,6 +1532,7 @@ mutable struct PointLocator
     tets::Matrix{Int32}
     ndof::Int                      # of the P2 space, 0 until an order=:quad call
     device::Int
+    ndof_herm::Int                 # of the Hermite space, 0 until locator_set_herm!
 end
 
 "release the device arrays of a PointLocator (the finalizer is only the safety net).  Idempotent."
@@ -1548,7 +1549,7 @@ function locator(mesh; cell_target::Integer=0, device::Integer=0)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:wae_locator_create, libwaehip), Cint, (Int32, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Int64, Ref{Ptr{Cvoid}}),
                 device, size(points, 2), points, size(t0, 2), t0, cell_target, h))
-    loc = PointLocator(h[], size(points, 2), size(t0, 2), (0, 0, 0), 0, 0, t0, 0, Int(device))
+    loc = PointLocator(h[], size(points, 2), size(t0, 2), (0, 0, 0), 0, 0, t0, 0, Int(device), 0)
     finalizer(free!, loc)                      # attached before anything else can throw, so the handle cannot leak
     np = Ref{Int64}(0); nt = Ref{Int64}(0); nr = Ref{Int64}(0); mx = Ref{Int64}(0); dims = zeros(Int64, 3)
     check(ccall((:wae_locator_info, libwaehip), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ref{Int64}, Ref{Int64}), h[], np, nt, dims, nr, mx))
@@ -1578,10 +1579,33 @@ function _locator_p2!(loc::PointLocator)
     return
 end
 
-function _locator_sample(loc::PointLocator, V::AbstractVecOrMat{<:Number}, X::Matrix{Float64}, n, order::Symbol)
-    order in (:lin, :quad) || throw(ArgumentError("order must be :lin or :quad, got $order"))
-    size(X, 1) == 3 || throw(ArgumentError("X must be 3 x nq"))
+"locator_set_herm!(loc, tets20): the Hermite unknowns of every tetrahedron (20 x ntets, 1-based, as `herm_connectivity` returns them for
+the boundary triangles the family was assembled with) on the handle; needed before the first order=:herm call, a second table replaces
+the first"
+function locator_set_herm!(loc::PointLocator, tets20::AbstractMatrix{<:Integer})
+    size(tets20) == (20, loc.ntets) || throw(ArgumentError("tets20 must be 20 x $(loc.ntets), got $(size(tets20))"))
+    # herm_connectivity returns 1-based unknowns, wae_hermite_locator_set wants 0-based ones
+    t20_0 = Matrix{Int32}(tets20) .- Int32(1)
+    ndof = Int(maximum(tets20))
+    check(ccall((:wae_hermite_locator_set, libwaehip), Cint, (Ptr{Cvoid}, Int64, Ptr{Int32}), loc.handle, ndof, t20_0))
+    loc.ndof_herm = ndof
+    return loc
+end
+
+"the order code of the library; order=:herm sets the caller's table first (or needs an earlier locator_set_herm!)"
+function _locator_order!(loc::PointLocator, order::Symbol, tets20)
+    order in (:lin, :quad, :herm) || throw(ArgumentError("order must be :lin, :quad or :herm, got $order"))
     order == :quad && _locator_p2!(loc)
+    if order == :herm
+        tets20 === nothing || locator_set_herm!(loc, tets20)
+        loc.ndof_herm > 0 || throw(ArgumentError("order=:herm needs tets20, the second result of herm_connectivity"))
+    end
+    return order == :lin ? 1 : (order == :quad ? 2 : 3)
+end
+
+function _locator_sample(loc::PointLocator, V::AbstractVecOrMat{<:Number}, X::Matrix{Float64}, n, order::Symbol, tets20=nothing)
+    size(X, 1) == 3 || throw(ArgumentError("X must be 3 x nq"))
+    code = _locator_order!(loc, order, tets20)
     nq = size(X, 2)
     tet = fill(Int32(-1), nq)
     check(ccall((:wae_locator_find, libwaehip), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Float64, Ptr{Int32}, Ptr{Float64}),
@@ -1590,35 +1614,37 @@ function _locator_sample(loc::PointLocator, V::AbstractVecOrMat{<:Number}, X::Ma
     out = zeros(ComplexF64, nq, size(Vc, 2))
     check(ccall((:wae_locator_sample, libwaehip), Cint,
                 (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Int64, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}),
-                loc.handle, order == :lin ? 1 : 2, n === nothing ? 0 : 1, nq, X, tet, n === nothing ? C_NULL : n, size(Vc, 1), size(Vc, 2), Vc, out))
+                loc.handle, code, n === nothing ? 0 : 1, nq, X, tet, n === nothing ? C_NULL : n, size(Vc, 1), size(Vc, 2), Vc, out))
     return V isa AbstractVector ? out[:, 1] : out
 end
 
-"get_p(loc, V, X; order=:lin): the pressure of every column of V at every column of X (NaN where the point lies in no tetrahedron)"
-get_p(loc::PointLocator, V::AbstractVecOrMat{<:Number}, X::Matrix{Float64}; order::Symbol=:lin) = _locator_sample(loc, V, X, nothing, order)
+"get_p(loc, V, X; order=:lin, tets20=nothing): the pressure of every column of V at every column of X (NaN where the point lies in no
+tetrahedron); order=:herm takes the Hermite vector of `discretize(...; order=:herm)` and, on its first call, tets20 (locator_set_herm!)"
+get_p(loc::PointLocator, V::AbstractVecOrMat{<:Number}, X::Matrix{Float64}; order::Symbol=:lin, tets20=nothing) =
+    _locator_sample(loc, V, X, nothing, order, tets20)
 
-"get_n_grad_p(loc, V, X, n; order=:lin): n . grad p there; n is one direction (3) or one per point (3 x nq)"
-function get_n_grad_p(loc::PointLocator, V::AbstractVecOrMat{<:Number}, X::Matrix{Float64}, n::AbstractVecOrMat{<:Real}; order::Symbol=:lin)
+"get_n_grad_p(loc, V, X, n; order=:lin, tets20=nothing): n . grad p there; n is one direction (3) or one per point (3 x nq)"
+function get_n_grad_p(loc::PointLocator, V::AbstractVecOrMat{<:Number}, X::Matrix{Float64}, n::AbstractVecOrMat{<:Real}; order::Symbol=:lin,
+                      tets20=nothing)
     N = n isa AbstractVector ? repeat(Float64.(n), 1, size(X, 2)) : Matrix{Float64}(n)
     size(N) == size(X) || throw(ArgumentError("n must have 3 entries or the shape of X"))
-    return _locator_sample(loc, V, X, N, order)
+    return _locator_sample(loc, V, X, N, order, tets20)
 end
 
 "idx, val = locator_weights(loc, X, tet; order=:lin, n=nothing): the rows of the point functionals (wae_locator_weights), 1-based unknowns,
-4 (:lin) or 10 (:quad) per point; tet as find_tetrahedra returns it"
-function locator_weights(loc::PointLocator, X::Matrix{Float64}, tet::AbstractVector{<:Integer}; order::Symbol=:lin, n=nothing)
-    order in (:lin, :quad) || throw(ArgumentError("order must be :lin or :quad, got $order"))
+4 (:lin), 10 (:quad) or 20 (:herm, tets20 as in get_p) per point; tet as find_tetrahedra returns it"
+function locator_weights(loc::PointLocator, X::Matrix{Float64}, tet::AbstractVector{<:Integer}; order::Symbol=:lin, n=nothing, tets20=nothing)
     size(X, 1) == 3 || throw(ArgumentError("X must be 3 x nq"))
-    nq = size(X, 2); nw = order == :lin ? 4 : 10
+    code = _locator_order!(loc, order, tets20)
+    nq = size(X, 2); nw = (4, 10, 20)[code]
     length(tet) == nq || throw(ArgumentError("tet must have one entry per column of X ($nq), got $(length(tet))"))
     N = n === nothing ? nothing : Matrix{Float64}(n)
     N === nothing || size(N) == size(X) || throw(ArgumentError("n must have the shape of X"))
-    order == :quad && _locator_p2!(loc)
     t0 = Int32.(tet) .- Int32(1)
     idx = zeros(Int32, nw, nq); val = zeros(Float64, nw, nq)
     check(ccall((:wae_locator_weights, libwaehip), Cint,
                 (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
-                loc.handle, order == :lin ? 1 : 2, N === nothing ? 0 : 1, nq, X, t0, N === nothing ? C_NULL : N, idx, val))
+                loc.handle, code, N === nothing ? 0 : 1, nq, X, t0, N === nothing ? C_NULL : N, idx, val))
     return Int.(idx) .+ 1, val
 end
 

@@ -52,7 +52,7 @@ EXPORTS = [
     "wae_herm_connectivity", "wae_herm_connectivity_info", "wae_herm_connectivity_get", "wae_herm_connectivity_free", "wae_herm_assemble",
     "wae_herm_assemble_boundary", "wae_herm_assemble_flame",
     "wae_hermite_prolongators", "wae_hermite_prolongators_info", "wae_hermite_prolongators_get", "wae_hermite_prolongators_free",
-    "wae_solver_level_weights",
+    "wae_solver_level_weights", "wae_hermite_locator_set",
 ]
 BLOCH_IMAGE, BLOCH_AXIS = 1, 2      # WAE_BLOCH_* flag bits
 TALL_MAXCOLS = 64           # WAE_TALL_MAXCOLS
@@ -183,6 +183,7 @@ def lib():
     L.wae_locator_weights.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, i32p, dp, i32p, dp]
     L.wae_locator_sample.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, dp, i32p, dp, C.c_int64, C.c_int32, dp, dp]
     L.wae_locator_free.argtypes = [C.c_void_p]
+    L.wae_hermite_locator_set.argtypes = [C.c_void_p, C.c_int64, i32p]
     L.wae_herm_connectivity.argtypes = [C.c_int32, C.c_int64, C.c_int64, i32p, C.c_int64, i32p, C.POINTER(C.c_void_p)]
     L.wae_herm_connectivity_info.argtypes = [C.c_void_p, i64p, i64p, i64p, i64p]
     L.wae_herm_connectivity_get.argtypes = [C.c_void_p, i32p, i32p, i32p]

@@ -1,6 +1,6 @@
-// Point location in a tetrahedral mesh and sampling of P1 / P2 vectors at the located points, on the device: the counterpart of
+// Point location in a tetrahedral mesh and sampling of P1 / P2 / Hermite vectors at the located points, on the device: the counterpart of
 // find_tetrahedron_containing_point (src/Meshutils.jl:800-815) and of get_p / get_n_grad_p (src/FEM/helmholtz_getters.jl:7-45) for many
-// points at once.  One handle keeps the mesh, a uniform cell grid over it and (once set) the P2 connectivity in HBM.
+// points at once.  One handle keeps the mesh, a uniform cell grid over it and (once set) the P2 and the Hermite connectivity in HBM.
 //
 // Containment.  The barycentric coordinates of x in the tetrahedron (p1, p2, p3, p4) by Cramer's rule on J = [a b c] = [p1-p4, p2-p4, p3-p4],
 // r = x - p4 (loc_bary; every operation rounded on its own, contract(off), so that a float64 host restatement gets the same bits):
@@ -25,9 +25,17 @@
 // average), the points outside the box leave at once, and a million points fill the device without any sharing of a point among lanes;
 // the lanes of a wavefront that fall into the same cell read the same candidates (one fetch).  A wavefront per point with a ballot over 64
 // candidates would test the whole list every time and idle most lanes on lists shorter than 64.
+//
+// Hermite rows (order 3).  The 20 weights of a point in the local order of tets20 (assemble_herm.hip): with x = p4 + J xi the
+// coordinates l1..l3 of loc_bary ARE xi, and g1..g3 = n . grad xi.  The reference functions psi_a = sum_m kHermCoef[a][m] xi^kHermExp[m]
+// (herm_tables.h) are evaluated from the twenty monomials (kind 1: from their derivatives along n, sum_j g_j d/dxi_j) held in registers;
+// the functions of the physical gradients at p_k are recombined as in the assembly, w[4 (1 + i) + k] = sum_j J[i][j] psi_{4 (1 + j) + k}.
+// All loops are unrolled, so the exponents and the (integer) coefficients are compile-time operands and the zero coefficients cost nothing.
 #include <climits>
 #include <memory>
+#include <vector>
 
+#include "herm_tables.h"
 #include "mesh_host.h"
 
 namespace {
@@ -54,9 +62,9 @@ __device__ inline double loc_dot(double u0, double u1, double u2, double w0, dou
     return (u0 * w0 + u1 * w1) + u2 * w2;
 }
 
-// the coordinates l[4] of x in tetrahedron t; n != null: also g[i] = n . grad l_i
+// the coordinates l[4] of x in tetrahedron t; n != null: also g[i] = n . grad l_i; J != null: also J[3 i + j] = (p_{j+1} - p4)_i
 __device__ inline void loc_bary(const double *__restrict__ pts, const int *__restrict__ tets, int64_t t, const double *x, const double *n, double *l,
-                                double *g) {
+                                double *g, double *J = nullptr) {
 #pragma clang fp contract(off)
     const int *v = tets + t * 4;
     const double *p1 = pts + (size_t)v[0] * 3, *p2 = pts + (size_t)v[1] * 3, *p3 = pts + (size_t)v[2] * 3, *p4 = pts + (size_t)v[3] * 3;
@@ -80,6 +88,11 @@ __device__ inline void loc_bary(const double *__restrict__ pts, const int *__res
         g[2] = loc_dot(n[0], n[1], n[2], ab0, ab1, ab2) / det;
         g[3] = -((g[0] + g[1]) + g[2]);
     }
+    if (J) {
+        J[0] = a0; J[1] = b0; J[2] = c0;
+        J[3] = a1; J[4] = b1; J[5] = c1;
+        J[6] = a2; J[7] = b2; J[8] = c2;
+    }
 }
 
 // the row of the probe functional: NW = 4 (P1) or 10 (P2) weights from l (and g for kind 1), in the order of probe_p / probe_n_grad_p
@@ -97,6 +110,58 @@ template <int NW> __device__ inline void loc_row(int kind, const double *l, cons
             const int i = EI[e], j = EJ[e];
             w[4 + e] = kind ? 4.0 * (l[j] * g[i] + l[i] * g[j]) : (4.0 * l[i]) * l[j];
         }
+    }
+}
+
+// psi_a from the monomials (or their directional derivatives): the terms in the order of m, the zero coefficients left out
+__device__ inline double loc_herm_psi(int a, const double *mono) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+#pragma unroll
+    for (int m = 0; m < 20; ++m)
+        if (kHermCoef[a][m] != 0.0) acc = acc + kHermCoef[a][m] * mono[m];
+    return acc;
+}
+
+// the Hermite row: 20 weights from xi = l[0..2] (kind 1: and g[0..2] = n . grad xi) and J, in the local order of tets20
+__device__ inline void loc_row_herm(int kind, const double *l, const double *g, const double *J, double *w) {
+#pragma clang fp contract(off)
+    double pw[3][4], mono[20];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        pw[j][0] = 1.0;
+        pw[j][1] = l[j];
+        pw[j][2] = l[j] * l[j];
+        pw[j][3] = pw[j][2] * l[j];
+    }
+    if (!kind) {
+#pragma unroll
+        for (int m = 0; m < 20; ++m) mono[m] = (pw[0][kHermExp[m][0]] * pw[1][kHermExp[m][1]]) * pw[2][kHermExp[m][2]];
+    } else {
+#pragma unroll
+        for (int m = 0; m < 20; ++m) {                               // sum_j g_j d(xi^e)/dxi_j, j ascending
+            double d = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                if (kHermExp[m][j] == 0) continue;
+                double term = (double)kHermExp[m][j];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) term = term * pw[i][i == j ? kHermExp[m][i] - 1 : kHermExp[m][i]];
+                d = d + g[j] * term;
+            }
+            mono[m] = d;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        w[k] = loc_herm_psi(k, mono);
+        w[16 + k] = loc_herm_psi(16 + k, mono);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                                    // one vertex at a time: three reference functions live, not twelve
+        const double p0 = loc_herm_psi(4 + k, mono), p1 = loc_herm_psi(8 + k, mono), p2 = loc_herm_psi(12 + k, mono);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) w[4 * (1 + i) + k] = loc_dot(J[3 * i], J[3 * i + 1], J[3 * i + 2], p0, p1, p2);
     }
 }
 
@@ -233,7 +298,7 @@ __global__ __launch_bounds__(256) void loc_find_kernel(LocGrid G, const double *
     }
 }
 
-// the row of point q: NW weights and the unknowns they act on (nodes: tets for P1, tets10 for P2); false for tet[q] == -1
+// the row of point q: NW weights and the unknowns they act on (nodes: tets for P1, tets10 for P2, tets20 for Hermite); false for tet[q] == -1
 template <int NW>
 __device__ inline bool loc_point_row(const double *__restrict__ pts, const int *__restrict__ tets, const int *__restrict__ nodes, int kind, int64_t q,
                                      const double *__restrict__ xq, const int *__restrict__ tet, const double *__restrict__ nq3, int *idx, double *w) {
@@ -242,8 +307,14 @@ __device__ inline bool loc_point_row(const double *__restrict__ pts, const int *
     const double x[3] = {xq[q * 3], xq[q * 3 + 1], xq[q * 3 + 2]};
     double n[3] = {0.0, 0.0, 0.0}, l[4], g[4] = {0.0, 0.0, 0.0, 0.0};
     if (kind) { n[0] = nq3[q * 3]; n[1] = nq3[q * 3 + 1]; n[2] = nq3[q * 3 + 2]; }
-    loc_bary(pts, tets, t, x, kind ? n : nullptr, l, g);
-    loc_row<NW>(kind, l, g, w);
+    if constexpr (NW == 20) {
+        double J[9];
+        loc_bary(pts, tets, t, x, kind ? n : nullptr, l, g, J);
+        loc_row_herm(kind, l, g, J, w);
+    } else {
+        loc_bary(pts, tets, t, x, kind ? n : nullptr, l, g);
+        loc_row<NW>(kind, l, g, w);
+    }
 #pragma unroll
     for (int i = 0; i < NW; ++i) idx[i] = nodes[(size_t)t * NW + i];
     return true;
@@ -298,10 +369,10 @@ __global__ __launch_bounds__(256) void loc_sample_kernel(const double *__restric
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 struct Locator {
     int device = 0;
-    int64_t np = 0, nt = 0, ndof = 0, nrefs = 0, maxlen = 0;
+    int64_t np = 0, nt = 0, ndof = 0, ndof20 = 0, nrefs = 0, maxlen = 0;
     LocGrid G;
     DevBuf<double> pts;
-    DevBuf<int> tets, tets10, cell_ptr, cell_tet;
+    DevBuf<int> tets, tets10, tets20, cell_ptr, cell_tet;
 };
 
 // about `want` cells over the box, as cubical as it allows: the axes with an extent share the cells, the others have one
@@ -399,9 +470,10 @@ void loc_check_finite(const double *x, int64_t count, const char *what) {
         if (!std::isfinite(x[i])) throw WaeError(WAE_ERR_INVALID, std::string(what) + " holds a coordinate that is not finite");
 }
 
-// the checks shared by wae_locator_weights and wae_locator_sample; returns the node table (tets or tets10)
+// the checks shared by wae_locator_weights and wae_locator_sample; returns the node table (tets, tets10 or tets20)
 const int *loc_check_rows(const Locator &H, int32_t order, int32_t kind, int64_t nq, const double *x, const int32_t *tet, const double *n) {
-    if (order != 1 && order != 2) throw WaeError(WAE_ERR_INVALID, "order must be 1 or 2");
+    // order 3 exists on a handle once its table is set; before that it is refused like any unknown order, with the words of that refusal
+    if (order != 1 && order != 2 && !(order == 3 && H.tets20.p)) throw WaeError(WAE_ERR_INVALID, "order must be 1 or 2");
     if (kind != 0 && kind != 1) throw WaeError(WAE_ERR_INVALID, "kind must be 0 (p) or 1 (n.grad p)");
     if (order == 2 && !H.tets10.p) throw WaeError(WAE_ERR_INVALID, "order 2 needs wae_locator_set_p2 first");
     if (kind == 1 && !n) throw WaeError(WAE_ERR_INVALID, "kind 1 needs the directions n");
@@ -409,7 +481,7 @@ const int *loc_check_rows(const Locator &H, int32_t order, int32_t kind, int64_t
     loc_check_finite(x, nq * 3, "x");
     for (int64_t q = 0; q < nq; ++q)
         if (tet[q] < -1 || tet[q] >= H.nt) throw WaeError(WAE_ERR_INVALID, "tet holds an index outside -1..ntets-1");
-    return order == 1 ? H.tets.p : H.tets10.p;
+    return order == 1 ? H.tets.p : (order == 2 ? H.tets10.p : H.tets20.p);
 }
 
 struct LocQuery {                       // the per-point inputs of a weights / sample call in HBM
@@ -496,6 +568,31 @@ int wae_locator_set_p2(void *h, int64_t ndof, const int32_t *tets10) {
     });
 }
 
+int wae_hermite_locator_set(void *h, int64_t ndof, const int32_t *tets20) {
+    return wae_guarded([&]() {
+        Locator &H = const_cast<Locator &>(loc_handle(h));
+        if (!tets20) throw WaeError(WAE_ERR_INVALID, "tets20 is null");
+        if (ndof < 4 * H.np || ndof > INT_MAX) throw WaeError(WAE_ERR_INVALID, "ndof must be at least 4*npoints and fit a 32-bit index");
+        HIP_CHECK(hipSetDevice(H.device));
+        std::vector<int> tets((size_t)H.nt * 4);
+        H.tets.to_host(tets.data(), tets.size());
+        for (int64_t t = 0; t < H.nt; ++t) {
+            const int32_t *r = tets20 + t * 20;
+            for (int b = 0; b < 4; ++b)
+                for (int k = 0; k < 4; ++k)
+                    if ((int64_t)r[4 * b + k] != b * H.np + tets[(size_t)t * 4 + k])
+                        throw WaeError(WAE_ERR_INVALID, "tets20: entry 4 b + k of a tetrahedron is not b * npoints + its point k");
+            for (int k = 16; k < 20; ++k)
+                if (r[k] < 4 * H.np || r[k] >= ndof) throw WaeError(WAE_ERR_INVALID, "tets20 holds a face unknown outside 4*npoints..ndof-1");
+        }
+        DevBuf<int> t20;
+        t20.from_host(tets20, (size_t)H.nt * 20);
+        H.tets20 = std::move(t20);
+        H.ndof20 = ndof;
+        return WAE_OK;
+    });
+}
+
 int wae_locator_weights(const void *h, int32_t order, int32_t kind, int64_t nq, const double *x, const int32_t *tet, const double *n, int32_t *idx,
                         double *val) {
     return wae_guarded([&]() {
@@ -505,7 +602,7 @@ int wae_locator_weights(const void *h, int32_t order, int32_t kind, int64_t nq, 
         const int *nodes = loc_check_rows(H, order, kind, nq, x, tet, n);
         if (!(idx && val)) throw WaeError(WAE_ERR_INVALID, "bad argument");
         HIP_CHECK(hipSetDevice(H.device));
-        const int nw = order == 1 ? 4 : 10;
+        const int nw = order == 1 ? 4 : (order == 2 ? 10 : 20);
         LocQuery Q(nq, x, tet, kind ? n : nullptr);
         DevBuf<int> di;
         DevBuf<double> dv;
@@ -513,8 +610,10 @@ int wae_locator_weights(const void *h, int32_t order, int32_t kind, int64_t nq, 
         dv.alloc((size_t)nq * nw);
         if (order == 1)
             hipLaunchKernelGGL(loc_weights_kernel<4>, grid_for(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, di.p, dv.p);
-        else
+        else if (order == 2)
             hipLaunchKernelGGL(loc_weights_kernel<10>, grid_for(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, di.p, dv.p);
+        else
+            hipLaunchKernelGGL(loc_weights_kernel<20>, grid_for(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, di.p, dv.p);
         HIP_CHECK(hipGetLastError());
         di.to_host(idx, (size_t)nq * nw);
         dv.to_host(val, (size_t)nq * nw);
@@ -529,7 +628,8 @@ int wae_locator_sample(const void *h, int32_t order, int32_t kind, int64_t nq, c
         if (nq < 0 || d < 0 || ncols < 0) throw WaeError(WAE_ERR_INVALID, "a count is negative");
         if (nq == 0) return WAE_OK;
         const int *nodes = loc_check_rows(H, order, kind, nq, x, tet, n);
-        if (d != (order == 1 ? H.np : H.ndof)) throw WaeError(WAE_ERR_INVALID, "d must be npoints (order 1) or ndof (order 2)");
+        if (order != 3 && d != (order == 1 ? H.np : H.ndof)) throw WaeError(WAE_ERR_INVALID, "d must be npoints (order 1) or ndof (order 2)");
+        if (order == 3 && d != H.ndof20) throw WaeError(WAE_ERR_INVALID, "d must be the ndof given to wae_hermite_locator_set (order 3)");
         if (!(V && out) || ncols < 1) throw WaeError(WAE_ERR_INVALID, "bad argument");
         HIP_CHECK(hipSetDevice(H.device));
         LocQuery Q(nq, x, tet, kind ? n : nullptr);
@@ -539,8 +639,11 @@ int wae_locator_sample(const void *h, int32_t order, int32_t kind, int64_t nq, c
         if (order == 1)
             hipLaunchKernelGGL(loc_sample_kernel<4>, grid_for(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, d,
                                (int)ncols, dV.p, dO.p);
-        else
+        else if (order == 2)
             hipLaunchKernelGGL(loc_sample_kernel<10>, grid_for(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, d,
+                               (int)ncols, dV.p, dO.p);
+        else
+            hipLaunchKernelGGL(loc_sample_kernel<20>, grid_for(nq), dim3(256), 0, 0, H.pts.p, H.tets.p, nodes, (int)kind, nq, Q.x.p, Q.tet.p, Q.n.p, d,
                                (int)ncols, dV.p, dO.p);
         HIP_CHECK(hipGetLastError());
         dO.to_host((cplx *)out, (size_t)nq * (size_t)ncols);

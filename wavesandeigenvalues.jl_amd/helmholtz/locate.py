@@ -8,7 +8,12 @@ barycentric coordinates are all >= -tol (-1: none); ``weights`` the rows (idx, v
 the columns of V in one gather kernel, ``observers`` hands them to ``nlevp.forced_response``, ``interpolation`` returns them as a CSR
 matrix in the format of ``RefinedMesh.prolongator`` (the transfer onto a mesh that is no refinement of this one).
 
-Out of scope: Hermite elements, nearest-tetrahedron answers for points outside the mesh, curved geometry, Bloch-expanded fields."""
+Orders: "lin" (P1), "quad" (P2, the edges numbered by ``p2_connectivity``) and "herm" (the cubic Hermite space of ``assemble_herm``).  The
+Hermite numbering depends on the boundary triangles the family was assembled with, so the locator never numbers faces itself: the first
+"herm" call takes ``tets20``, the second result of ``assemble.herm_connectivity``; later calls reuse it, another table replaces it.
+``herm_transfer`` carries a Hermite vector onto another mesh (values, gradients and face-centroid values there).
+
+Out of scope: Hermite source vectors, nearest-tetrahedron answers for points outside the mesh, curved geometry, Bloch-expanded fields."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,7 +24,8 @@ import scipy.sparse as sp
 from .. import _lib
 
 TOL_MAX = 1e-6
-_ORDERS = {"lin": 1, "quad": 2}
+_ORDERS = {"lin": 1, "quad": 2, "herm": 3}
+_NW = {"lin": 4, "quad": 10, "herm": 20}
 _KINDS = {"p": 0, "n_grad_p": 1}
 _dp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 
@@ -79,7 +85,7 @@ class Locator:
     def _row_args(X, order, kind, n, tet, outside):
         X = _queries(X)
         if order not in _ORDERS:
-            raise ValueError(f"order must be 'lin' or 'quad', got {order!r}")
+            raise ValueError(f"order must be 'lin', 'quad' or 'herm', got {order!r}")
         if kind not in _KINDS:
             raise ValueError(f"kind must be 'p' or 'n_grad_p', got {kind!r}")
         if outside not in ("raise", "nan"):
@@ -119,6 +125,30 @@ class Locator:
         _lib.check(_lib.lib().wae_locator_set_p2(self._handle(), ndof, t10.ctypes.data_as(_ip)))
         self._tets10, self.ndof_p2 = t10, ndof
 
+    def _herm_table(self, tets20):
+        """(tets20, ndof) of an order="herm" call, checked without the library: the caller's table, or the one on the handle"""
+        if tets20 is None:
+            have = getattr(self, "_tets20", None)
+            if have is None:
+                raise ValueError("order='herm' needs tets20, the second result of assemble.herm_connectivity(points, tets, tris) with the "
+                                 "boundary triangles the family was assembled with")
+            return have, self.ndof_herm
+        t20 = np.asarray(tets20)
+        if t20.shape != (len(self.tets), 20) or not np.issubdtype(t20.dtype, np.integer):
+            raise ValueError(f"tets20 must be an integer array of shape ({len(self.tets)}, 20), got {t20.dtype} {t20.shape}")
+        if t20.min() < 0 or t20.max() >= 2 ** 31 - 1:
+            raise ValueError("tets20 holds an entry that is negative or does not fit 32 bits")
+        return np.ascontiguousarray(t20, dtype=np.int32), int(t20.max()) + 1
+
+    def _set_herm(self, t20, ndof):
+        """the Hermite unknowns of the tetrahedra on the handle, unless they are there already"""
+        have = getattr(self, "_tets20", None)
+        if have is not None and (have is t20 or np.array_equal(have, t20)):
+            return
+        h = self._handle()
+        _lib.check(_lib.lib().wae_hermite_locator_set(h, ndof, t20.ctypes.data_as(_ip)))
+        self._tets20, self.ndof_herm = t20, ndof
+
     def _located(self, X, tet, outside, tol):
         if tet is None:
             tet = self.find(X, tol=tol)
@@ -141,25 +171,29 @@ class Locator:
                                                None if lam is None else lam.ctypes.data_as(_dp)))
         return (tet, lam) if barycentric else tet
 
-    def weights(self, X, order="lin", kind="p", n=None, tet=None, tets10=None, outside="raise", tol=0.0):
+    def weights(self, X, order="lin", kind="p", n=None, tet=None, tets10=None, outside="raise", tol=0.0, tets20=None):
         """The rows of ``probe.probe_p`` (kind "p") or ``probe.probe_n_grad_p`` (kind "n_grad_p", n: one direction (3,) or one per point) at
         every row of X: (idx, val) of shape (nq, 4) for order "lin", (nq, 10) for "quad" (``tets10``: the second result of
-        ``p2_connectivity`` if the caller has it).  ``tet``: the tetrahedra of the points if known, else ``find(X, tol)``.  A point in no
+        ``p2_connectivity`` if the caller has it), (nq, 20) for "herm" (``tets20``: the second result of ``herm_connectivity``, needed by
+        the first "herm" call; the rows act on the values, the physical gradients and the face values in the local order of tets20).
+        ``tet``: the tetrahedra of the points if known, else ``find(X, tol)``.  A point in no
         tetrahedron: ValueError naming the first (``outside="raise"``), or a row of idx 0, val 0 (``outside="nan"``)."""
         X, n, tet = self._row_args(X, order, kind, n, tet, outside)
+        if order == "herm":
+            self._set_herm(*self._herm_table(tets20))
         if order == "quad":
             self._set_p2(tets10)
         tet = self._located(X, tet, outside, tol)
-        nw = 4 if order == "lin" else 10
+        nw = _NW[order]
         idx, val = np.zeros((len(X), nw), dtype=np.int32), np.zeros((len(X), nw))
         _lib.check(_lib.lib().wae_locator_weights(self._handle(), _ORDERS[order], _KINDS[kind], len(X), X.ctypes.data_as(_dp), tet.ctypes.data_as(_ip),
                                                   None if n is None else n.ctypes.data_as(_dp), idx.ctypes.data_as(_ip), val.ctypes.data_as(_dp)))
         return idx, val
 
-    def sample(self, V, X, order="lin", kind="p", n=None, tet=None, tets10=None, outside="raise", tol=0.0):
+    def sample(self, V, X, order="lin", kind="p", n=None, tet=None, tets10=None, outside="raise", tol=0.0, tets20=None):
         """p (or n . grad p) of every column of V at every row of X: a complex array (nq, ncols), (nq,) for a vector V.  V has one row per
-        unknown: the points (order "lin") or the points and edges of ``assemble_p2`` ("quad").  ``outside="nan"``: NaN rows for the points
-        in no tetrahedron."""
+        unknown: the points (order "lin"), the points and edges of ``assemble_p2`` ("quad") or the 4 npoints + nfaces unknowns of
+        ``assemble_herm`` ("herm", ``tets20`` as in ``weights``).  ``outside="nan"``: NaN rows for the points in no tetrahedron."""
         X, n, tet = self._row_args(X, order, kind, n, tet, outside)
         V = np.asarray(V)
         if V.ndim not in (1, 2) or V.size == 0 or not (np.issubdtype(V.dtype, np.floating) or np.issubdtype(V.dtype, np.complexfloating)
@@ -167,6 +201,11 @@ class Locator:
             raise ValueError(f"V must be a real or complex vector or matrix, got {V.dtype} {V.shape}")
         if order == "lin" and V.shape[0] != len(self.points):
             raise ValueError(f"V has {V.shape[0]} rows, the mesh has {len(self.points)} points")
+        if order == "herm":
+            t20, ndof = self._herm_table(tets20)
+            if V.shape[0] != ndof:
+                raise ValueError(f"V has {V.shape[0]} rows, the Hermite space of tets20 has {ndof} unknowns")
+            self._set_herm(t20, ndof)
         if order == "quad":
             self._set_p2(tets10)
             if V.shape[0] != self.ndof_p2:
@@ -180,22 +219,52 @@ class Locator:
                                                  out.ctypes.data_as(_dp)))
         return out[:, 0] if V.ndim == 1 else out
 
-    def observers(self, X, order="lin", kind="p", n=None, tet=None, tets10=None, tol=0.0):
+    def observers(self, X, order="lin", kind="p", n=None, tet=None, tets10=None, tol=0.0, tets20=None):
         """the list of (idx, val) pairs, one per row of X, that ``nlevp.forced_response(..., observers=...)`` takes: a microphone array
         in one call.  Every point must lie in the mesh."""
-        idx, val = self.weights(X, order, kind, n, tet, tets10, "raise", tol)
+        idx, val = self.weights(X, order, kind, n, tet, tets10, "raise", tol, tets20)
         return [(idx[q].copy(), val[q].copy()) for q in range(len(idx))]
 
-    def interpolation(self, X, order="lin", tets10=None, tol=1e-10):
+    def interpolation(self, X, order="lin", tets10=None, tol=1e-10, tets20=None):
         """The interpolation onto the points X as a ``scipy.sparse.csr_matrix`` (nq x unknowns of this mesh) in the format of
         ``RefinedMesh.prolongator``: columns ascending, exact zeros kept out.  Every point must lie in the mesh.  The points of another
         mesh sit on vertices and faces of this one, where rounding leaves a coordinate at -1e-17 as often as at 0: the default ``tol`` is
         1e-10, not the 0 of ``find``."""
-        idx, val = self.weights(X, order, "p", None, None, tets10, "raise", tol)
+        idx, val = self.weights(X, order, "p", None, None, tets10, "raise", tol, tets20)
         nq, nw = idx.shape
-        ncol = len(self.points) if order == "lin" else self.ndof_p2
+        ncol = len(self.points) if order == "lin" else (self.ndof_p2 if order == "quad" else self.ndof_herm)
         o = np.argsort(idx, axis=1, kind="stable")
         idx, val = np.take_along_axis(idx, o, axis=1), np.take_along_axis(val, o, axis=1)
         keep = val != 0.0
         ptr = np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int32)
         return sp.csr_matrix((val[keep], idx[keep].astype(np.int32), ptr), shape=(nq, ncol))
+
+    def herm_transfer(self, V, points2, tets2, tris2=None, tets20=None, tol=1e-10):
+        """The Hermite unknowns on another mesh (points2, tets2, boundary triangles tris2) of the field that the Hermite vector(s) V
+        represent on this one: an array (ndof2, ncols), (ndof2,) for a vector V, in the order of ``assemble.herm_dofs`` -- the values, then
+        the x, y, z derivatives at ``points2``, then the values at the face centroids of mesh 2, ``tris2`` first, then the faces that
+        ``herm_connectivity(points2, tets2, tris2)`` returns.  This is how an eigenpair of a coarse Hermite mesh becomes a start vector
+        on a finer one, nested or not.  One ``find`` for the points, one for the centroids, and ``sample`` with the found tetrahedra;
+        every point and centroid must lie in this mesh (to ``tol``).  The field is C0 only: where a point of mesh 2 lies on an element
+        boundary of this mesh, the gradient is that of the lowest-numbered tetrahedron holding the point."""
+        from .assemble import _herm_mesh_checked, herm_connectivity
+        p2, t2, s2 = _herm_mesh_checked(points2, tets2, tris2)
+        if t2.min() < 0 or t2.max() >= len(p2) or (s2 is not None and s2.size and (s2.min() < 0 or s2.max() >= len(p2))):
+            raise ValueError("tets2 or tris2 refers to a point outside points2")
+        V = np.asarray(V)
+        if V.ndim not in (1, 2) or V.size == 0 or V.dtype.kind not in "fciu":
+            raise ValueError(f"V must be a real or complex vector or matrix, got {V.dtype} {V.shape}")
+        t20, ndof = self._herm_table(tets20)
+        if V.shape[0] != ndof:
+            raise ValueError(f"V has {V.shape[0]} rows, the Hermite space of tets20 has {ndof} unknowns")
+        self._set_herm(t20, ndof)
+        faces2 = herm_connectivity(p2, t2, s2, device=self.device)[0]
+        allf = faces2 if s2 is None else np.concatenate([s2, faces2])
+        cen = p2[allf].mean(axis=1).reshape(-1, 3)
+        tp = self._located(p2, None, "raise", tol)
+        blocks = [self.sample(V, p2, "herm", tet=tp)]
+        for e in np.eye(3):
+            blocks.append(self.sample(V, p2, "herm", "n_grad_p", n=e, tet=tp))
+        if len(cen):
+            blocks.append(self.sample(V, cen, "herm", tet=self._located(cen, None, "raise", tol)))
+        return np.concatenate(blocks, axis=0)
